@@ -13,9 +13,12 @@ Multi-GPU (--gpus N via torch.distributed.run): independent prompts shard across
 rank owns a full replica of its weights and runs the same per-GPU work ("scaling": "weak"); the
 only collective is the timing barrier / max-reduction (no data-path exchange exists).
 
-Extra fields: "roofline" (dominant kernel: algorithmic bytes per launch / HIP-event duration on
-the backend's own stream, vs 8 TB/s HBM), "cpu_baseline" (the reference ggml CPU backend,
-oracle/_ref/libggml_ref.so, timed on this host -- rank 0, N=1 only) and a per-config sweep.
+A plain run sets up, warms up, times --steps steps and prints the result line; its one extra
+field is "roofline" (dominant kernel: algorithmic bytes per launch / HIP-event duration of the
+timed steps on the backend's own stream, vs 8 TB/s HBM). --dump-outputs DIR writes what the last
+timed step computed (DIR/y.npy). Everything that takes runs of its own is behind --full:
+"cpu_baseline" (the reference ggml CPU backend, oracle/_ref/libggml_ref.so, timed on this host
+-- rank 0, N=1 only), the per-config sweep, the GPT-2 legs and the multi-GPU prefill legs.
 """
 from __future__ import annotations
 
@@ -73,9 +76,29 @@ class MulMatWorkload:
         st = self.lib.ggml_backend_graph_compute_async(self.backend, self.graph)
         assert st == 0, st
 
+    def outputs(self):
+        """What a caller of step() receives: the R products Y_r, f32 [R, B, N] (read back after a
+        backend synchronize)."""
+        return np.stack([G.tensor_get(self.lib, y) for y in self.y]).reshape(self.R, self.B, self.N)
+
     def free(self):
         self.lib.ggml_backend_buffer_free(self.buf)
         self.ctx.free()
+
+
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir, y):
+    """--dump-outputs: the last timed step's Y as out_dir/y.npy (f32 [R, B, N]). An output larger
+    than DUMP_LIMIT_BYTES is cut to a fixed sample of its flattened elements (seed 0, ascending
+    positions), the same positions in every run with the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    keep = DUMP_LIMIT_BYTES // y.itemsize
+    if y.size > keep:
+        y = y.reshape(-1)[np.sort(np.random.default_rng(0).choice(y.size, keep, replace=False))]
+    np.save(os.path.join(out_dir, "y.npy"), y)
 
 
 def host_cpus():
@@ -540,6 +563,9 @@ def main():
     ap.add_argument("--N", type=int, default=4096)
     ap.add_argument("--B", type=int, default=1)
     ap.add_argument("--rotate", type=int, default=32)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/y.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: config sweep, GPT-2, CPU baselines, multi-GPU prefill")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
@@ -594,6 +620,8 @@ def main():
         ev1.record(ext_stream)
 
     dt = timed_region(run_steps, sync, dist, coll_device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl.outputs())
 
     ub = unit_bytes(t, K, N, B)
     value = R * ub * args.steps * world / dt / 1e9
@@ -637,7 +665,7 @@ def main():
                              "the kernel; traffic = PMC HBM bytes per launch (tools/pmc_traffic.py, gfx950-corrected)"},
     }
 
-    if rank == 0 and world == 1 and not args.no_sweep:
+    if args.full and rank == 0 and world == 1 and not args.no_sweep:
         sweep = {}
         for name, tt, k, n in (("q4_0_4096x4096", 2, 4096, 4096), ("q4_K_4096x11008", 12, 4096, 11008),
                                ("q5_K_4096x11008", 13, 4096, 11008), ("q8_0_4096x11008", 8, 4096, 11008)):
@@ -701,7 +729,7 @@ def main():
             sweep[f"q4_K_4096x4096_b{bb}_prefill"] = e
         result["sweep"] = sweep
 
-    if world > 1 and not args.no_sweep:
+    if args.full and world > 1 and not args.no_sweep:
         # BASELINE config 5: ONE B=512 prefill (Q4_K 4096x4096) prompt-sharded across the GPUs --
         # each rank runs its columns against its own weight replica; no data-path collective
         start, cnt = shard_range(512, world, rank)
@@ -719,7 +747,7 @@ def main():
                                      "us_per_mul_mat": round(dtp / 5 / 8 * 1e6, 2)}
         w4.free()
 
-    if world > 1 and not args.no_sweep:
+    if args.full and world > 1 and not args.no_sweep:
         # the optional tensor-split row path (RCCL): reported beside the main line, never fatal to it
         try:
             if dist_backend != "nccl":
@@ -728,7 +756,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             result["prefill_rowsplit_rccl"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0 and world == 1 and not args.no_gpt2:
+    if args.full and rank == 0 and world == 1 and not args.no_gpt2:
         # BASELINE config 4 (the metric's "+ GPT-2 tokens/s" half)
         result["gpt2"] = gpt2_f16_bench(lib, backend, args.gpt2_tokens)
         result["gpt2_q4_k"] = gpt2_q4k_bench(lib, backend, args.gpt2_tokens)
@@ -737,7 +765,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             result["gpt2_batched"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         result["cpu_baseline"] = cpu_baseline(t, K, N, B, args.cpu_seconds)
         threads = host_cpus()["threads"]
         if "gpt2" in result:

@@ -65,6 +65,40 @@ def test_torch_view_and_rowsplit_leg():
     assert out["same_as_direct"]
 
 
+def test_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """A plain bench.py run does the headline alone (the legs that take runs of their own are
+    behind --full), --steps sets the timed steps, and --dump-outputs writes the last step's
+    products: f32 [R, B, N], within 1e-3 of max|y| of the CPU oracle's mul_mat on the same seeded
+    inputs (the bound __graft_entry__.smoke() holds the same kernel to)."""
+    import pyoracle as orc
+    from ggml_mi355x import ggml as G, synth
+    K, N, R = 4096, 512, 4
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--N", str(N),
+           "--rotate", str(R), "--dump-outputs", str(tmp_path / "dump")]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=200, cwd=REPO)
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["n_gpus"] == 1
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["unit"] == "GB/s" and out["higher_is_better"] is True
+    for leg in ("sweep", "gpt2", "gpt2_q4_k", "gpt2_batched", "cpu_baseline", "prefill_sharded", "prefill_rowsplit_rccl"):
+        assert leg not in out, leg
+    assert os.listdir(tmp_path / "dump") == ["y.npy"]
+    y = np.load(tmp_path / "dump" / "y.npy")
+    assert y.dtype == np.float32 and y.shape == (R, 1, N)
+    # the workload's inputs, rebuilt as MulMatWorkload seeds them
+    rt = G.runtime()
+    with G.Context(rt, 1024, no_alloc=True):
+        pass  # ggml_init: the fp16 tables ggml_quantize_chunk's rounding reads
+    wf = synth.uniform(42, K * N)
+    wq = np.empty(G.row_size(12, K) * N, np.uint8)
+    rt.ggml_quantize_chunk(12, wf.ctypes.data, wq.ctypes.data, 0, N, K, None)
+    x = np.concatenate([synth.uniform(43 + r, K) for r in range(R)])
+    ref = orc.mul_mat(orc.Q4_K, wq, K, N, x, R).reshape(R, 1, N)
+    assert float(np.abs(y - ref).max() / np.abs(ref).max()) <= 1e-3
+
+
 def test_bench_two_ranks_rehearsal():
     """bench.py's world > 1 branches end to end before the driver's 8-GPU run: two ranks launched by
     torch.distributed.run as the driver launches them, sharing this box's one GPU over the gloo
@@ -78,8 +112,8 @@ def test_bench_two_ranks_rehearsal():
         port = s.getsockname()[1]
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-gpt2",
-           "--no-cpu"]
+           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+           "--no-gpt2", "--no-cpu"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400, cwd=REPO)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

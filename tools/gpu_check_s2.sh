@@ -4,5 +4,5 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $OUT/pytest_gpu.log 2>&1 || { tail -30 $OUT/pytest_gpu.log; exit 1; }
 tail -3 $OUT/pytest_gpu.log
-timeout -k 10 400 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
