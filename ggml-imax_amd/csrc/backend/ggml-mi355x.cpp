@@ -513,7 +513,7 @@ static void scratch_reserve(mi_backend_ctx * ctx, size_t bytes) {
 // ---------------------------------------------------------------------------------------------
 
 static bool mm_src0_supported(ggml_type t) {
-    return t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K ||
+    return t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K ||
            t == GGML_TYPE_F16 || t == GGML_TYPE_F32;
 }
 
@@ -523,7 +523,7 @@ static bool is_f16_or_f32(const ggml_tensor * t) { return t && (t->type == GGML_
 // the quantized vec_dot_type a src1 may already have for weight type t (GGML_TYPE_COUNT: none)
 static ggml_type q8_src1_type(ggml_type t) {
     switch (t) {
-        case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: return GGML_TYPE_Q8_K;
+        case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: return GGML_TYPE_Q8_K;
         case GGML_TYPE_Q4_0: case GGML_TYPE_Q8_0: return GGML_TYPE_Q8_0;
         default: return GGML_TYPE_COUNT;
     }
@@ -543,7 +543,7 @@ static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
             if (!mm_src0_supported(a->type)) return false;
             if (a->nb[0] != ggml_type_size(a->type) || b->nb[0] != ggml_type_size(b->type)) return false;
             // src1 F32, or src1 already of the weight's vec_dot_type, which the reference CPU reads as
-            // it lies (ggml.c:11952; F16 x F16, Q4_K/Q5_K x Q8_K, Q4_0/Q8_0 x Q8_0): the quantized
+            // it lies (ggml.c:11952; F16 x F16, Q4_K/Q5_K/Q6_K x Q8_K, Q4_0/Q8_0 x Q8_0): the quantized
             // ones with whole superblocks, on the device's own weights
             // (the split-buffer path converts an F32 src1 on the main device: F16 src1 only unsplit)
             if (b->type == GGML_TYPE_F32 || (b->type == GGML_TYPE_F16 && a->type == GGML_TYPE_F16 && !is_split_tensor(a))) return true;
@@ -578,7 +578,7 @@ static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
             }
         case GGML_OP_GET_ROWS:
             return (is_f16_or_f32(a) || a->type == GGML_TYPE_Q4_0 || a->type == GGML_TYPE_Q8_0 || a->type == GGML_TYPE_Q4_K ||
-                    a->type == GGML_TYPE_Q5_K) &&
+                    a->type == GGML_TYPE_Q5_K || a->type == GGML_TYPE_Q6_K) &&
                    b->type == GGML_TYPE_I32 && is_f32(op);
         case GGML_OP_CPY:
         case GGML_OP_DUP:
@@ -612,7 +612,7 @@ static bool mi_offload_op(ggml_backend_t, const ggml_tensor * op) {
 static int act_kind(ggml_type wtype) {
     switch (wtype) {
         case GGML_TYPE_Q4_0: case GGML_TYPE_Q8_0: return 0;
-        case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: return 1;
+        case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: return 1;
         case GGML_TYPE_F16: return 2;
         default: return -1;
     }
@@ -726,7 +726,9 @@ static bool mm_batched(const mi_mm_desc & m, const ggml_tensor * src1) {
 // The activation format mul_mat_run converts src1 to for this mul_mat (act_bytes kinds), or -1
 // (F32 weights: src1 is read as it lies). Q4_K / Q5_K prompts: the exact-integer int8 GEMM's
 // q8_K layouts (8); Q4_0 / Q8_0 prompts: its q8_0 layouts (9); F16 prompts: f16 operands (2, or
-// K-blocked 5); decode: q8 SoA (0 / 1) or f16 (2).
+// K-blocked 5); decode: q8 SoA (0 / 1) or f16 (2). Q6_K has neither an exact MFMA GEMM nor a
+// dequantizer in the f16 GEMM (mi_mmq_supported / mi_mmqx_supported refuse it): q8_K SoA (1) at
+// any column count, the GEMV runs the prompt in 8-column chunks.
 static int mm_act_kind(const mi_mm_desc & m, const ggml_tensor * src1) {
     const int kind = act_kind((ggml_type) m.type);
     if (kind < 0) return -1;
@@ -1284,6 +1286,14 @@ static bool overlaps(const ggml_tensor * a, const ggml_tensor * b) {
     return a0 < b0 + ggml_nbytes(b) && b0 < a0 + ggml_nbytes(a);
 }
 
+// the streaming GEMV's weight alignment: 16-byte rows, except Q6_K, whose 210-byte blocks its
+// loads re-align themselves (rows of an odd superblock count are 2 mod 4: K = 11008 has 9030-byte
+// rows) -- a 16-byte tensor base and 2-byte rows
+static bool fused_weight_aligned(const ggml_tensor * a) {
+    if (a->type == GGML_TYPE_Q6_K) return (uintptr_t) a->data % 16 == 0 && a->nb[1] % 2 == 0;
+    return ((uintptr_t) a->data | a->nb[1]) % 16 == 0;
+}
+
 static bool fused_mv_eligible(const ggml_tensor * n) {
     if (n->op != GGML_OP_MUL_MAT || is_split_tensor(n->src[0])) return false;
     const ggml_tensor * a = n->src[0];
@@ -1291,7 +1301,7 @@ static bool fused_mv_eligible(const ggml_tensor * n) {
     if (b->type != GGML_TYPE_F32 || !mi_mmv_fused_supported(a->type, a->ne[0], b->ne[1])) return false;
     if (a->ne[2] != 1 || a->ne[3] != 1 || b->ne[2] != 1 || b->ne[3] != 1) return false;
     if (a->nb[0] != ggml_type_size(a->type) || b->nb[0] != sizeof(float) || n->nb[0] != sizeof(float)) return false;
-    if (((uintptr_t) a->data | a->nb[1]) % 16 != 0 || ((uintptr_t) b->data | b->nb[1]) % 16 != 0) return false;
+    if (!fused_weight_aligned(a) || ((uintptr_t) b->data | b->nb[1]) % 16 != 0) return false;
     return true;
 }
 
@@ -1952,11 +1962,13 @@ static bool ord_prefill_chunked(const ggml_tensor * n) {
     const ggml_tensor * a = n->src[0];
     const ggml_tensor * b = n->src[1];
     if (b->type != GGML_TYPE_F32 || b->ne[1] <= 8 || b->ne[1] > (mi_mmv_order() == 1 ? g_ord_prefill_cols : g_tree_prefill_cols)) return false;
-    if (a->type != GGML_TYPE_Q4_K && a->type != GGML_TYPE_Q5_K && a->type != GGML_TYPE_Q4_0 && a->type != GGML_TYPE_Q8_0) return false;
+    if (a->type != GGML_TYPE_Q4_K && a->type != GGML_TYPE_Q5_K && a->type != GGML_TYPE_Q6_K && a->type != GGML_TYPE_Q4_0 &&
+        a->type != GGML_TYPE_Q8_0)
+        return false;
     if (!mi_mmv_fused_supported(a->type, a->ne[0], 8)) return false;
     if (a->ne[2] != 1 || a->ne[3] != 1 || b->ne[2] != 1 || b->ne[3] != 1) return false;
     if (a->nb[0] != ggml_type_size(a->type) || b->nb[0] != sizeof(float) || n->nb[0] != sizeof(float)) return false;
-    if (((uintptr_t) a->data | a->nb[1]) % 16 != 0 || ((uintptr_t) b->data | b->nb[1]) % 16 != 0 || n->nb[1] % sizeof(float)) return false;
+    if (!fused_weight_aligned(a) || ((uintptr_t) b->data | b->nb[1]) % 16 != 0 || n->nb[1] % sizeof(float)) return false;
     return !overlaps(n, a) && !overlaps(n, b);
 }
 

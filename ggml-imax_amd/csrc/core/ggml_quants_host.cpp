@@ -1,5 +1,5 @@
 // ggml_quants_host.cpp -- ggml_quantize_chunk (include/ggml/ggml.h:2240-2254) for the weight
-// formats on the hot path: Q4_0, Q8_0, Q4_K, Q5_K (+ F16 / F32 passthrough).
+// formats on the hot path: Q4_0, Q8_0, Q4_K, Q5_K, Q6_K (+ F16 / F32 passthrough).
 //
 // These produce the bytes the MI355X kernels consume. They must be bit-identical to the
 // reference's imatrix == NULL path (src/ggml.c:21594-21660 -> src/ggml-quants.c reference
@@ -22,7 +22,9 @@ struct blk_q4_0 { ggml_fp16_t d; uint8_t qs[16]; };
 struct blk_q8_0 { ggml_fp16_t d; int8_t qs[32]; };
 struct blk_q4_K { ggml_fp16_t d, dmin; uint8_t scales[12]; uint8_t qs[128]; };
 struct blk_q5_K { ggml_fp16_t d, dmin; uint8_t scales[12]; uint8_t qh[32]; uint8_t qs[128]; };
+struct blk_q6_K { uint8_t ql[128]; uint8_t qh[64]; int8_t scales[16]; ggml_fp16_t d; };
 static_assert(sizeof(blk_q4_0) == 18 && sizeof(blk_q8_0) == 34 && sizeof(blk_q4_K) == 144 && sizeof(blk_q5_K) == 176, "blocks");
+static_assert(sizeof(blk_q6_K) == 210, "blocks");
 
 // src/ggml-quants.c:1097-1102: round half to even through the 1.5*2^23 bias
 inline int rne_int(float v) {
@@ -225,6 +227,128 @@ void quantize_q5_K_rows(const float * x, blk_q5_K * y, int64_t n) {
     }
 }
 
+// nearest_int(a * b) as the reference's -mfma build computes it: the product is contracted into
+// the bias add, fma(a, b, 1.5 * 2^23)
+inline int rne_int_fma(float a, float b) {
+    float t = fmaf(a, b, 12582912.f);
+    int32_t bits;
+    memcpy(&bits, &t, 4);
+    return (bits & 0x007fffff) - 0x00400000;
+}
+
+// a product rounded to f32 on its own, which the compiler may not contract into a following add
+inline float mul_rn(float a, float b) {
+    float r = a * b;
+    __asm__("" : "+x"(r));
+    return r;
+}
+
+// src/ggml-quants.c:1104-1171 make_qx_quants(n = 16, nmax = 32, rmse_type = 1, qw = NULL): the
+// symmetric scale of one 16-element sub-block, weights x^2, searched over 19 candidate scales.
+// L gets the levels + 32. The roundings are written out as the reference's x86 build
+// (make_qx_quants.constprop, gcc -O3 -mfma) performs them, because they differ between its loops:
+// the first pass is scalar and contracts sumlx = fma(w*x, l, sumlx), suml2 = fma(w*l, l, suml2);
+// the candidate loop is vectorised, so its products (w*x)*l and (w*l)*l are rounded on their own
+// and then added in element order; nmax + 0.1f*is is one fma (nmax is a run-time argument there).
+float search_scale_sym16(const float * x, int8_t * L) {
+    constexpr int n = 16, nmax = 32;
+    float max = 0;
+    float amax = 0;
+    for (int i = 0; i < n; ++i) {
+        float ax = fabsf(x[i]);
+        if (ax > amax) { amax = ax; max = x[i]; }
+    }
+    if (amax < 1e-30f) {  // all zero
+        for (int i = 0; i < n; ++i) L[i] = 0;
+        return 0.f;
+    }
+    float iscale = -nmax / max;
+    float sumlx = 0;
+    float suml2 = 0;
+    for (int i = 0; i < n; ++i) {
+        int l = rne_int_fma(iscale, x[i]);
+        l = std::max(-nmax, std::min(nmax - 1, l));
+        L[i] = (int8_t) (l + nmax);
+        float w = x[i] * x[i];
+        sumlx = fmaf(w * x[i], (float) l, sumlx);
+        suml2 = fmaf(w * (float) l, (float) l, suml2);
+    }
+    float scale = sumlx / suml2;
+    float best = scale * sumlx;
+    for (int is = -9; is <= 9; ++is) {
+        if (is == 0) continue;
+        iscale = -fmaf(0.1f, (float) is, (float) nmax) / max;
+        sumlx = suml2 = 0;
+        for (int i = 0; i < n; ++i) {
+            int l = rne_int_fma(iscale, x[i]);
+            l = std::max(-nmax, std::min(nmax - 1, l));
+            float w = x[i] * x[i];
+            sumlx += mul_rn(w * x[i], (float) l);
+            suml2 += mul_rn(w * (float) l, (float) l);
+        }
+        if (suml2 > 0 && sumlx * sumlx > best * suml2) {
+            for (int i = 0; i < n; ++i) {
+                int l = rne_int_fma(iscale, x[i]);
+                L[i] = (int8_t) (nmax + std::max(-nmax, std::min(nmax - 1, l)));
+            }
+            scale = sumlx / suml2;
+            best = scale * sumlx;
+        }
+    }
+    return scale;
+}
+
+// src/ggml-quants.c:2631-2711 quantize_row_q6_K_reference
+void quantize_q6_K_rows(const float * x, blk_q6_K * y, int64_t n) {
+    int8_t L[kQKK];
+    float scales[kQKK / 16];
+    for (int64_t b = 0; b < n / kQKK; ++b, x += kQKK) {
+        float max_scale = 0;
+        float max_abs_scale = 0;
+        for (int ib = 0; ib < kQKK / 16; ++ib) {
+            const float scale = search_scale_sym16(x + 16 * ib, L + 16 * ib);
+            scales[ib] = scale;
+            const float abs_scale = fabsf(scale);
+            if (abs_scale > max_abs_scale) {
+                max_abs_scale = abs_scale;
+                max_scale = scale;
+            }
+        }
+        if (!max_abs_scale) {
+            memset(&y[b], 0, sizeof(blk_q6_K));
+            y[b].d = ggml_fp32_to_fp16(0.f);
+            continue;
+        }
+        float iscale = -128.f / max_scale;
+        y[b].d = ggml_fp32_to_fp16(1 / iscale);
+        for (int ib = 0; ib < kQKK / 16; ++ib) y[b].scales[ib] = (int8_t) std::min(127, rne_int_fma(iscale, scales[ib]));
+        for (int j = 0; j < kQKK / 16; ++j) {
+            float d = ggml_fp16_to_fp32(y[b].d) * y[b].scales[j];
+            if (!d) continue;
+            for (int ii = 0; ii < 16; ++ii) {
+                int l = rne_int(x[16 * j + ii] / d);
+                l = std::max(-32, std::min(31, l));
+                L[16 * j + ii] = (int8_t) (l + 32);
+            }
+        }
+        uint8_t * ql = y[b].ql;
+        uint8_t * qh = y[b].qh;
+        for (int j = 0; j < kQKK; j += 128) {
+            for (int l = 0; l < 32; ++l) {
+                const uint8_t q1 = L[j + l + 0] & 0xF;
+                const uint8_t q2 = L[j + l + 32] & 0xF;
+                const uint8_t q3 = L[j + l + 64] & 0xF;
+                const uint8_t q4 = L[j + l + 96] & 0xF;
+                ql[l + 0] = (uint8_t) (q1 | (q3 << 4));
+                ql[l + 32] = (uint8_t) (q2 | (q4 << 4));
+                qh[l] = (uint8_t) ((L[j + l] >> 4) | ((L[j + l + 32] >> 4) << 2) | ((L[j + l + 64] >> 4) << 4) | ((L[j + l + 96] >> 4) << 6));
+            }
+            ql += 64;
+            qh += 32;
+        }
+    }
+}
+
 } // namespace
 
 extern "C" {
@@ -252,6 +376,7 @@ size_t ggml_quantize_chunk(enum ggml_type type, const float * src, void * dst, i
         case GGML_TYPE_Q8_0: quantize_q8_0_rows(in, (blk_q8_0 *) out, n); break;
         case GGML_TYPE_Q4_K: quantize_q4_K_rows(in, (blk_q4_K *) out, n); break;
         case GGML_TYPE_Q5_K: quantize_q5_K_rows(in, (blk_q5_K *) out, n); break;
+        case GGML_TYPE_Q6_K: quantize_q6_K_rows(in, (blk_q6_K *) out, n); break;
         case GGML_TYPE_F16: ggml_fp32_to_fp16_row(in, (ggml_fp16_t *) out, n); break;
         case GGML_TYPE_F32: memcpy(out, in, (size_t) n * sizeof(float)); break;
         default: GGML_ASSERT(!"ggml_quantize_chunk: type not supported by this runtime");

@@ -14,6 +14,7 @@
 //   Q8_0 x Q8_0  ggml_vec_dot_q8_0_q8_0  src/ggml-quants.c:4819+
 //   Q4_K x Q8_K  ggml_vec_dot_q4_K_q8_K  src/ggml-quants.c:7007-7502
 //   Q5_K x Q8_K  ggml_vec_dot_q5_K_q8_K  src/ggml-quants.c:7833-8378
+//   Q6_K x Q8_K  ggml_vec_dot_q6_K_q8_K  src/ggml-quants.c:8730-9310
 // (F16 and F32 live in mmv_ordered.hip: bit-exact CPU summation order.)
 
 #include "mi355x_common.h"
@@ -357,6 +358,152 @@ __global__ __launch_bounds__(256) void k_mmv_kq_ord(const uint8_t * __restrict__
     }
 }
 
+// ---------------------------------------------------------------- Q6_K x Q8_K
+//
+// ggml_vec_dot_q6_K_q8_K (src/ggml-quants.c:8838-8915, the AVX2 branch). A 210-byte block is
+// ql[128] | qh[64] | int8 scales[16] | fp16 d; element e of the superblock is
+// d * scales[e / 16] * (q - 32) with q in 0..63. For the 128-half h, byte p (0..31):
+//   ql[64h + p]      low nibble -> element 128h + p,      high nibble -> element 128h + 64 + p
+//   ql[64h + 32 + p] low nibble -> element 128h + 32 + p, high nibble -> element 128h + 96 + p
+//   qh[32h + p]      bits 2t, 2t+1 -> bits 4, 5 of element 128h + 32t + p
+// Blocks are only 2-byte aligned (210 = 2 * 105; rows of an odd superblock count are 2 mod 4):
+// every load is an aligned dword (+ v_alignbyte) or narrower, never a uint4 on a block address.
+
+// bytes of q (each 0..63) -> bytes of q - 32 as int8, no carries between the bytes:
+// (q + 128 - 32) never borrows, the xor takes the 128 back out mod 256
+__device__ __forceinline__ int q6_center(uint32_t q) { return (int) (((q | 0x80808080u) - 0x20202020u) ^ 0x80808080u); }
+
+// a dword at a 2-byte aligned address from the two aligned dwords covering it
+__device__ __forceinline__ uint32_t ld32_a2(const uint8_t * p) {
+    const uintptr_t a = (uintptr_t) p;
+    const uint32_t * w = (const uint32_t *) (a & ~(uintptr_t) 3);
+    const uint32_t lo = w[0];
+    const uint32_t hi = (a & 3) ? w[1] : 0u;
+    return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t) (a & 3));
+}
+
+// Tree order: one wave per row, an item is (superblock s, 128-half h, 16-byte lane range u): the
+// four 16-element sub-blocks at elements 128h + 32t + 16u (t = 0..3), scale index 8h + 2t + u.
+// Four items per superblock, so a K = 4096 row is one item per lane. The item's integer sum
+// (up to 4 * 8,323,072, over 2^24) is accumulated in int32 and converted once.
+template <int NC>
+__global__ __launch_bounds__(256) void k_mmv_q6k(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t) blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+    if (row >= g.N) return;
+    int64_t i11, i12, i13, i02, i03;
+    mmv_coords(g, NC, i11, i12, i13, i02, i03);
+    const uint8_t * wrow = W + i02 * g.nb02 + i03 * g.nb03 + row * g.nb01;
+    const int nsb = (int) (g.K / 256);
+    const int64_t col0 = i11 + g.ne11 * (i12 + g.ne12 * i13);
+
+    float acc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) acc[c] = 0.0f;
+
+    for (int it = lane; it < 4 * nsb; it += 64) {
+        const int s = it >> 2;
+        const int h = (it >> 1) & 1;
+        const int u = it & 1;
+        const uint8_t * blk = wrow + (size_t) s * 210;
+        uint32_t la[4], lb[4], hh[4];
+        load_qs_unaligned<16>(blk + 64 * h + 16 * u, la);
+        load_qs_unaligned<16>(blk + 64 * h + 32 + 16 * u, lb);
+        load_qs_unaligned<16>(blk + 128 + 32 * h + 16 * u, hh);
+        int q[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            q[0][i] = q6_center((la[i] & 0x0F0F0F0Fu) | ((hh[i] & 0x03030303u) << 4));
+            q[1][i] = q6_center((lb[i] & 0x0F0F0F0Fu) | (((hh[i] >> 2) & 0x03030303u) << 4));
+            q[2][i] = q6_center(((la[i] >> 4) & 0x0F0F0F0Fu) | (((hh[i] >> 4) & 0x03030303u) << 4));
+            q[3][i] = q6_center(((lb[i] >> 4) & 0x0F0F0F0Fu) | (((hh[i] >> 6) & 0x03030303u) << 4));
+        }
+        const int8_t * scp = (const int8_t *) blk + 192 + 8 * h + u;
+        const int sc[4] = {scp[0], scp[2], scp[4], scp[6]};
+        const float dw = mi_h2f(*(const uint16_t *) (blk + 208));
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            if (NC > 1 && i11 + c >= g.ne11) break;
+            const int64_t col = col0 + c;
+            const int4 * a = (const int4 *) (act.qs + col * g.K + (int64_t) s * 256 + 128 * h + 16 * u);
+            int sumi = 0;
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const int4 av = a[2 * t];
+                int p = mi_dot4(q[t][0], av.x, 0);
+                p = mi_dot4(q[t][1], av.y, p);
+                p = mi_dot4(q[t][2], av.z, p);
+                p = mi_dot4(q[t][3], av.w, p);
+                sumi += sc[t] * p;
+            }
+            acc[c] += (act.d[col * nsb + s] * dw) * (float) sumi;
+        }
+    }
+    mmv_store<NC>(g, dst, row, i11, i12, i13, acc, lane);
+}
+
+// Reference order: the AVX2 dot keeps eight int32 lanes per superblock, lane l = sum over the
+// eight 32-element groups g of scales[2g + (l >= 4)] * sum_{e = 4l..4l+3} (q - 32)[32g + e] * a[32g + e]
+// (maddubs pairs, the -32 taken as maddubs(32, a) and subtracted, then madd_epi16 with the
+// sign-extended scales: no step saturates, |pair| <= 2 * 63 * 127), then acc[l] = fma(y.d * fp16(x.d),
+// (float) sumi[l], acc[l]) over the superblocks in order and hsum_float_8. A lane sum is at most
+// 8 * 128 * 4 * 32 * 127 = 16,646,144 < 2^24, so the conversion is exact. Here eight lanes are the
+// eight CPU lanes of one row (8 rows per wave), as k_mmv_kq_ord.
+template <int NC>
+__global__ __launch_bounds__(256) void k_mmv_q6k_ord(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
+    const int l = threadIdx.x & 7;
+    const int64_t row = (int64_t) blockIdx.x * 32 + (threadIdx.x >> 3);
+    const bool live = row < g.N;
+    const int64_t rc = live ? row : g.N - 1;  // (dead groups run a valid row: no early exit before the shuffles)
+    int64_t i11, i12, i13, i02, i03;
+    mmv_coords(g, NC, i11, i12, i13, i02, i03);
+    const uint8_t * wrow = W + i02 * g.nb02 + i03 * g.nb03 + rc * g.nb01;
+    const int nsb = (int) (g.K / 256);
+    const int64_t col0 = i11 + g.ne11 * (i12 + g.ne12 * i13);
+    const int hi = l >> 2;  // which 16-element half of each 32-group the lane's elements lie in
+
+    float A[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) A[c] = 0.0f;
+
+    for (int s = 0; s < nsb; s++) {
+        const uint8_t * blk = wrow + (size_t) s * 210;
+        const float dw = mi_h2f(*(const uint16_t *) (blk + 208));
+        int q[8], sc[8];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const uint32_t la = ld32_a2(blk + 64 * h + 4 * l);
+            const uint32_t lb = ld32_a2(blk + 64 * h + 32 + 4 * l);
+            const uint32_t hh = ld32_a2(blk + 128 + 32 * h + 4 * l);
+            q[4 * h + 0] = q6_center((la & 0x0F0F0F0Fu) | ((hh & 0x03030303u) << 4));
+            q[4 * h + 1] = q6_center((lb & 0x0F0F0F0Fu) | (((hh >> 2) & 0x03030303u) << 4));
+            q[4 * h + 2] = q6_center(((la >> 4) & 0x0F0F0F0Fu) | (((hh >> 4) & 0x03030303u) << 4));
+            q[4 * h + 3] = q6_center(((lb >> 4) & 0x0F0F0F0Fu) | (((hh >> 6) & 0x03030303u) << 4));
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) sc[j] = ((const int8_t *) blk)[192 + 2 * j + hi];
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            if (NC > 1 && i11 + c >= g.ne11) break;
+            const int64_t col = col0 + c;
+            const int8_t * aq = act.qs + col * g.K + (int64_t) s * 256 + 4 * l;
+            int sumi = 0;
+#pragma unroll
+            for (int j = 0; j < 8; j++) sumi += sc[j] * mi_dot4(q[j], *(const int *) (aq + 32 * j), 0);
+            A[c] = fmaf(act.d[col * nsb + s] * dw, (float) sumi, A[c]);  // _mm256_fmadd_ps(d, cvt(sumi), acc)
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        // hsum_float_8: ((a0 + a4) + (a2 + a6)) + ((a1 + a5) + (a3 + a7))
+        float z = A[c] + __shfl_xor(A[c], 4, 8);
+        z = z + __shfl_xor(z, 2, 8);
+        z = z + __shfl_xor(z, 1, 8);
+        if (l == 0 && live && i11 + c < g.ne11)
+            *(float *) ((char *) dst + (i11 + c) * g.nb1 + i12 * g.nb2 + i13 * g.nb3 + row * sizeof(float)) = z;
+    }
+}
+
 mmv_geom make_geom(const mi_mm_desc & m, int NC) {
     mmv_geom g;
     g.K = m.K;
@@ -433,6 +580,32 @@ void mi_mul_mat_q(const mi_mm_desc & m, const mi_act_q8 & act, hipStream_t s) {
             default: MI_MMV_KORD_LAUNCH(8); break;
         }
 #undef MI_MMV_KORD_LAUNCH
+        return;
+    }
+    if (m.type == 14) {  // Q6_K: reference CPU order (8 rows per wave) or tree order (a wave per row)
+        if (mi_mmv_order() == 1) {
+#define MI_MMV_Q6ORD_LAUNCH(NC)                                                                              \
+        do {                                                                                                  \
+            const mmv_geom g = make_geom(m, NC);                                                              \
+            const dim3 grid((unsigned) ((m.N + 31) / 32), (unsigned) (g.col_chunks * m.ne12 * m.ne13));      \
+            hipLaunchKernelGGL((k_mmv_q6k_ord<NC>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); \
+        } while (0)
+            switch (nc) {
+                case 1: MI_MMV_Q6ORD_LAUNCH(1); break;
+                case 2: MI_MMV_Q6ORD_LAUNCH(2); break;
+                case 3: case 4: MI_MMV_Q6ORD_LAUNCH(4); break;
+                default: MI_MMV_Q6ORD_LAUNCH(8); break;
+            }
+#undef MI_MMV_Q6ORD_LAUNCH
+            return;
+        }
+        switch (nc) {
+            case 1: MI_MMV_LAUNCH(k_mmv_q6k, 1); break;
+            case 2: MI_MMV_LAUNCH(k_mmv_q6k, 2); break;
+            case 3: MI_MMV_LAUNCH(k_mmv_q6k, 3); break;
+            case 4: MI_MMV_LAUNCH(k_mmv_q6k, 4); break;
+            default: MI_MMV_LAUNCH(k_mmv_q6k, 8); break;
+        }
         return;
     }
     switch (m.type) {

@@ -1,6 +1,6 @@
 // mmv_fused_impl.h -- the streaming decode GEMV k_mmv_stream (see mmv_fused.hip for the design),
 // its weight-format policies and launchers. Included by one translation unit per weight format
-// (mmv_fused_q4k.hip, _q5k, _q40, _q80) so that the kernel instances compile in parallel; each
+// (mmv_fused_q4k.hip, _q5k, _q6k, _q40, _q80) so that the kernel instances compile in parallel; each
 // exports one mi_mmv_launch_* entry point that mmv_fused.hip's dispatcher calls.
 #pragma once
 
@@ -683,6 +683,174 @@ struct FmtQ8R {
     using Act = Q::Act;
     __device__ static __forceinline__ void act_load(Act & v, int item, const lds_act & a, int64_t K) { Q::act_load(v, item, a, K); }
     __device__ static __forceinline__ float dot_act(const Regs & r, int, const Act & v, float acc) { return bdot(r, v.av, v.da, acc); }
+};
+
+// Q6_K (210 B superblocks: ql[128] | qh[64] | int8 scales[16] | fp16 d; element e is
+// d * scales[e / 16] * (q - 32)). An item is (superblock s, 128-half h, 16-byte range u), item =
+// 4 s + 2 h + u: ql[64h + 16u ..], ql[64h + 32 + 16u ..] and qh[32h + 16u ..] hold the four
+// 16-element sub-blocks at elements 128h + 32t + 16u (t = 0..3; t & 1 picks the ql range, t & 2 its
+// high nibbles, qh bits 2t..2t+1 the upper two bits), whose scales are scales[8h + 2t + u]. Four
+// items per superblock on adjacent lanes, so a K = 4096 row is one item per lane, as Q4_K.
+// Blocks are 2-byte aligned and so are rows of an odd superblock count (LLaMA's ffn_down,
+// K = 11008: 9030-byte rows), so the misalignment of a block is taken from its address: every load
+// is an aligned dword from two bytes below or at the data, re-aligned with v_alignbyte (shift 0 or
+// 2). The dword after a 16-byte range still lies in the block; the one holding d may reach two
+// bytes past it (the next block, or the buffer's tail slack).
+struct FmtQ6K {
+    static constexpr bool KL = false;
+    static constexpr int QKA = 256;
+    static constexpr int ITEM = 64;
+    static constexpr int BS = 210;
+    struct Regs {
+        uint32_t la[5], lb[5], hh[5];  // the dwords covering the two ql ranges and the qh range
+        uint32_t sc[3];                // ... the eight scales of the 128-half
+        uint32_t dd;                   // ... d
+        uint32_t off;                  // the block's misalignment: 0 or 2
+    };
+    __device__ static __forceinline__ void load(Regs & r, const uint8_t * row, int item) {
+        const uint32_t s = (uint32_t) item >> 2, h = ((uint32_t) item >> 1) & 1, u = (uint32_t) item & 1;
+        const uint32_t blk = s * BS;
+        r.off = ((uint32_t) (uintptr_t) row + blk) & 2;
+        const uint8_t * p = row + (int) (blk - r.off);  // 4-byte aligned (item 0 of a misaligned row: its first dword starts in the row before)
+        const uint32_t qa = 64 * h + 16 * u, qh = 128 + 32 * h + 16 * u, sc = 192 + 8 * h;
+#pragma unroll
+        for (int i = 0; i < 5; i++) {
+            r.la[i] = *(const uint32_t *) (p + qa + 4 * i);
+            r.lb[i] = *(const uint32_t *) (p + qa + 32 + 4 * i);
+            r.hh[i] = *(const uint32_t *) (p + qh + 4 * i);
+        }
+        r.sc[0] = *(const uint32_t *) (p + sc);
+        r.sc[1] = *(const uint32_t *) (p + sc + 4);
+        r.sc[2] = *(const uint32_t *) (p + sc + (r.off ? 8 : 4));  // (aligned blocks: not needed, no read past d)
+        r.dd = *(const uint32_t *) (p + 208);
+    }
+    // the item's operands: (q - 32) of sub-block t as four int8x4 dwords, its scale, the block's d
+    struct Dec {
+        int q[4][4];
+        int sc[4];
+        float dw;
+    };
+    // bytes of q (each 0..63) -> bytes of q - 32 as int8, no carries between the bytes
+    __device__ static __forceinline__ int center(uint32_t q) { return (int) (((q | 0x80808080u) - 0x20202020u) ^ 0x80808080u); }
+    __device__ static __forceinline__ void decode(Dec & d, const Regs & r, int item) {
+        const int u = item & 1;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t la = __builtin_amdgcn_alignbyte(r.la[i + 1], r.la[i], r.off);
+            const uint32_t lb = __builtin_amdgcn_alignbyte(r.lb[i + 1], r.lb[i], r.off);
+            const uint32_t hh = __builtin_amdgcn_alignbyte(r.hh[i + 1], r.hh[i], r.off);
+            d.q[0][i] = center((la & 0x0F0F0F0Fu) | ((hh & 0x03030303u) << 4));
+            d.q[1][i] = center((lb & 0x0F0F0F0Fu) | (((hh >> 2) & 0x03030303u) << 4));
+            d.q[2][i] = center(((la >> 4) & 0x0F0F0F0Fu) | (((hh >> 4) & 0x03030303u) << 4));
+            d.q[3][i] = center(((lb >> 4) & 0x0F0F0F0Fu) | (((hh >> 6) & 0x03030303u) << 4));
+        }
+        const uint32_t s0 = __builtin_amdgcn_alignbyte(r.sc[1], r.sc[0], r.off) >> (8 * u);
+        const uint32_t s1 = __builtin_amdgcn_alignbyte(r.sc[2], r.sc[1], r.off) >> (8 * u);
+        d.sc[0] = (int) (int8_t) (s0 & 0xFF);
+        d.sc[1] = (int) (int8_t) ((s0 >> 16) & 0xFF);
+        d.sc[2] = (int) (int8_t) (s1 & 0xFF);
+        d.sc[3] = (int) (int8_t) ((s1 >> 16) & 0xFF);
+        d.dw = mi_h2f((uint16_t) ((r.dd >> (8 * r.off)) & 0xFFFF));
+    }
+    // the item's 64 quantized activations of one column: sub-block t = av[4t .. 4t+3]
+    __device__ static __forceinline__ void act16(int (&av)[16], const int8_t * qs, int item) {
+        const int s = item >> 2, h = (item >> 1) & 1, u = item & 1;
+        const int4 * p = (const int4 *) (qs + (int64_t) s * 256 + 128 * h + 16 * u);
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int4 a = p[2 * t];
+            av[4 * t] = a.x; av[4 * t + 1] = a.y; av[4 * t + 2] = a.z; av[4 * t + 3] = a.w;
+        }
+    }
+    // An item's integer sum can reach 4 * 128 * 16 * 32 * 128 = 2^25, which f32 does not hold
+    // exactly (FmtKQ's f32 scale products do not carry over): int32, converted once.
+    __device__ static __forceinline__ float item_dot(const Dec & d, const int (&av)[16], float ad, float acc) {
+        int sumi = 0;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            int p = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) p = mi_dot4(d.q[t][i], av[4 * t + i], p);
+            sumi += __mul24(d.sc[t], p);  // |p| <= 16 * 32 * 128
+        }
+        return fmaf((float) sumi, d.dw * ad, acc);
+    }
+    template <int NC>
+    __device__ static __forceinline__ void dot(const Regs & r, int item, const lds_act & a, int64_t K, int ncols, float (&acc)[NC]) {
+        Dec d;
+        decode(d, r, item);
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            if (NC > 1 && c >= ncols) break;
+            int av[16];
+            act16(av, a.qs + c * K, item);
+            acc[c] = item_dot(d, av, a.d[c * (K / 256) + (item >> 2)], acc[c]);
+        }
+    }
+    struct Act {
+        int av[16];
+        float ad;
+    };
+    __device__ static __forceinline__ void act_load(Act & v, int item, const lds_act & a, int64_t) {
+        act16(v.av, a.qs, item);
+        v.ad = a.d[item >> 2];
+    }
+    __device__ static __forceinline__ float dot_act(const Regs & r, int item, const Act & v, float acc) {
+        Dec d;
+        decode(d, r, item);
+        return item_dot(d, v.av, v.ad, acc);
+    }
+
+    // CPU order (ggml_vec_dot_q6_K_q8_K, AVX2): eight int32 lanes per superblock, lane l = sum over
+    // the eight 32-groups g of scales[2g + (l >= 4)] * sum_{e = 4l..4l+3} (q - 32)[32g + e] a[32g + e].
+    // Item (h, u) holds groups g = 4h + t at bytes 16u..16u+15, i.e. CPU lanes 4u + i (its dword i)
+    // with exactly its four scales; the two h items of the quad add up to the lane totals (< 2^24 in
+    // magnitude, or exactly 2^24: the float conversion is exact). Entry of superblock sb in the
+    // scratch: [0..7] the eight sums as floats, [12] d = y.d * x.d (FmtKQ's slots).
+    template <int NC>
+    __device__ static __forceinline__ void dot_ord(const Regs & r, int item, int slot, const lds_act & a, int64_t K, int ncols,
+                                                   uint32_t * scr, int cs, int) {
+        const int h = (item >> 1) & 1, u = item & 1;
+        Dec d;
+        decode(d, r, item);
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            if (NC > 1 && c >= ncols) break;
+            int av[16];
+            act16(av, a.qs + c * K, item);
+            int v[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                v[i] = 0;
+#pragma unroll
+                for (int t = 0; t < 4; t++) v[i] += __mul24(d.sc[t], mi_dot4(d.q[t][i], av[4 * t + i], 0));
+                v[i] += mi_dpp<MI_DPP_QP_2301>(0, v[i]);  // the other 128-half: lane ^ 2 of the quad
+            }
+            uint32_t * e = scr + c * cs + (slot >> 2) * 16;
+            if (h == 0) {
+                *(uint4 *) (e + 4 * u) = make_uint4(__float_as_uint((float) v[0]), __float_as_uint((float) v[1]),
+                                                   __float_as_uint((float) v[2]), __float_as_uint((float) v[3]));
+            } else if (u == 0) {
+                e[12] = __float_as_uint(a.d[c * (K / 256) + (item >> 2)] * d.dw);
+            }
+        }
+    }
+    // acc[l] = fma(d, (float) sumi[l], acc[l]) per superblock (_mm256_fmadd_ps)
+    __device__ static __forceinline__ void chain(const uint32_t * scr, int l, int n_items, int, float & A, float &) {
+        const float * e = (const float *) scr;
+        const int nsb = n_items >> 2;
+        for (int sb = 0; sb < nsb; sb++, e += 16) A = fmaf(e[12], e[l], A);
+    }
+    static int ord_words(int nitems, int & stride) {
+        stride = 0;
+        return 16 * (nitems / 4) + 8;
+    }
+    __device__ static __forceinline__ float finish(float A, float) {
+        // hsum_float_8: ((a0 + a4) + (a2 + a6)) + ((a1 + a5) + (a3 + a7))
+        float z = A + __shfl_xor(A, 4, 8);
+        z = z + __shfl_xor(z, 2, 8);
+        return z + __shfl_xor(z, 1, 8);
+    }
 };
 
 // a format's weight load (FmtQ0R's needs the row length)

@@ -2,7 +2,7 @@
 //
 // All are memory- or launch-bound. Each follows the reference CPU forward's rounding sequence so
 // that results are bit-identical where the CPU order is reproducible:
-//   get_rows   src/ggml.c:12920 (f16) / :13006 (f32) / :12874 (Q4_0, Q8_0, Q4_K, Q5_K) -- exact
+//   get_rows   src/ggml.c:12920 (f16) / :13006 (f32) / :12874 (Q4_0, Q8_0, Q4_K, Q5_K, Q6_K) -- exact
 //   add / mul  src/ggml.c:8568 / :9687 (broadcast src1)      -- exact
 //   scale      src/ggml.c:12637                              -- exact
 //   norm       src/ggml.c:11353-11406 (double sums)          -- sums in double, then the same f32 ops
@@ -156,6 +156,16 @@ __device__ __forceinline__ float dequant_elem(const uint8_t * row, int64_t c) {
         } else {
             return (float) (int8_t) blk[2 + j] * d;
         }
+    } else if constexpr (TYPE == 14) {  // Q6_K (210 B) superblocks: ql[128] qh[64] int8 scales[16] fp16 d
+        // dequantize_row_q6_K (:2713-2758): d * sc * q, two separately rounded multiplies
+        const uint8_t * blk = row + (c >> 8) * 210;
+        const int e = (int) (c & 255), h = e >> 7, t = (e >> 5) & 3, p = e & 31;
+        uint16_t dh;
+        __builtin_memcpy(&dh, blk + 208, 2);
+        const uint8_t lq = blk[64 * h + 32 * (t & 1) + p];
+        const int q = (int) (((t & 2) ? (lq >> 4) : (lq & 0x0F)) | (((blk[128 + 32 * h + p] >> (2 * t)) & 3) << 4)) - 32;
+        const int sc = (int8_t) blk[192 + (e >> 4)];
+        return mul_rn(mul_rn(mi_h2f(dh), (float) sc), (float) q);
     } else {  // Q4_K (144 B) / Q5_K (176 B) superblocks of 256
         constexpr bool Q5 = TYPE == 13;
         const uint8_t * blk = row + (c >> 8) * (Q5 ? 176 : 144);
@@ -468,6 +478,7 @@ void mi_op_get_rows(const mi_tensor_desc & d, const mi_tensor_desc & a, const mi
         case 8: hipLaunchKernelGGL(k_get_rows_q<8>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
         case 12: hipLaunchKernelGGL(k_get_rows_q<12>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
         case 13: hipLaunchKernelGGL(k_get_rows_q<13>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
+        case 14: hipLaunchKernelGGL(k_get_rows_q<14>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
         default: hipLaunchKernelGGL(k_get_rows, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
     }
 }
@@ -493,6 +504,7 @@ static void launch_get_rows_add(const mi_tensor_desc & d, const mi_tensor_desc &
             case 8: hipLaunchKernelGGL((k_get_rows_add<TA, 8>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0, st); break;
             case 12: hipLaunchKernelGGL((k_get_rows_add<TA, 12>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0, st); break;
             case 13: hipLaunchKernelGGL((k_get_rows_add<TA, 13>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0, st); break;
+            case 14: hipLaunchKernelGGL((k_get_rows_add<TA, 14>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0, st); break;
             case 1: hipLaunchKernelGGL((k_get_rows_add<TA, 1>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0, st); break;
             default: hipLaunchKernelGGL((k_get_rows_add<TA, 0>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0, st); break;
         }
@@ -507,6 +519,7 @@ void mi_op_get_rows_add(const mi_tensor_desc & d, const mi_tensor_desc & a, cons
         case 8: launch_get_rows_add<8>(d, a, ia, b, ib, n, s); break;
         case 12: launch_get_rows_add<12>(d, a, ia, b, ib, n, s); break;
         case 13: launch_get_rows_add<13>(d, a, ia, b, ib, n, s); break;
+        case 14: launch_get_rows_add<14>(d, a, ia, b, ib, n, s); break;
         case 1: launch_get_rows_add<1>(d, a, ia, b, ib, n, s); break;
         default: launch_get_rows_add<0>(d, a, ia, b, ib, n, s); break;
     }

@@ -27,8 +27,9 @@ GPT2_LIB = os.path.join(LIB_DIR, "libgpt2_mi355x.so")
 # enum ggml_type (include/ggml/ggml.h:348-381)
 GGML_TYPE_F32, GGML_TYPE_F16, GGML_TYPE_Q4_0, GGML_TYPE_Q8_0 = 0, 1, 2, 8
 GGML_TYPE_Q4_K, GGML_TYPE_Q5_K, GGML_TYPE_Q8_K, GGML_TYPE_I32 = 12, 13, 15, 26
-TYPE_BY_NAME = {"f32": 0, "f16": 1, "q4_0": 2, "q8_0": 8, "q4_K": 12, "q5_K": 13, "i32": 26}
-BLOCK = {0: (1, 4), 1: (1, 2), 2: (32, 18), 8: (32, 34), 12: (256, 144), 13: (256, 176), 26: (1, 4)}
+GGML_TYPE_Q6_K = 14
+TYPE_BY_NAME = {"f32": 0, "f16": 1, "q4_0": 2, "q8_0": 8, "q4_K": 12, "q5_K": 13, "q6_K": 14, "i32": 26}
+BLOCK = {0: (1, 4), 1: (1, 2), 2: (32, 18), 8: (32, 34), 12: (256, 144), 13: (256, 176), 14: (256, 210), 26: (1, 4)}
 
 GGML_OP_MUL_MAT = 23
 GGML_STATUS_SUCCESS = 0
