@@ -512,8 +512,10 @@ static void scratch_reserve(mi_backend_ctx * ctx, size_t bytes) {
 // conformance harness does)
 // ---------------------------------------------------------------------------------------------
 
+static bool is_legacy_q1(ggml_type t) { return t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1; }
+
 static bool mm_src0_supported(ggml_type t) {
-    return t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K ||
+    return is_legacy_q1(t) || t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K ||
            t == GGML_TYPE_F16 || t == GGML_TYPE_F32;
 }
 
@@ -524,7 +526,8 @@ static bool is_f16_or_f32(const ggml_tensor * t) { return t && (t->type == GGML_
 static ggml_type q8_src1_type(ggml_type t) {
     switch (t) {
         case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: return GGML_TYPE_Q8_K;
-        case GGML_TYPE_Q4_0: case GGML_TYPE_Q8_0: return GGML_TYPE_Q8_0;
+        case GGML_TYPE_Q4_0: case GGML_TYPE_Q8_0: case GGML_TYPE_Q5_0: return GGML_TYPE_Q8_0;
+        case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_1: return GGML_TYPE_Q8_1;
         default: return GGML_TYPE_COUNT;
     }
 }
@@ -543,7 +546,7 @@ static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
             if (!mm_src0_supported(a->type)) return false;
             if (a->nb[0] != ggml_type_size(a->type) || b->nb[0] != ggml_type_size(b->type)) return false;
             // src1 F32, or src1 already of the weight's vec_dot_type, which the reference CPU reads as
-            // it lies (ggml.c:11952; F16 x F16, Q4_K/Q5_K/Q6_K x Q8_K, Q4_0/Q8_0 x Q8_0): the quantized
+            // it lies (ggml.c:11952; F16 x F16, Q4_K/Q5_K/Q6_K x Q8_K, Q4_0/Q5_0/Q8_0 x Q8_0, Q4_1/Q5_1 x Q8_1): the quantized
             // ones with whole superblocks, on the device's own weights
             // (the split-buffer path converts an F32 src1 on the main device: F16 src1 only unsplit)
             if (b->type == GGML_TYPE_F32 || (b->type == GGML_TYPE_F16 && a->type == GGML_TYPE_F16 && !is_split_tensor(a))) return true;
@@ -577,14 +580,14 @@ static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
                     return false;
             }
         case GGML_OP_GET_ROWS:
-            return (is_f16_or_f32(a) || a->type == GGML_TYPE_Q4_0 || a->type == GGML_TYPE_Q8_0 || a->type == GGML_TYPE_Q4_K ||
+            return (is_f16_or_f32(a) || is_legacy_q1(a->type) || a->type == GGML_TYPE_Q4_0 || a->type == GGML_TYPE_Q8_0 || a->type == GGML_TYPE_Q4_K ||
                     a->type == GGML_TYPE_Q5_K || a->type == GGML_TYPE_Q6_K) &&
                    b->type == GGML_TYPE_I32 && is_f32(op);
         case GGML_OP_CPY:
         case GGML_OP_DUP:
         case GGML_OP_CONT:
-            // F32 -> Q8_K / Q8_0 (from_float = quantize_row_q8_K / _q8_0): whole rows of blocks
-            if (is_f32(a) && (op->type == GGML_TYPE_Q8_K || op->type == GGML_TYPE_Q8_0))
+            // F32 -> Q8_K / Q8_0 / Q8_1 (from_float = quantize_row_q8_K / _q8_0 / _q8_1): whole rows of blocks
+            if (is_f32(a) && (op->type == GGML_TYPE_Q8_K || op->type == GGML_TYPE_Q8_0 || op->type == GGML_TYPE_Q8_1))
                 return ggml_are_same_shape(a, op) && a->nb[0] == sizeof(float) && op->nb[0] == ggml_type_size(op->type) &&
                        op->ne[0] % (op->type == GGML_TYPE_Q8_K ? 256 : 32) == 0;
             return is_f16_or_f32(a) && is_f16_or_f32(op);
@@ -611,17 +614,19 @@ static bool mi_offload_op(ggml_backend_t, const ggml_tensor * op) {
 
 static int act_kind(ggml_type wtype) {
     switch (wtype) {
-        case GGML_TYPE_Q4_0: case GGML_TYPE_Q8_0: return 0;
+        case GGML_TYPE_Q4_0: case GGML_TYPE_Q8_0: case GGML_TYPE_Q5_0: return 0;
         case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: return 1;
         case GGML_TYPE_F16: return 2;
+        case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_1: return 10;
         default: return -1;
     }
 }
 
 // kinds: 0 q8_0, 1 q8_K, 2 f16, 3/4 q8_0/q8_K quants expanded to f16(d * q) (mmq.hip operand),
 // 5/6/7 = 2/3/4 in the GEMM's K-blocked layout [K/16][ncols][16], 8 q8_K / 9 q8_0 in the int8-MFMA
-// layouts of the exact prefill GEMMs (mmq_exact.hip)
+// layouts of the exact prefill GEMMs (mmq_exact.hip), 10 q8_1 (q8_0 plus the blocks' s; the GEMVs only)
 static size_t act_bytes(int kind, int64_t K, int64_t ncols) {
+    if (kind == 10) return mi_act_q8_bytes(K, ncols, false, true);
     if (kind == 8) return mi_act_mmx_bytes(K, ncols);
     if (kind == 9) return mi_act_mmx0_bytes(K, ncols);
     if (kind >= 2) return (size_t) K * ncols * 2;
@@ -668,7 +673,13 @@ static void * get_activations(mi_backend_ctx * ctx, const ggml_tensor * src1, in
     const int64_t ncols = src1->ne[1] * src1->ne[2] * src1->ne[3];
     void * dev = scratch_take(ctx, act_bytes(kind, K, ncols));
     const mi_src_cols x = src_cols(src1);
-    if (src1->type == GGML_TYPE_Q8_K || src1->type == GGML_TYPE_Q8_0) {
+    if (src1->type == GGML_TYPE_Q8_1) {
+        MI_ASSERT(kind == 10);
+        const mi_act_q8 act = mi_act_q8_carve(dev, K, ncols, false, true);
+        mi_q8_rows_to_act(x, K, false, &act, nullptr, ctx->stream, true);
+    } else if (kind == 10) {
+        mi_quantize_q8_1(x, K, mi_act_q8_carve(dev, K, ncols, false, true), ctx->stream);
+    } else if (src1->type == GGML_TYPE_Q8_K || src1->type == GGML_TYPE_Q8_0) {
         // already quantized by the reference's rules (e.g. a CPY F32 -> Q8_K): re-laid out only
         MI_ASSERT(kind == 0 || kind == 1 || kind == 8 || kind == 9);
         const bool q8K = src1->type == GGML_TYPE_Q8_K;
@@ -728,10 +739,12 @@ static bool mm_batched(const mi_mm_desc & m, const ggml_tensor * src1) {
 // q8_K layouts (8); Q4_0 / Q8_0 prompts: its q8_0 layouts (9); F16 prompts: f16 operands (2, or
 // K-blocked 5); decode: q8 SoA (0 / 1) or f16 (2). Q6_K has neither an exact MFMA GEMM nor a
 // dequantizer in the f16 GEMM (mi_mmq_supported / mi_mmqx_supported refuse it): q8_K SoA (1) at
-// any column count, the GEMV runs the prompt in 8-column chunks.
+// any column count, the GEMV runs the prompt in 8-column chunks. Q4_1 / Q5_0 / Q5_1 likewise: q8_1
+// SoA (10) resp. q8_0 SoA (0) at any column count.
 static int mm_act_kind(const mi_mm_desc & m, const ggml_tensor * src1) {
     const int kind = act_kind((ggml_type) m.type);
     if (kind < 0) return -1;
+    if (kind == 10) return kind;
     const int64_t ncols = src1->ne[1] * src1->ne[2] * src1->ne[3];
     if (src1->type != GGML_TYPE_F32 && src1->type != GGML_TYPE_F16) {
         // pre-quantized src1 (Q8_K / Q8_0 rows): the exact GEMMs' layouts, else the GEMV's
@@ -833,7 +846,10 @@ static void mul_mat_run(mi_backend_ctx * ctx, const ggml_tensor * src0, const vo
     } else {
         const int64_t ncols = src1->ne[1] * src1->ne[2] * src1->ne[3];
         void * xa = get_activations(ctx, src1, xkind, m.K);
-        if (xkind == 8 || xkind == 9) {
+        if (xkind == 10) {
+            // Q4_1 / Q5_1 x q8_1: the GEMVs at any column count
+            mi_mul_mat_q(m, mi_act_q8_carve(xa, m.K, ncols, false, true), ctx->stream);
+        } else if (xkind == 8 || xkind == 9) {
             // Q4_K / Q5_K / Q4_0 / Q8_0: the exact-integer int8 MFMA GEMMs (mmq_exact.hip)
             const mi_act_mmx act = xkind == 8 ? mi_act_mmx_carve(xa, m.K, ncols) : mi_act_mmx0_carve(xa, m.K, ncols);
             mi_mul_mat_mmqx(m.type, m.W, m.nb01, m.K, m.N, act, m.dst, m.nb1, ctx->stream, W == src0->data && N == src0->ne[1] ? planes_of(ctx, src0, src1) : nullptr);
@@ -1217,8 +1233,8 @@ static void op_companion(mi_backend_ctx * ctx, ggml_tensor * node) {
         case GGML_OP_DUP:
         case GGML_OP_CONT:
             MI_ASSERT(ggml_nelements(node) == ggml_nelements(a));
-            if (node->type == GGML_TYPE_Q8_K || node->type == GGML_TYPE_Q8_0) {
-                mi_quantize_rows_q8(src_cols(a), a->ne[0], node->type == GGML_TYPE_Q8_K, src_cols(node), st);
+            if (node->type == GGML_TYPE_Q8_K || node->type == GGML_TYPE_Q8_0 || node->type == GGML_TYPE_Q8_1) {
+                mi_quantize_rows_q8(src_cols(a), a->ne[0], node->type == GGML_TYPE_Q8_K, src_cols(node), st, node->type == GGML_TYPE_Q8_1);
                 break;
             }
             mi_op_cpy(desc(node), desc(a), st);
@@ -1269,7 +1285,7 @@ static size_t graph_scratch_bytes(const ggml_cgraph * cgraph) {
         const int64_t ncols = b->ne[1] * b->ne[2] * b->ne[3];
         // q8 blocks and/or their f16 expansion (batched) -- both counted, the choice is made at run time
         total += (act_bytes(kind, b->ne[0], ncols) + kBufferAlign - 1) & ~(kBufferAlign - 1);
-        if (ncols > 8) {
+        if (ncols > 8 && kind != 10) {
             const size_t big = std::max(act_bytes(kind + 3, b->ne[0], ncols),
                                         kind == 1 ? act_bytes(8, b->ne[0], ncols) : kind == 0 ? act_bytes(9, b->ne[0], ncols) : 0);
             total += (big + kBufferAlign - 1) & ~(kBufferAlign - 1);
@@ -1963,7 +1979,7 @@ static bool ord_prefill_chunked(const ggml_tensor * n) {
     const ggml_tensor * b = n->src[1];
     if (b->type != GGML_TYPE_F32 || b->ne[1] <= 8 || b->ne[1] > (mi_mmv_order() == 1 ? g_ord_prefill_cols : g_tree_prefill_cols)) return false;
     if (a->type != GGML_TYPE_Q4_K && a->type != GGML_TYPE_Q5_K && a->type != GGML_TYPE_Q6_K && a->type != GGML_TYPE_Q4_0 &&
-        a->type != GGML_TYPE_Q8_0)
+        a->type != GGML_TYPE_Q8_0 && !is_legacy_q1(a->type))
         return false;
     if (!mi_mmv_fused_supported(a->type, a->ne[0], 8)) return false;
     if (a->ne[2] != 1 || a->ne[3] != 1 || b->ne[2] != 1 || b->ne[3] != 1) return false;
@@ -3124,7 +3140,8 @@ bool ggml_backend_mi355x_quantize_activations(ggml_backend_t backend, int vec_do
                                               int64_t ncols, int8_t * qs, float * d, int16_t * s32) {
     MI_ASSERT(ggml_backend_is_mi355x(backend));
     const bool is_k = vec_dot_type == GGML_TYPE_Q8_K;
-    if (!is_k && vec_dot_type != GGML_TYPE_Q8_0) return false;
+    const bool is_1 = vec_dot_type == GGML_TYPE_Q8_1;  // s32: the fp16 bits of the blocks' s
+    if (!is_k && !is_1 && vec_dot_type != GGML_TYPE_Q8_0) return false;
     if (K % (is_k ? 256 : 32) != 0) return false;
     auto * ctx = (mi_backend_ctx *) backend->context;
     mi_device_guard g(ctx->device);
@@ -3132,7 +3149,7 @@ bool ggml_backend_mi355x_quantize_activations(ggml_backend_t backend, int vec_do
     void * dx = nullptr;
     void * dq = nullptr;
     MI_CHECK(hipMalloc(&dx, xbytes));
-    MI_CHECK(hipMalloc(&dq, mi_act_q8_bytes(K, ncols, is_k)));
+    MI_CHECK(hipMalloc(&dq, mi_act_q8_bytes(K, ncols, is_k, is_1)));
     MI_CHECK(hipMemcpy(dx, x, xbytes, hipMemcpyHostToDevice));
     mi_src_cols src;
     src.base = (const char *) dx;
@@ -3140,13 +3157,14 @@ bool ggml_backend_mi355x_quantize_activations(ggml_backend_t backend, int vec_do
     src.ne2 = src.ne3 = 1;
     src.nb1 = (size_t) K * sizeof(float);
     src.nb2 = src.nb3 = src.nb1 * ncols;
-    const mi_act_q8 act = mi_act_q8_carve(dq, K, ncols, is_k);
+    const mi_act_q8 act = mi_act_q8_carve(dq, K, ncols, is_k, is_1);
     if (is_k) mi_quantize_q8_K(src, K, act, ctx->stream);
+    else if (is_1) mi_quantize_q8_1(src, K, act, ctx->stream);
     else mi_quantize_q8_0(src, K, act, ctx->stream);
     MI_CHECK(hipStreamSynchronize(ctx->stream));
     MI_CHECK(hipMemcpy(qs, act.qs, (size_t) K * ncols, hipMemcpyDeviceToHost));
     MI_CHECK(hipMemcpy(d, act.d, (size_t) (K / (is_k ? 256 : 32)) * ncols * sizeof(float), hipMemcpyDeviceToHost));
-    if (is_k && s32) MI_CHECK(hipMemcpy(s32, act.s32, (size_t) (K / 32) * ncols * sizeof(int16_t), hipMemcpyDeviceToHost));
+    if ((is_k || is_1) && s32) MI_CHECK(hipMemcpy(s32, act.s32, (size_t) (K / 32) * ncols * sizeof(int16_t), hipMemcpyDeviceToHost));
     MI_CHECK(hipFree(dx));
     MI_CHECK(hipFree(dq));
     return true;

@@ -1,5 +1,5 @@
 // ggml_quants_host.cpp -- ggml_quantize_chunk (include/ggml/ggml.h:2240-2254) for the weight
-// formats on the hot path: Q4_0, Q8_0, Q4_K, Q5_K, Q6_K (+ F16 / F32 passthrough).
+// formats on the hot path: Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q4_K, Q5_K, Q6_K (+ F16 / F32 passthrough).
 //
 // These produce the bytes the MI355X kernels consume. They must be bit-identical to the
 // reference's imatrix == NULL path (src/ggml.c:21594-21660 -> src/ggml-quants.c reference
@@ -25,6 +25,10 @@ struct blk_q5_K { ggml_fp16_t d, dmin; uint8_t scales[12]; uint8_t qh[32]; uint8
 struct blk_q6_K { uint8_t ql[128]; uint8_t qh[64]; int8_t scales[16]; ggml_fp16_t d; };
 static_assert(sizeof(blk_q4_0) == 18 && sizeof(blk_q8_0) == 34 && sizeof(blk_q4_K) == 144 && sizeof(blk_q5_K) == 176, "blocks");
 static_assert(sizeof(blk_q6_K) == 210, "blocks");
+struct blk_q4_1 { ggml_fp16_t d, m; uint8_t qs[16]; };
+struct blk_q5_0 { ggml_fp16_t d; uint8_t qh[4]; uint8_t qs[16]; };
+struct blk_q5_1 { ggml_fp16_t d, m; uint8_t qh[4]; uint8_t qs[16]; };
+static_assert(sizeof(blk_q4_1) == 20 && sizeof(blk_q5_0) == 22 && sizeof(blk_q5_1) == 24, "blocks");
 
 // src/ggml-quants.c:1097-1102: round half to even through the 1.5*2^23 bias
 inline int rne_int(float v) {
@@ -56,6 +60,85 @@ void quantize_q4_0_rows(const float * x, blk_q4_0 * y, int64_t n) {
             const int q1 = std::min(15, (int) (int8_t) (v1 + 8.5f));
             y[b].qs[j] = (uint8_t) (q0 | (q1 << 4));
         }
+    }
+}
+
+// The 32-element min/max and signed-max formats below round a level as (int8_t) (v * id + c). The
+// reference's x86 build (gcc -O3 -mfma) contracts that product into the add of the constant, one
+// fma, in the scalar and in the vectorised form of the loop alike; it is written out here so that
+// the bytes do not depend on this file's compiler (tests/test_legacy_quants.py pins it against
+// the reference library).
+inline int level_fma(float v, float id, float c) { return (int) (int8_t) fmaf(v, id, c); }
+
+// src/ggml-quants.c:302-337 quantize_row_q4_1_reference: d = (max - min) / 15, m = min,
+// q = min(15, (int8_t) ((x - min) * id + 0.5))
+void quantize_q4_1_rows(const float * x, blk_q4_1 * y, int64_t n) {
+    for (int64_t b = 0; b < n / 32; ++b, x += 32) {
+        float lo = 3.402823466e+38f, hi = -3.402823466e+38f;
+        for (int j = 0; j < 32; ++j) {
+            if (x[j] < lo) lo = x[j];
+            if (x[j] > hi) hi = x[j];
+        }
+        const float d = (hi - lo) / 15;
+        const float id = d ? 1.0f / d : 0.0f;
+        y[b].d = ggml_fp32_to_fp16(d);
+        y[b].m = ggml_fp32_to_fp16(lo);
+        for (int j = 0; j < 16; ++j) {
+            const int q0 = std::min(15, level_fma(x[j] - lo, id, 0.5f));
+            const int q1 = std::min(15, level_fma(x[16 + j] - lo, id, 0.5f));
+            y[b].qs[j] = (uint8_t) ((uint8_t) q0 | ((uint8_t) q1 << 4));
+        }
+    }
+}
+
+// src/ggml-quants.c:343-385 quantize_row_q5_0_reference: the first element of largest |x| keeps its
+// sign, d = max / -16, q = min(31, (int8_t) (x * id + 16.5)); bit j of qh = the fifth bit of element j
+void quantize_q5_0_rows(const float * x, blk_q5_0 * y, int64_t n) {
+    for (int64_t b = 0; b < n / 32; ++b, x += 32) {
+        float amax = 0.0f, extreme = 0.0f;
+        for (int j = 0; j < 32; ++j) {
+            if (amax < fabsf(x[j])) {
+                amax = fabsf(x[j]);
+                extreme = x[j];
+            }
+        }
+        const float d = extreme / -16;
+        const float id = d ? 1.0f / d : 0.0f;
+        y[b].d = ggml_fp32_to_fp16(d);
+        uint32_t qh = 0;
+        for (int j = 0; j < 16; ++j) {
+            const uint8_t q0 = (uint8_t) std::min(31, level_fma(x[j], id, 16.5f));
+            const uint8_t q1 = (uint8_t) std::min(31, level_fma(x[16 + j], id, 16.5f));
+            y[b].qs[j] = (uint8_t) ((q0 & 0x0F) | ((q1 & 0x0F) << 4));
+            qh |= ((q0 & 0x10u) >> 4) << j;
+            qh |= ((q1 & 0x10u) >> 4) << (j + 16);
+        }
+        memcpy(y[b].qh, &qh, 4);
+    }
+}
+
+// src/ggml-quants.c:391-433 quantize_row_q5_1_reference: d = (max - min) / 31, m = min,
+// q = (uint8_t) ((x - min) * id + 0.5) (no clamp: the fifth bit and the nibble are masked out of it)
+void quantize_q5_1_rows(const float * x, blk_q5_1 * y, int64_t n) {
+    for (int64_t b = 0; b < n / 32; ++b, x += 32) {
+        float lo = 3.402823466e+38f, hi = -3.402823466e+38f;
+        for (int j = 0; j < 32; ++j) {
+            if (x[j] < lo) lo = x[j];
+            if (x[j] > hi) hi = x[j];
+        }
+        const float d = (hi - lo) / 31;
+        const float id = d ? 1.0f / d : 0.0f;
+        y[b].d = ggml_fp32_to_fp16(d);
+        y[b].m = ggml_fp32_to_fp16(lo);
+        uint32_t qh = 0;
+        for (int j = 0; j < 16; ++j) {
+            const uint8_t q0 = (uint8_t) (int) fmaf(x[j] - lo, id, 0.5f);
+            const uint8_t q1 = (uint8_t) (int) fmaf(x[16 + j] - lo, id, 0.5f);
+            y[b].qs[j] = (uint8_t) ((q0 & 0x0F) | ((q1 & 0x0F) << 4));
+            qh |= ((q0 & 0x10u) >> 4) << j;
+            qh |= ((q1 & 0x10u) >> 4) << (j + 16);
+        }
+        memcpy(y[b].qh, &qh, 4);
     }
 }
 
@@ -373,6 +456,9 @@ size_t ggml_quantize_chunk(enum ggml_type type, const float * src, void * dst, i
     }
     switch (type) {
         case GGML_TYPE_Q4_0: quantize_q4_0_rows(in, (blk_q4_0 *) out, n); break;
+        case GGML_TYPE_Q4_1: quantize_q4_1_rows(in, (blk_q4_1 *) out, n); break;
+        case GGML_TYPE_Q5_0: quantize_q5_0_rows(in, (blk_q5_0 *) out, n); break;
+        case GGML_TYPE_Q5_1: quantize_q5_1_rows(in, (blk_q5_1 *) out, n); break;
         case GGML_TYPE_Q8_0: quantize_q8_0_rows(in, (blk_q8_0 *) out, n); break;
         case GGML_TYPE_Q4_K: quantize_q4_K_rows(in, (blk_q4_K *) out, n); break;
         case GGML_TYPE_Q5_K: quantize_q5_K_rows(in, (blk_q5_K *) out, n); break;

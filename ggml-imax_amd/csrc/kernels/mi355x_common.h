@@ -71,6 +71,15 @@ __device__ __forceinline__ uint16_t mi_f2h(float f) {
     return h;
 }
 
+// f16(a * b) with the product rounded to f32 first, then to f16, as the CPU's F16C code rounds it. The
+// empty asm keeps the compiler from folding the multiply into the conversion (a mixed-precision
+// v_fma_mixlo_f16 rounds the exact product once: a different f16 about once in 2^13 products).
+__device__ __forceinline__ uint16_t mi_mul_f2h(float a, float b) {
+    float p = a * b;
+    asm volatile("" : "+v"(p));
+    return mi_f2h(p);
+}
+
 __device__ __forceinline__ float mi_wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, MI_WAVE);

@@ -9,7 +9,8 @@
 // them (vec_dot_type from_float, src/ggml.c:11952-11974), stored structure-of-arrays in HBM:
 //   qs  [ncols][K]      int8 quants
 //   d   [ncols][K/QK]   f32 block scale (Q8_0: the fp16-rounded d; Q8_K: f32 d)
-//   s32 [ncols][K/32]   int16 sums of 32 quants (Q8_K only; = bsums[2j] + bsums[2j+1])
+//   s32 [ncols][K/32]   int16 sums of 32 quants (Q8_K; = bsums[2j] + bsums[2j+1]), or the fp16 bits of
+//                       the block's s = d * sum(qs) (Q8_1, the vec_dot_type of Q4_1 / Q5_1: Q8_0 + s)
 struct mi_act_q8 {
     int8_t * qs;
     float * d;
@@ -38,10 +39,11 @@ struct mi_mm_desc {
     size_t nb1, nb2, nb3;  // dst strides in bytes (nb0 == 4)
 };
 
-size_t mi_act_q8_bytes(int64_t K, int64_t ncols, bool is_q8K);
-mi_act_q8 mi_act_q8_carve(void * base, int64_t K, int64_t ncols, bool is_q8K);
+size_t mi_act_q8_bytes(int64_t K, int64_t ncols, bool is_q8K, bool is_q8_1 = false);
+mi_act_q8 mi_act_q8_carve(void * base, int64_t K, int64_t ncols, bool is_q8K, bool is_q8_1 = false);
 
 void mi_quantize_q8_0(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, hipStream_t s);
+void mi_quantize_q8_1(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, hipStream_t s);
 void mi_quantize_q8_K(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, hipStream_t s);
 // blocked: write the GEMM's K-blocked layout [K/16][ncols][16] instead of [ncols][K];
 // src_f16: the columns are f16 already (copied, not rounded)
@@ -208,11 +210,12 @@ void mi_quantize_q8_K_mmx_group(mi_mmx_qgroup & q, hipStream_t s);
 size_t mi_act_mmx0_bytes(int64_t K, int64_t ncols);
 mi_act_mmx mi_act_mmx0_carve(void * base, int64_t K, int64_t ncols);
 void mi_quantize_q8_0_mmx_group(mi_mmx_qgroup & q, hipStream_t s);
-// src1 of the weight's vec_dot type (quantize.hip): GGML_OP_CPY F32 -> Q8_K / Q8_0 rows in the
+// src1 of the weight's vec_dot type (quantize.hip): GGML_OP_CPY F32 -> Q8_K / Q8_0 / Q8_1 rows in the
 // reference block layouts (dst columns addressed like src1's), and such rows -> the GEMV's q8 SoA
-// (act) or the prefill GEMMs' MFMA layout (mx); exactly one of act / mx non-null
-void mi_quantize_rows_q8(const mi_src_cols & x, int64_t K, bool is_q8K, const mi_src_cols & dst, hipStream_t s);
-void mi_q8_rows_to_act(const mi_src_cols & xs, int64_t K, bool is_q8K, const mi_act_q8 * act, const mi_act_mmx * mx, hipStream_t s);
+// (act) or the prefill GEMMs' MFMA layout (mx); exactly one of act / mx non-null (Q8_1: act)
+void mi_quantize_rows_q8(const mi_src_cols & x, int64_t K, bool is_q8K, const mi_src_cols & dst, hipStream_t s, bool is_q8_1 = false);
+void mi_q8_rows_to_act(const mi_src_cols & xs, int64_t K, bool is_q8K, const mi_act_q8 * act, const mi_act_mmx * mx, hipStream_t s,
+                       bool is_q8_1 = false);
 bool mi_mmqx_supported(int type, int64_t K, size_t ycol, int64_t ncols, size_t nb01);
 // Independent Q4_K / Q5_K (q8_K activations) or Q4_0 / Q8_0 (q8_0 activations, mi_act_mmx0_*)
 // mul_mats (same type, K and activation column count) in one launch:

@@ -12,6 +12,9 @@
 // Reference per-type dot products mirrored here:
 //   Q4_0 x Q8_0  ggml_vec_dot_q4_0_q8_0  src/ggml-quants.c:3469-3874
 //   Q8_0 x Q8_0  ggml_vec_dot_q8_0_q8_0  src/ggml-quants.c:4819+
+//   Q4_1 x Q8_1  ggml_vec_dot_q4_1_q8_1  src/ggml-quants.c:4006-4039 (AVX2)
+//   Q5_0 x Q8_0  ggml_vec_dot_q5_0_q8_0  src/ggml-quants.c:4279-4301 (AVX2)
+//   Q5_1 x Q8_1  ggml_vec_dot_q5_1_q8_1  src/ggml-quants.c:4623-4648 (AVX2)
 //   Q4_K x Q8_K  ggml_vec_dot_q4_K_q8_K  src/ggml-quants.c:7007-7502
 //   Q5_K x Q8_K  ggml_vec_dot_q5_K_q8_K  src/ggml-quants.c:7833-8378
 //   Q6_K x Q8_K  ggml_vec_dot_q6_K_q8_K  src/ggml-quants.c:8730-9310
@@ -132,7 +135,27 @@ __global__ __launch_bounds__(256) void k_mmv_kq(const uint8_t * __restrict__ W, 
     mmv_store<NC>(g, dst, row, i11, i12, i13, acc, lane);
 }
 
-// ---------------------------------------------------------------- Q4_0 / Q8_0 x Q8_0
+// ---------------------------------------------------------------- 32-element blocks x Q8_0 / Q8_1
+//
+// T is the weight's ggml_type: Q4_0 (2, 18 B: fp16 d, qs[16]), Q8_0 (8, 34 B: fp16 d, int8 qs[32]),
+// Q4_1 (3, 20 B: fp16 d, m, qs[16]), Q5_0 (6, 22 B: fp16 d, qh[4], qs[16]), Q5_1 (7, 24 B: fp16 d, m,
+// qh[4], qs[16]). In the nibble formats element j < 16 is the low nibble of qs[j], element j >= 16
+// the high nibble of qs[j - 16]; bit j of the little-endian qh is the fifth bit of element j.
+// Values: Q4_0 (q - 8) d, Q5_0 (q - 16) d, Q4_1 / Q5_1 q d + m. Q4_1 / Q5_1 dot with Q8_1
+// activations, whose per-block s = fp16(d * sum(qs)) lies as fp16 bits in act.s32.
+template <int T> struct q32_fmt {
+    static constexpr bool Q8 = T == 8;
+    static constexpr bool HAS_M = T == 3 || T == 7;   // fp16 m after d, Q8_1 activations
+    static constexpr bool HAS_QH = T == 6 || T == 7;  // fifth bits
+    static constexpr int BS = T == 2 ? 18 : T == 8 ? 34 : T == 3 ? 20 : T == 6 ? 22 : 24;
+    static constexpr int QH = HAS_M ? 4 : 2;          // offset of qh
+    static constexpr int QS = (HAS_M ? 4 : 2) + (HAS_QH ? 4 : 0);  // offset of the quants
+    static constexpr int SUB = T == 2 ? 8 : T == 6 ? 16 : 0;  // subtracted from every level
+};
+
+// four fifth bits (bits 0..3 of x) to bit 4 of four bytes: bit b of x * 0x00204081 lands at b, b + 7,
+// b + 14, b + 21 -- sixteen distinct positions, no carries -- of which 0, 8, 16, 24 are kept
+__device__ __forceinline__ uint32_t q5_spread(uint32_t x) { return (((x & 0xFu) * 0x00204081u) & 0x01010101u) << 4; }
 
 // 32 quants of a block starting at a 2-byte aligned address, gathered from aligned dwords.
 template <int NBYTES>
@@ -148,14 +171,16 @@ __device__ __forceinline__ void load_qs_unaligned(const uint8_t * p, uint32_t (&
     for (int i = 0; i < NBYTES / 4; i++) out[i] = __builtin_amdgcn_alignbyte(raw[i + 1], raw[i], shift);
 }
 
-template <int NC, bool Q8>
+template <int NC, int T>
 __global__ __launch_bounds__(256) void k_mmv_q0(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
+    using F = q32_fmt<T>;
+    constexpr bool Q8 = F::Q8;
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t) blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
     if (row >= g.N) return;
     int64_t i11, i12, i13, i02, i03;
     mmv_coords(g, NC, i11, i12, i13, i02, i03);
-    constexpr int BS = Q8 ? 34 : 18;
+    constexpr int BS = F::BS;
     const uint8_t * wrow = W + i02 * g.nb02 + i03 * g.nb03 + row * g.nb01;
     const int nb = (int) (g.K / 32);
     const int64_t col0 = i11 + g.ne11 * (i12 + g.ne12 * i13);
@@ -175,13 +200,21 @@ __global__ __launch_bounds__(256) void k_mmv_q0(const uint8_t * __restrict__ W, 
             for (int i = 0; i < 8; i++) wq[i] = (int) t[i];
         } else {
             uint32_t t[4];
-            load_qs_unaligned<16>(blk + 2, t);
+            load_qs_unaligned<16>(blk + F::QS, t);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 wq[i] = (int) (t[i] & 0x0F0F0F0Fu);          // elements 4i..4i+3
                 wq[i + 4] = (int) ((t[i] >> 4) & 0x0F0F0F0Fu);  // elements 16+4i..
             }
+            if constexpr (F::HAS_QH) {
+                uint32_t qh[1];
+                load_qs_unaligned<4>(blk + F::QH, qh);
+#pragma unroll
+                for (int i = 0; i < 8; i++) wq[i] |= (int) q5_spread(qh[0] >> (4 * i));
+            }
         }
+        float mw = 0.0f;
+        if constexpr (F::HAS_M) mw = mi_h2f(*(const uint16_t *) (blk + 2));
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             if (NC > 1 && i11 + c >= g.ne11) break;
@@ -192,14 +225,15 @@ __global__ __launch_bounds__(256) void k_mmv_q0(const uint8_t * __restrict__ W, 
             int sumi = 0;
 #pragma unroll
             for (int i = 0; i < 8; i++) sumi = mi_dot4(wq[i], av[i], sumi);
-            if constexpr (!Q8) {
-                // (q - 8) * y summed = q*y - 8 * sum(y)
+            if constexpr (F::SUB != 0) {
+                // (q - 8) * y summed = q*y - 8 * sum(y) (Q5_0: 16)
                 int sy = 0;
 #pragma unroll
                 for (int i = 0; i < 8; i++) sy = mi_dot4(0x01010101, av[i], sy);
-                sumi -= 8 * sy;
+                sumi -= F::SUB * sy;
             }
             acc[c] += (float) sumi * (dw * act.d[col * nb + b]);
+            if constexpr (F::HAS_M) acc[c] += mw * mi_h2f((uint16_t) act.s32[col * nb + b]);  // m * s, the fp16-rounded s
         }
     }
     mmv_store<NC>(g, dst, row, i11, i12, i13, acc, lane);
@@ -214,24 +248,31 @@ __global__ __launch_bounds__(256) void k_mmv_q0(const uint8_t * __restrict__ W, 
 // l < 4, high nibbles of bytes 4(l-4).. for l >= 4) in acc[l] = fma(x.d * y.d, q, acc[l]) over the
 // blocks in order, then hsum_float_8. Here eight lanes are those eight CPU lanes of one row (8 rows
 // per wave): each runs its own chain, the hsum is three xor shuffles in the same pairing.
-template <int NC, bool Q8>
+// Q5_0 (ggml_vec_dot_q5_0_q8_0 :4279-4301) is the same with the fifth bits or-ed in and 16 taken
+// off. Q4_1 / Q5_1 (ggml_vec_dot_q4_1_q8_1 :4006-4039, _q5_1_q8_1 :4623-4648) keep the unsigned
+// levels in the lanes and one scalar chain summs += fp16(x.m) * fp16(y.s) over the blocks in order
+// (the product of two fp16 values is exact in f32, so a contracted fma gives the same bits); the
+// result is hsum_float_8(acc) + summs.
+template <int NC, int T>
 __global__ __launch_bounds__(256) void k_mmv_q0_ord(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
+    using F = q32_fmt<T>;
+    constexpr bool Q8 = F::Q8;
     const int l = threadIdx.x & 7;
     const int64_t row = (int64_t) blockIdx.x * 32 + (threadIdx.x >> 3);
     const bool live = row < g.N;
     const int64_t rc = live ? row : g.N - 1;  // (dead groups run a valid row: no early exit before the shuffles)
     int64_t i11, i12, i13, i02, i03;
     mmv_coords(g, NC, i11, i12, i13, i02, i03);
-    constexpr int BS = Q8 ? 34 : 18;
+    constexpr int BS = F::BS;
     const uint8_t * wrow = W + i02 * g.nb02 + i03 * g.nb03 + rc * g.nb01;
     const int nb = (int) (g.K / 32);
     const int64_t col0 = i11 + g.ne11 * (i12 + g.ne12 * i13);
-    // the lane's 4 quant bytes: block byte 2 + 4 l (Q4_0: 2 + 4 (l & 3), nibble half l >> 2)
-    const int qoff = 2 + 4 * (Q8 ? l : (l & 3));
+    // the lane's 4 quant bytes: block byte 2 + 4 l (nibble formats: QS + 4 (l & 3), nibble half l >> 2)
+    const int qoff = F::QS + 4 * (Q8 ? l : (l & 3));
 
-    float A[NC];
+    float A[NC], M[NC];
 #pragma unroll
-    for (int c = 0; c < NC; c++) A[c] = 0.0f;
+    for (int c = 0; c < NC; c++) A[c] = M[c] = 0.0f;
 
 #pragma unroll 4
     for (int b = 0; b < nb; b++) {
@@ -244,14 +285,24 @@ __global__ __launch_bounds__(256) void k_mmv_q0_ord(const uint8_t * __restrict__
         const uint32_t * qp = (const uint32_t *) (qa & ~(uintptr_t) 3);
         uint32_t q = __builtin_amdgcn_alignbyte(qp[1], qp[0], (uint32_t) (qa & 3));
         if constexpr (!Q8) q = (l < 4 ? q : q >> 4) & 0x0F0F0F0Fu;
+        float mw = 0.0f;
+        if constexpr (F::HAS_M) mw = mi_h2f((uint16_t) ((blk & 2) ? *(const uint32_t *) (blk + 2) & 0xFFFF : dw0 >> 16));
+        if constexpr (F::HAS_QH) {
+            const uintptr_t ha = blk + F::QH;
+            const uint32_t * hp = (const uint32_t *) (ha & ~(uintptr_t) 3);
+            const uint32_t qh = (ha & 3) ? __builtin_amdgcn_alignbyte(hp[1], hp[0], (uint32_t) (ha & 3)) : hp[0];
+            q |= q5_spread(qh >> (4 * l));  // elements 4l..4l+3: bits 4l.. of qh
+        }
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             if (NC > 1 && i11 + c >= g.ne11) break;
             const int64_t col = col0 + c;
             const int av = *(const int *) (act.qs + col * g.K + (int64_t) b * 32 + 4 * l);
-            // Q4_0: (q - 8) . y, exact (0xF8 = -8 per byte)
-            const int sumi = Q8 ? mi_dot4((int) q, av, 0) : mi_dot4((int) q, av, mi_dot4((int) 0xF8F8F8F8u, av, 0));
+            // Q4_0: (q - 8) . y, exact (0xF8 = -8 per byte); Q5_0: (q - 16) . y (0xF0)
+            constexpr int kSub = (int) (F::SUB == 16 ? 0xF0F0F0F0u : 0xF8F8F8F8u);
+            const int sumi = F::SUB == 0 ? mi_dot4((int) q, av, 0) : mi_dot4((int) q, av, mi_dot4(kSub, av, 0));
             A[c] = fmaf(dw * act.d[col * nb + b], (float) sumi, A[c]);  // _mm256_fmadd_ps, exact int -> float
+            if constexpr (F::HAS_M) M[c] = M[c] + mw * mi_h2f((uint16_t) act.s32[col * nb + b]);  // summs += x.m * y.s (exact product)
         }
     }
 #pragma unroll
@@ -260,6 +311,7 @@ __global__ __launch_bounds__(256) void k_mmv_q0_ord(const uint8_t * __restrict__
         float z = A[c] + __shfl_xor(A[c], 4, 8);
         z = z + __shfl_xor(z, 2, 8);
         z = z + __shfl_xor(z, 1, 8);
+        if constexpr (F::HAS_M) z = z + M[c];
         if (l == 0 && live && i11 + c < g.ne11)
             *(float *) ((char *) dst + (i11 + c) * g.nb1 + i12 * g.nb2 + i13 * g.nb3 + row * sizeof(float)) = z;
     }
@@ -546,14 +598,19 @@ mmv_geom make_geom(const mi_mm_desc & m, int NC) {
 void mi_mul_mat_q(const mi_mm_desc & m, const mi_act_q8 & act, hipStream_t s) {
     const int nc = m.ne11 >= 5 ? 8 : (int) m.ne11;
     const mi_act_q8 act_or_x = act;
-    if (mi_mmv_order() == 1 && (m.type == 2 || m.type == 8)) {  // reference CPU order: 8 rows per wave (mode 2 is a timing ablation of the fused kernel only)
-        const bool q8 = m.type == 8;
+    const bool q32 = m.type == 2 || m.type == 8 || m.type == 3 || m.type == 6 || m.type == 7;
+    if (mi_mmv_order() == 1 && q32) {  // reference CPU order: 8 rows per wave (mode 2 is a timing ablation of the fused kernel only)
 #define MI_MMV_ORD_LAUNCH(NC)                                                                               \
         do {                                                                                                 \
             const mmv_geom g = make_geom(m, NC);                                                             \
             const dim3 grid((unsigned) ((m.N + 31) / 32), (unsigned) (g.col_chunks * m.ne12 * m.ne13));     \
-            if (q8) hipLaunchKernelGGL((k_mmv_q0_ord<NC, true>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); \
-            else hipLaunchKernelGGL((k_mmv_q0_ord<NC, false>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); \
+            switch (m.type) {                                                                                \
+                case 8: hipLaunchKernelGGL((k_mmv_q0_ord<NC, 8>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); break; \
+                case 3: hipLaunchKernelGGL((k_mmv_q0_ord<NC, 3>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); break; \
+                case 6: hipLaunchKernelGGL((k_mmv_q0_ord<NC, 6>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); break; \
+                case 7: hipLaunchKernelGGL((k_mmv_q0_ord<NC, 7>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); break; \
+                default: hipLaunchKernelGGL((k_mmv_q0_ord<NC, 2>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); break; \
+            }                                                                                                \
         } while (0)
         switch (nc) {
             case 1: MI_MMV_ORD_LAUNCH(1); break;
@@ -611,8 +668,11 @@ void mi_mul_mat_q(const mi_mm_desc & m, const mi_act_q8 & act, hipStream_t s) {
     switch (m.type) {
         case 12: MI_MMV_SWITCH(k_mmv_kq, false); break;  // Q4_K
         case 13: MI_MMV_SWITCH(k_mmv_kq, true); break;   // Q5_K
-        case 2:  MI_MMV_SWITCH(k_mmv_q0, false); break;  // Q4_0
-        case 8:  MI_MMV_SWITCH(k_mmv_q0, true); break;   // Q8_0
+        case 2:  MI_MMV_SWITCH(k_mmv_q0, 2); break;  // Q4_0
+        case 8:  MI_MMV_SWITCH(k_mmv_q0, 8); break;  // Q8_0
+        case 3:  MI_MMV_SWITCH(k_mmv_q0, 3); break;  // Q4_1
+        case 6:  MI_MMV_SWITCH(k_mmv_q0, 6); break;  // Q5_0
+        case 7:  MI_MMV_SWITCH(k_mmv_q0, 7); break;  // Q5_1
         default: break;
     }
 }

@@ -101,12 +101,15 @@ size_t mi_stamps_read(uint64_t * host, size_t n, char * log, size_t log_size) {
 }
 
 
-// per-format launchers (mmv_fused_q4k.hip, _q5k, _q6k, _q40, _q80: one translation unit each)
+// per-format launchers (mmv_fused_q4k.hip, _q5k, _q6k, _q40, _q80, _q41, _q50, _q51: one translation unit each)
 void mi_mmv_launch_q4k(const mi_mmv_group & g, int variant, hipStream_t s);
 void mi_mmv_launch_q5k(const mi_mmv_group & g, int variant, hipStream_t s);
 void mi_mmv_launch_q40(const mi_mmv_group & g, int variant, hipStream_t s);
 void mi_mmv_launch_q80(const mi_mmv_group & g, int variant, hipStream_t s);
 void mi_mmv_launch_q6k(const mi_mmv_group & g, int variant, hipStream_t s);
+void mi_mmv_launch_q41(const mi_mmv_group & g, int variant, hipStream_t s);
+void mi_mmv_launch_q50(const mi_mmv_group & g, int variant, hipStream_t s);
+void mi_mmv_launch_q51(const mi_mmv_group & g, int variant, hipStream_t s);
 
 // LDS of the quantized activations: qs [NC][K] int8 | d [NC][K/QKA] f32 | s32 [NC][K/32] int16
 // (lds_bytes in mmv_fused_impl.h)
@@ -117,7 +120,7 @@ size_t mi_mmv_fused_lds_bytes(int type, int64_t K, int64_t ncols) {
 }
 
 bool mi_mmv_fused_supported(int type, int64_t K, int64_t ncols) {
-    if (type != 12 && type != 13 && type != 14 && type != 2 && type != 8) return false;
+    if (type != 12 && type != 13 && type != 14 && type != 2 && type != 8 && type != 3 && type != 6 && type != 7) return false;
     if (ncols < 1 || ncols > 8 || K % 256 != 0) return false;
     // more than 4 columns whose activations do not fit run as two launches of <= 4 columns
     return mi_mmv_fused_lds_bytes(type, K, ncols < 4 ? ncols : 4) <= 64 * 1024;  // + <= 36 KB of order scratch
@@ -155,11 +158,16 @@ static void mi_mul_mat_q_fused_launch(mi_mmv_group & g, hipStream_t s) {
     // boxes (profiles/r04p_gemv_sweep.txt, r04r_gemv_sweep.txt): Q4_K depth 3 (4096^2 +2..4 %,
     // 4096 x 11008 +2..4 %), Q5_K depth 2 (+2 %), Q4_0 pairs depth 3 (+1..4 %), Q8_0 depth 1 (+1 %)
     int variant = g_mi_tuning.mmv_variant;
-    if (variant == 0) variant = g.type == 12 ? 31 : g.type == 13 || g.type == 14 ? 21 : g.type == 2 ? 32 : 11;
+    // (Q4_1 / Q5_0 / Q5_1: depth 2 like the other 5- and 6-dword items, not tuned: DESIGN section 14)
+    if (variant == 0)
+        variant = g.type == 12 ? 31 : g.type == 13 || g.type == 14 || g.type == 3 || g.type == 6 || g.type == 7 ? 21 : g.type == 2 ? 32 : 11;
     switch (g.type) {
         case 12: mi_mmv_launch_q4k(g, variant, s); break;
         case 13: mi_mmv_launch_q5k(g, variant, s); break;
         case 14: mi_mmv_launch_q6k(g, variant, s); break;
+        case 3: mi_mmv_launch_q41(g, variant, s); break;
+        case 6: mi_mmv_launch_q50(g, variant, s); break;
+        case 7: mi_mmv_launch_q51(g, variant, s); break;
         case 2: mi_mmv_launch_q40(g, variant, s); break;
         case 8: mi_mmv_launch_q80(g, variant, s); break;
         default: break;

@@ -1,6 +1,6 @@
 // mmv_fused_impl.h -- the streaming decode GEMV k_mmv_stream (see mmv_fused.hip for the design),
 // its weight-format policies and launchers. Included by one translation unit per weight format
-// (mmv_fused_q4k.hip, _q5k, _q6k, _q40, _q80) so that the kernel instances compile in parallel; each
+// (mmv_fused_q4k.hip, _q5k, _q6k, _q40, _q80, _q41, _q50, _q51) so that the kernel instances compile in parallel; each
 // exports one mi_mmv_launch_* entry point that mmv_fused.hip's dispatcher calls.
 #pragma once
 
@@ -18,6 +18,8 @@ namespace {
 
 // ------------------------------------------------------------------ activations in LDS
 // layout per member: qs [NC][K] int8 | d [NC][K/QKA] f32 | s32 [NC][K/32] int16
+// (s32: the integer sum of the block's 32 quants; Q8_1 activations -- formats with F::S1 -- keep the
+// fp16 bits of the block's s = d * sum there instead)
 
 struct lds_act {
     int8_t * qs;
@@ -42,8 +44,12 @@ __host__ __device__ constexpr size_t lds_bytes(int NC, int64_t K) {
 // reference-order scratch (per wave: rows x columns x F::ord_words), after the activations
 __host__ __device__ constexpr size_t ord_offset(size_t act) { return (act + 15) & ~(size_t) 15; }
 
+// whether format F takes Q8_1 activations (F::S1; absent: no)
+template <class F, class = void> struct fmt_s1 : std::false_type {};
+template <class F> struct fmt_s1<F, std::enable_if_t<F::S1>> : std::true_type {};
+
 // one 256-element slice (four floats per lane) of column c into LDS
-template <int QKA>
+template <int QKA, bool S1 = false>
 __device__ __forceinline__ void quantize_slice(float4 v4, int lane, const lds_act & a, int64_t K, int c, int sl) {
     const float v[4] = {v4.x, v4.y, v4.z, v4.w};
     int8_t * qs = a.qs + c * K + sl * 256;
@@ -80,7 +86,10 @@ __device__ __forceinline__ void quantize_slice(float4 v4, int lane, const lds_ac
         if ((lane & 7) == 0) {
             const int blk = sl * 8 + (lane >> 3);
             a.d[c * (K / 32) + blk] = mi_h2f(mi_f2h(amax / 127.f));
-            a.s32[c * (K / 32) + blk] = (int16_t) s;
+            // Q8_1 (AVX2 quantize_row_q8_1, src/ggml-quants.c:806-867): s = fp16(d * (float) sum) with
+            // the f32 d = amax / 127 before its own fp16 rounding
+            if constexpr (S1) a.s32[c * (K / 32) + blk] = (int16_t) mi_mul_f2h(amax / 127.f, (float) s);
+            else a.s32[c * (K / 32) + blk] = (int16_t) s;
         }
     }
 }
@@ -514,6 +523,177 @@ struct FmtQ0 {
         float z = A + __shfl_xor(A, 4, 8);
         z = z + __shfl_xor(z, 2, 8);
         return z + __shfl_xor(z, 1, 8);
+    }
+};
+
+// Q4_1 (T = 3, 20 B: fp16 d, m, qs[16]), Q5_0 (6, 22 B: fp16 d, qh[4], qs[16]) and Q5_1 (7, 24 B:
+// fp16 d, m, qh[4], qs[16]) blocks of 32. Element j < 16 is the low nibble of qs[j], element j >= 16
+// the high nibble of qs[j - 16]; bit j of the little-endian qh is its fifth bit. Values q d + m
+// (Q4_1 / Q5_1, against Q8_1 activations: S1) resp. (q - 16) d (Q5_0, against Q8_0). Rows start
+// 16-byte aligned, so Q4_1 / Q5_1 blocks are whole aligned dwords; a Q5_0 block is 0 or 2 (mod 4)
+// and takes the six dwords covering it, re-aligned with v_alignbyte as FmtQ0 does.
+template <int T>
+struct FmtQ1 {
+    static constexpr bool KL = false;
+    static constexpr int QKA = 32;
+    static constexpr int ITEM = 32;
+    static constexpr bool HAS_M = T != 6, HAS_QH = T != 3;
+    static constexpr bool S1 = HAS_M;  // the activations' 16-bit slot: fp16 s (Q8_1), else the integer sum
+    static constexpr int BS = T == 3 ? 20 : T == 6 ? 22 : 24;
+    static constexpr int NW = T == 3 ? 5 : 6;
+    struct Regs {
+        uint32_t w[NW];
+        uint32_t off;  // Q5_0: byte offset of the block in w[0], 0 or 2
+    };
+    __device__ static __forceinline__ void load(Regs & r, const uint8_t * row, int item) {
+        const uint32_t blk = (uint32_t) item * BS;
+        r.off = T == 6 ? blk & 2 : 0;
+        const uint32_t base = blk - r.off;
+#pragma unroll
+        for (int i = 0; i < NW; i++) r.w[i] = *(const uint32_t *) (row + base + 4 * i);  // (Q5_0: 256 B tail slack)
+    }
+    // the block's levels as bytes (lo[i]: elements 4i.., hi[i]: elements 16 + 4i..) and its scales
+    struct Blk {
+        uint32_t lo[4], hi[4];
+        float d, m;
+    };
+    __device__ static __forceinline__ void unpack(const Regs & r, Blk & b) {
+        uint32_t qs[4], qh = 0;
+        if constexpr (T == 6) {
+            b.d = mi_h2f((uint16_t) ((r.off ? r.w[0] >> 16 : r.w[0]) & 0xFFFF));
+            b.m = 0.0f;
+            qh = r.off ? r.w[1] : __builtin_amdgcn_alignbyte(r.w[1], r.w[0], 2);
+#pragma unroll
+            for (int i = 0; i < 4; i++) qs[i] = r.off ? r.w[i + 2] : __builtin_amdgcn_alignbyte(r.w[i + 2], r.w[i + 1], 2);
+        } else {
+            b.d = mi_h2f((uint16_t) (r.w[0] & 0xFFFF));
+            b.m = mi_h2f((uint16_t) (r.w[0] >> 16));
+            if constexpr (HAS_QH) qh = r.w[1];
+#pragma unroll
+            for (int i = 0; i < 4; i++) qs[i] = r.w[NW - 4 + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            b.lo[i] = qs[i] & 0x0F0F0F0Fu;
+            b.hi[i] = (qs[i] >> 4) & 0x0F0F0F0Fu;
+            if constexpr (HAS_QH) {
+                // four fifth bits to bit 4 of four bytes: bit k of x * 0x00204081 lands at k, k + 7,
+                // k + 14, k + 21 (distinct, no carries); bits 0, 8, 16, 24 are kept
+                b.lo[i] |= ((((qh >> (4 * i)) & 0xFu) * 0x00204081u) & 0x01010101u) << 4;
+                b.hi[i] |= ((((qh >> (16 + 4 * i)) & 0xFu) * 0x00204081u) & 0x01010101u) << 4;
+            }
+        }
+    }
+    // tree order: the exact block integer (levels up to 31 fit mi_dot4's signed bytes), Q5_0 less
+    // 16 sum(y); Q4_1 / Q5_1 add m * s with the fp16-rounded s
+    __device__ static __forceinline__ float block_dot(const Blk & b, const int (&av)[8], int slot, float da, float acc) {
+        int sumi = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            sumi = mi_dot4((int) b.lo[i], av[i], sumi);
+            sumi = mi_dot4((int) b.hi[i], av[i + 4], sumi);
+        }
+        if constexpr (!HAS_M) sumi -= 16 * slot;
+        acc = fmaf((float) sumi, b.d * da, acc);
+        if constexpr (HAS_M) acc = fmaf(b.m, mi_h2f((uint16_t) slot), acc);
+        return acc;
+    }
+    template <int NC>
+    __device__ static __forceinline__ void dot(const Regs & r, int item, const lds_act & a, int64_t K, int ncols, float (&acc)[NC]) {
+        Blk b;
+        unpack(r, b);
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            if (NC > 1 && c >= ncols) break;
+            const int4 * p = (const int4 *) (a.qs + c * K + (int64_t) item * 32);
+            const int4 a0 = p[0], a1 = p[1];
+            const int av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+            acc[c] = block_dot(b, av, (int) a.s32[c * (K / 32) + item], a.d[c * (K / 32) + item], acc[c]);
+        }
+    }
+    struct Act {
+        int av[8];
+        int slot;
+        float da;
+    };
+    __device__ static __forceinline__ void act_load(Act & v, int item, const lds_act & a, int64_t K) {
+        const int4 * p = (const int4 *) (a.qs + (int64_t) item * 32);
+        const int4 a0 = p[0], a1 = p[1];
+        const int av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+        for (int i = 0; i < 8; i++) v.av[i] = av[i];
+        v.slot = (int) a.s32[item];
+        v.da = a.d[item];
+    }
+    __device__ static __forceinline__ float dot_act(const Regs & r, int, const Act & v, float acc) {
+        Blk b;
+        unpack(r, b);
+        return block_dot(b, v.av, v.slot, v.da, acc);
+    }
+
+    // CPU order (AVX2 ggml_vec_dot_q4_1_q8_1 src/ggml-quants.c:4006-4039, _q5_0_q8_0 :4279-4301,
+    // _q5_1_q8_1 :4623-4648): eight f32 lanes, lane l = the exact int32 sum of q[e] y[e] over
+    // e = 4l..4l+3 (Q5_0: q - 16), acc[l] = fma(x.d * y.d, (float) sum, acc[l]) over the blocks in
+    // order; Q4_1 / Q5_1 also one scalar chain summs += x.m * y.s (the product of two fp16 values
+    // is exact in f32, so a contracted fma gives the same bits). Scratch as FmtQ0's -- [l][slot], d
+    // at [8][slot] -- plus the m s products at [9][slot].
+    template <int NC>
+    __device__ static __forceinline__ void dot_ord(const Regs & r, int item, int slot, const lds_act & a, int64_t K, int ncols,
+                                                   uint32_t * scr, int cs, int S) {
+        Blk b;
+        unpack(r, b);
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            if (NC > 1 && c >= ncols) break;
+            const int4 * p = (const int4 *) (a.qs + c * K + (int64_t) item * 32);
+            const int4 a0 = p[0], a1 = p[1];
+            const int av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+            uint32_t * e = scr + c * cs + slot;
+#pragma unroll
+            for (int l = 0; l < 8; l++) {
+                const int lev = (int) (l < 4 ? b.lo[l & 3] : b.hi[l & 3]);
+                const int q = HAS_M ? mi_dot4(lev, av[l], 0) : mi_dot4(lev, av[l], mi_dot4((int) 0xF0F0F0F0u, av[l], 0));  // (q - 16) . y
+                e[l * S] = __float_as_uint((float) q);  // exact; _mm256_cvtepi32_ps
+            }
+            e[8 * S] = __float_as_uint(b.d * a.d[c * (K / 32) + item]);
+            if constexpr (HAS_M) e[9 * S] = __float_as_uint(b.m * mi_h2f((uint16_t) a.s32[c * (K / 32) + item]));
+        }
+    }
+    __device__ static __forceinline__ void chain(const uint32_t * scr, int l, int n_items, int S, float & A, float & M) {
+        if constexpr (!HAS_M) {
+            FmtQ0<true>::chain(scr, l, n_items, S, A, M);
+        } else {
+            // the lane's fma chain and summs (in block order) side by side: two independent chains
+            const float * q = (const float *) scr + l * S;
+            const float * d = (const float *) scr + 8 * S;
+            const float * ms = (const float *) scr + 9 * S;
+            int i = 0;
+            for (; i + 4 <= n_items; i += 4) {
+                const float4 qq = *(const float4 *) (q + i);
+                const float4 dd = *(const float4 *) (d + i);
+                const float4 mm = *(const float4 *) (ms + i);
+                A = fmaf(dd.x, qq.x, A);
+                M = M + mm.x;
+                A = fmaf(dd.y, qq.y, A);
+                M = M + mm.y;
+                A = fmaf(dd.z, qq.z, A);
+                M = M + mm.z;
+                A = fmaf(dd.w, qq.w, A);
+                M = M + mm.w;
+            }
+            for (; i < n_items; i++) {
+                A = fmaf(d[i], q[i], A);
+                M = M + ms[i];
+            }
+        }
+    }
+    static int ord_words(int nitems, int & stride) {
+        const int w = FmtQ0<true>::ord_words(nitems, stride);
+        return HAS_M ? w / 9 * 10 : w;
+    }
+    __device__ static __forceinline__ float finish(float A, float M) {
+        const float z = FmtQ0<true>::finish(A, 0.0f);
+        return HAS_M ? z + M : z;  // hsum_float_8(acc) + summs
     }
 };
 
@@ -1294,7 +1474,7 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
                     const int p = p0 + 4 * u;
                     if (p < total) {
                         const int c = p / nsl, sl = p - c * nsl;
-                        quantize_slice<F::QKA>(v[u], lane, act, K, c, sl);
+                        quantize_slice<F::QKA, fmt_s1<F>::value>(v[u], lane, act, K, c, sl);
                     }
                 }
             }

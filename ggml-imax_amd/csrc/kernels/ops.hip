@@ -2,7 +2,7 @@
 //
 // All are memory- or launch-bound. Each follows the reference CPU forward's rounding sequence so
 // that results are bit-identical where the CPU order is reproducible:
-//   get_rows   src/ggml.c:12920 (f16) / :13006 (f32) / :12874 (Q4_0, Q8_0, Q4_K, Q5_K, Q6_K) -- exact
+//   get_rows   src/ggml.c:12920 (f16) / :13006 (f32) / :12874 (Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q4_K, Q5_K, Q6_K) -- exact
 //   add / mul  src/ggml.c:8568 / :9687 (broadcast src1)      -- exact
 //   scale      src/ggml.c:12637                              -- exact
 //   norm       src/ggml.c:11353-11406 (double sums)          -- sums in double, then the same f32 ops
@@ -155,6 +155,27 @@ __device__ __forceinline__ float dequant_elem(const uint8_t * row, int64_t c) {
             return (float) ((j < 16 ? (b & 0x0F) : (b >> 4)) - 8) * d;
         } else {
             return (float) (int8_t) blk[2 + j] * d;
+        }
+    } else if constexpr (TYPE == 3 || TYPE == 6 || TYPE == 7) {
+        // Q4_1 (20 B: fp16 d, m, qs[16]) / Q5_0 (22 B: fp16 d, qh[4], qs[16]) / Q5_1 (24 B: fp16 d, m,
+        // qh[4], qs[16]) blocks of 32: dequantize_row_q4_1 / _q5_0 / _q5_1 (src/ggml-quants.c:1000-1072),
+        // q * d + m resp. (q - 16) * d. The product of a 5-bit level and an fp16 scale is exact in f32,
+        // so the reference build's contraction of q * d + m changes nothing. Q5_0 blocks are only
+        // 2-byte aligned: bytes and 2-byte copies only.
+        constexpr int BS = TYPE == 3 ? 20 : TYPE == 6 ? 22 : 24;
+        constexpr int QH = TYPE == 6 ? 2 : 4, QS = TYPE == 3 ? 4 : QH + 4;
+        const uint8_t * blk = row + (c >> 5) * BS;
+        const int j = (int) (c & 31);
+        uint16_t dh;
+        __builtin_memcpy(&dh, blk, 2);
+        const uint8_t b = blk[QS + (j & 15)];
+        int q = j < 16 ? (b & 0x0F) : (b >> 4);
+        if constexpr (TYPE != 3) q |= ((blk[QH + (j >> 3)] >> (j & 7)) & 1) << 4;  // bit j of the little-endian qh
+        if constexpr (TYPE == 6) return (float) (q - 16) * mi_h2f(dh);
+        else {
+            uint16_t mh;
+            __builtin_memcpy(&mh, blk + 2, 2);
+            return add_rn(mul_rn((float) q, mi_h2f(dh)), mi_h2f(mh));
         }
     } else if constexpr (TYPE == 14) {  // Q6_K (210 B) superblocks: ql[128] qh[64] int8 scales[16] fp16 d
         // dequantize_row_q6_K (:2713-2758): d * sc * q, two separately rounded multiplies
@@ -476,6 +497,9 @@ void mi_op_get_rows(const mi_tensor_desc & d, const mi_tensor_desc & a, const mi
     switch (a.type) {
         case 2: hipLaunchKernelGGL(k_get_rows_q<2>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
         case 8: hipLaunchKernelGGL(k_get_rows_q<8>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
+        case 3: hipLaunchKernelGGL(k_get_rows_q<3>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
+        case 6: hipLaunchKernelGGL(k_get_rows_q<6>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
+        case 7: hipLaunchKernelGGL(k_get_rows_q<7>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
         case 12: hipLaunchKernelGGL(k_get_rows_q<12>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
         case 13: hipLaunchKernelGGL(k_get_rows_q<13>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
         case 14: hipLaunchKernelGGL(k_get_rows_q<14>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
@@ -502,6 +526,9 @@ static void launch_get_rows_add(const mi_tensor_desc & d, const mi_tensor_desc &
         switch (b.type) {
             case 2: hipLaunchKernelGGL((k_get_rows_add<TA, 2>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0, st); break;
             case 8: hipLaunchKernelGGL((k_get_rows_add<TA, 8>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0, st); break;
+            case 3: hipLaunchKernelGGL((k_get_rows_add<TA, 3>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0, st); break;
+            case 6: hipLaunchKernelGGL((k_get_rows_add<TA, 6>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0, st); break;
+            case 7: hipLaunchKernelGGL((k_get_rows_add<TA, 7>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0, st); break;
             case 12: hipLaunchKernelGGL((k_get_rows_add<TA, 12>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0, st); break;
             case 13: hipLaunchKernelGGL((k_get_rows_add<TA, 13>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0, st); break;
             case 14: hipLaunchKernelGGL((k_get_rows_add<TA, 14>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0, st); break;
@@ -517,6 +544,9 @@ void mi_op_get_rows_add(const mi_tensor_desc & d, const mi_tensor_desc & a, cons
     switch (a.type) {
         case 2: launch_get_rows_add<2>(d, a, ia, b, ib, n, s); break;
         case 8: launch_get_rows_add<8>(d, a, ia, b, ib, n, s); break;
+        case 3: launch_get_rows_add<3>(d, a, ia, b, ib, n, s); break;
+        case 6: launch_get_rows_add<6>(d, a, ia, b, ib, n, s); break;
+        case 7: launch_get_rows_add<7>(d, a, ia, b, ib, n, s); break;
         case 12: launch_get_rows_add<12>(d, a, ia, b, ib, n, s); break;
         case 13: launch_get_rows_add<13>(d, a, ia, b, ib, n, s); break;
         case 14: launch_get_rows_add<14>(d, a, ia, b, ib, n, s); break;

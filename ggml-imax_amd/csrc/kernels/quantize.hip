@@ -6,6 +6,8 @@
 // build's exact rounding sequence:
 //   Q8_0: AVX2 quantize_row_q8_0 (src/ggml-quants.c:535-618): amax, d = amax/127 -> fp16 RNE,
 //         id = 127/amax, q = round-half-even(x*id)           (vmulps + vroundps)
+//   Q8_1: AVX2 quantize_row_q8_1 (src/ggml-quants.c:806-867): the Q8_0 quants and d, plus
+//         s = fp16(d32 * (float) sum(q)) with d32 = amax/127 before its fp16 rounding
 //   Q8_K: quantize_row_q8_K_reference (src/ggml-quants.c:3370-3407) as gcc -mfma compiles it:
 //         first max-|x| element (sign kept), iscale = -127/max, q = min(127, RNE(fma(iscale, x,
 //         1.5*2^23)) via the bit trick), d = 1/iscale, sums of 16 (we keep sums of 32).
@@ -30,14 +32,14 @@ static __device__ __forceinline__ int64_t xh_index(int64_t c, int64_t k, int64_t
     return nblk ? ((k >> 4) * nblk + c) * 16 + (k & 15) : c * K + k;
 }
 
-size_t mi_act_q8_bytes(int64_t K, int64_t ncols, bool is_q8K) {
+size_t mi_act_q8_bytes(int64_t K, int64_t ncols, bool is_q8K, bool is_q8_1) {
     const size_t qs = (size_t) (K * ncols + 255) & ~(size_t) 255;
     const size_t d = ((size_t) (K / (is_q8K ? 256 : 32)) * ncols * sizeof(float) + 255) & ~(size_t) 255;
-    const size_t s = is_q8K ? (((size_t) (K / 32) * ncols * sizeof(int16_t) + 255) & ~(size_t) 255) : 0;
+    const size_t s = is_q8K || is_q8_1 ? (((size_t) (K / 32) * ncols * sizeof(int16_t) + 255) & ~(size_t) 255) : 0;
     return qs + d + s;
 }
 
-mi_act_q8 mi_act_q8_carve(void * base, int64_t K, int64_t ncols, bool is_q8K) {
+mi_act_q8 mi_act_q8_carve(void * base, int64_t K, int64_t ncols, bool is_q8K, bool is_q8_1) {
     char * p = (char *) base;
     mi_act_q8 a;
     a.K = K;
@@ -46,14 +48,14 @@ mi_act_q8 mi_act_q8_carve(void * base, int64_t K, int64_t ncols, bool is_q8K) {
     p += ((size_t) (K * ncols) + 255) & ~(size_t) 255;
     a.d = (float *) p;
     p += ((size_t) (K / (is_q8K ? 256 : 32)) * ncols * sizeof(float) + 255) & ~(size_t) 255;
-    a.s32 = is_q8K ? (int16_t *) p : nullptr;
+    a.s32 = is_q8K || is_q8_1 ? (int16_t *) p : nullptr;
     return a;
 }
 
 // One 32-element block per half-wave, one element per lane; grid (column, group of 8 blocks).
 // XH: write f16(d * q) to xh[c*K + k] (the batched-prompt GEMM's operand, mmq.hip) instead of the
-// q8 blocks.
-template <bool XH>
+// q8 blocks. S1: Q8_1 -- also the block's s, as fp16 bits in act.s32.
+template <bool XH, bool S1 = false>
 __global__ __launch_bounds__(256) void k_quantize_q8_0(mi_src_cols x, int64_t K, mi_act_q8 act, uint16_t * xh,
                                                        int64_t xh_blk = 0) {
     const int64_t nb_per_col = K / 32;
@@ -74,6 +76,12 @@ __global__ __launch_bounds__(256) void k_quantize_q8_0(mi_src_cols x, int64_t K,
     }
     act.qs[c * K + b * 32 + l] = (int8_t) (int) q;
     if (l == 0) act.d[c * nb_per_col + b] = mi_h2f(mi_f2h(d));
+    if constexpr (S1) {
+        int sum = (int) q;
+#pragma unroll
+        for (int off = 16; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 32);
+        if (l == 0) act.s32[c * nb_per_col + b] = (int16_t) mi_mul_f2h(d, (float) sum);
+    }
 }
 
 // One 256-element superblock per wave, four consecutive elements per lane; grid (column, group of
@@ -169,6 +177,12 @@ void mi_quantize_q8_0(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, h
                        nullptr);
 }
 
+void mi_quantize_q8_1(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, hipStream_t s) {
+    if (act.ncols == 0 || K < 32) return;
+    hipLaunchKernelGGL((k_quantize_q8_0<false, true>), dim3((unsigned) act.ncols, (unsigned) ((K / 32 + 7) / 8)), dim3(256), 0, s, x, K,
+                       act, nullptr, 0);
+}
+
 void mi_quantize_q8_K(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, hipStream_t s) {
     if (act.ncols == 0 || K < 256) return;
     hipLaunchKernelGGL(k_quantize_q8_K<false>, dim3((unsigned) act.ncols, (unsigned) ((K / 256 + 3) / 4)), dim3(256), 0, s, x, K, act,
@@ -202,6 +216,7 @@ void mi_convert_f16(const mi_src_cols & x, int64_t K, uint16_t * out, hipStream_
 // -> from_float = quantize_row_q8_K / quantize_row_q8_0). Reference block layouts:
 //   block_q8_K (292 B): float d | int8 qs[256] | int16 bsums[16] (sums of 16 quants)
 //   block_q8_0 (34 B):  fp16 d  | int8 qs[32]
+//   block_q8_1 (36 B):  fp16 d  | fp16 s = d * sum(qs) | int8 qs[32]   (Q4_1 / Q5_1 weights)
 static __device__ __forceinline__ const char * col_base(const mi_src_cols & x, uint32_t c) {
     if (x.ne2 == 1 && x.ne3 == 1) return x.base + (size_t) c * x.nb1;
     const uint32_t ne1 = (uint32_t) x.ne1, ne2 = (uint32_t) x.ne2;
@@ -249,7 +264,8 @@ __global__ __launch_bounds__(256) void k_quantize_rows_q8_K(mi_src_cols x, int64
 
 // CPY F32 -> Q8_0: one block per half-wave (k_quantize_q8_0's rounding, the AVX2 branch of
 // quantize_row_q8_0, src/ggml-quants.c:535-618); grid (column, group of 8 blocks). Blocks are
-// 2-byte aligned: the quants go out as bytes.
+// 2-byte aligned: the quants go out as bytes. S1: Q8_1 blocks (quantize_row_q8_1 :806-867).
+template <bool S1>
 __global__ __launch_bounds__(256) void k_quantize_rows_q8_0(mi_src_cols x, int64_t K, mi_src_cols dl) {
     const int64_t b = (int64_t) blockIdx.y * 8 + (threadIdx.x >> 5);
     const int l = threadIdx.x & 31;
@@ -262,12 +278,18 @@ __global__ __launch_bounds__(256) void k_quantize_rows_q8_0(mi_src_cols x, int64
     const float d = amax / 127.f;
     const float id = amax != 0.0f ? 127.f / amax : 0.0f;
     const float q = __builtin_rintf(__fmul_rn(v, id));
-    char * blk = (char *) col_base(dl, c) + (size_t) b * 34;
-    blk[2 + l] = (char) (int8_t) (int) q;
+    char * blk = (char *) col_base(dl, c) + (size_t) b * (S1 ? 36 : 34);
+    blk[(S1 ? 4 : 2) + l] = (char) (int8_t) (int) q;
     if (l == 0) *(uint16_t *) blk = mi_f2h(d);
+    if constexpr (S1) {
+        int sum = (int) q;
+#pragma unroll
+        for (int off = 16; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 32);
+        if (l == 0) *(uint16_t *) (blk + 2) = mi_mul_f2h(d, (float) sum);
+    }
 }
 
-void mi_quantize_rows_q8(const mi_src_cols & x, int64_t K, bool is_q8K, const mi_src_cols & dst, hipStream_t s) {
+void mi_quantize_rows_q8(const mi_src_cols & x, int64_t K, bool is_q8K, const mi_src_cols & dst, hipStream_t s, bool is_q8_1) {
     const int64_t ncols = x.ne1 * x.ne2 * x.ne3;
     if (ncols == 0) return;
     if (is_q8K) {
@@ -276,7 +298,8 @@ void mi_quantize_rows_q8(const mi_src_cols & x, int64_t K, bool is_q8K, const mi
         if (a16) hipLaunchKernelGGL(k_quantize_rows_q8_K<true>, grid, dim3(256), 0, s, x, K, dst);
         else hipLaunchKernelGGL(k_quantize_rows_q8_K<false>, grid, dim3(256), 0, s, x, K, dst);
     }
-    else hipLaunchKernelGGL(k_quantize_rows_q8_0, dim3((unsigned) ncols, (unsigned) ((K / 32 + 7) / 8)), dim3(256), 0, s, x, K, dst);
+    else if (is_q8_1) hipLaunchKernelGGL(k_quantize_rows_q8_0<true>, dim3((unsigned) ncols, (unsigned) ((K / 32 + 7) / 8)), dim3(256), 0, s, x, K, dst);
+    else hipLaunchKernelGGL(k_quantize_rows_q8_0<false>, dim3((unsigned) ncols, (unsigned) ((K / 32 + 7) / 8)), dim3(256), 0, s, x, K, dst);
 }
 
 // Q8_K rows -> the kernels' activation layouts. One superblock per wave (four quant bytes per lane),
@@ -315,14 +338,15 @@ __global__ __launch_bounds__(256) void k_q8K_rows_to_act(mi_src_cols xs, int64_t
 }
 
 // Q8_0 rows -> activation layouts: one block per half-wave, one quant per lane; d as f32
-template <bool MMX>
+// (S1: Q8_1 rows -> the GEMV's SoA, the fp16 bits of s into act.s32)
+template <bool MMX, bool S1 = false>
 __global__ __launch_bounds__(256) void k_q8_0_rows_to_act(mi_src_cols xs, int64_t K, mi_act_q8 act, mi_act_mmx mx) {
     const int64_t b = (int64_t) blockIdx.y * 8 + (threadIdx.x >> 5);
     const int l = threadIdx.x & 31;
     if (b >= K / 32) return;
     const uint32_t c = blockIdx.x;
-    const char * blk = col_base(xs, c) + (size_t) b * 34;
-    const int8_t q = (int8_t) blk[2 + l];
+    const char * blk = col_base(xs, c) + (size_t) b * (S1 ? 36 : 34);
+    const int8_t q = (int8_t) blk[(S1 ? 4 : 2) + l];
     const float d = mi_h2f(*(const uint16_t *) blk);
     if constexpr (MMX) {
         mx.xq[(b * mx.ncols + c) * 32 + l] = q;
@@ -330,10 +354,14 @@ __global__ __launch_bounds__(256) void k_q8_0_rows_to_act(mi_src_cols xs, int64_
     } else {
         act.qs[(int64_t) c * K + b * 32 + l] = q;
         if (l == 0) act.d[(int64_t) c * (K / 32) + b] = d;
+        if constexpr (S1) {
+            if (l == 0) act.s32[(int64_t) c * (K / 32) + b] = *(const int16_t *) (blk + 2);
+        }
     }
 }
 
-void mi_q8_rows_to_act(const mi_src_cols & xs, int64_t K, bool is_q8K, const mi_act_q8 * act, const mi_act_mmx * mx, hipStream_t s) {
+void mi_q8_rows_to_act(const mi_src_cols & xs, int64_t K, bool is_q8K, const mi_act_q8 * act, const mi_act_mmx * mx, hipStream_t s,
+                       bool is_q8_1) {
     const int64_t ncols = xs.ne1 * xs.ne2 * xs.ne3;
     if (ncols == 0) return;
     const mi_act_q8 a = act ? *act : mi_act_q8{};
@@ -344,7 +372,8 @@ void mi_q8_rows_to_act(const mi_src_cols & xs, int64_t K, bool is_q8K, const mi_
         else hipLaunchKernelGGL(k_q8K_rows_to_act<false>, grid, dim3(256), 0, s, xs, K, a, m);
     } else {
         const dim3 grid((unsigned) ncols, (unsigned) ((K / 32 + 7) / 8));
-        if (mx) hipLaunchKernelGGL(k_q8_0_rows_to_act<true>, grid, dim3(256), 0, s, xs, K, a, m);
+        if (is_q8_1) hipLaunchKernelGGL((k_q8_0_rows_to_act<false, true>), grid, dim3(256), 0, s, xs, K, a, m);  // (GEMV layout only)
+        else if (mx) hipLaunchKernelGGL(k_q8_0_rows_to_act<true>, grid, dim3(256), 0, s, xs, K, a, m);
         else hipLaunchKernelGGL(k_q8_0_rows_to_act<false>, grid, dim3(256), 0, s, xs, K, a, m);
     }
 }

@@ -83,9 +83,10 @@ GGML_API int ggml_backend_mi355x_graph_stats_ex(ggml_backend_t backend, int64_t 
 GGML_API bool ggml_backend_mi355x_set_tuning(const char * name, int value);
 
 // Runs the device activation quantizer that GGML_OP_MUL_MAT uses for `vec_dot_type`
-// (GGML_TYPE_Q8_0 or GGML_TYPE_Q8_K) on ncols host columns of K floats and returns its
-// structure-of-arrays result: qs [ncols*K], d [ncols*K/QK], s32 [ncols*K/32] (Q8_K only,
-// sums of 32 quants). Lets tests compare the device rounding with the reference bit for bit.
+// (GGML_TYPE_Q8_0, GGML_TYPE_Q8_1 or GGML_TYPE_Q8_K) on ncols host columns of K floats and returns
+// its structure-of-arrays result: qs [ncols*K], d [ncols*K/QK], s32 [ncols*K/32] (Q8_K: sums of 32
+// quants; Q8_1: the fp16 bits of each block's s). Lets tests compare the device rounding with the
+// reference bit for bit.
 GGML_API bool ggml_backend_mi355x_quantize_activations(ggml_backend_t backend, int vec_dot_type, const float * x,
                                                        int64_t K, int64_t ncols, int8_t * qs, float * d, int16_t * s32);
 
