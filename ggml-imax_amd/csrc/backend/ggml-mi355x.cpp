@@ -552,6 +552,14 @@ static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
             if (b->type == GGML_TYPE_F32 || (b->type == GGML_TYPE_F16 && a->type == GGML_TYPE_F16 && !is_split_tensor(a))) return true;
             return b->type == q8_src1_type(a->type) && a->ne[0] % 256 == 0 && !is_split_tensor(a);
         }
+        case GGML_OP_MUL_MAT_ID: {
+            // experts of any mul_mat weight type on this device, F32 activations (quantized or converted
+            // here, as the reference does), I32 ids read by the kernels
+            const ggml_tensor * ids = op->src[2];
+            if (!mm_src0_supported(a->type) || is_split_tensor(a)) return false;
+            if (a->nb[0] != ggml_type_size(a->type) || b->nb[0] != ggml_type_size(b->type)) return false;
+            return b->type == GGML_TYPE_F32 && ids && ids->type == GGML_TYPE_I32;
+        }
         case GGML_OP_ADD:
         case GGML_OP_SUB:
         case GGML_OP_MUL:
@@ -896,6 +904,138 @@ static void op_mul_mat(mi_backend_ctx * ctx, ggml_tensor * dst) {
     MI_ASSERT(dst->nb[0] == sizeof(float));
     const ggml_tensor * src0 = dst->src[0];
     mul_mat_run(ctx, src0, src0->data, src0->ne[1], dst->src[1], (float *) dst->data, dst->nb[1], dst->nb[2], dst->nb[3]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// GGML_OP_MUL_MAT_ID (src/ggml.c:4852-4897, 12099-12279): dst[:, e, t] = as[:, :, ids[e, t]] . b[:, e % ne11, t]
+// ---------------------------------------------------------------------------------------------
+//
+// The ids stay in device memory: every kernel looks its expert up itself, so the node is a fixed
+// sequence of launches whatever the ids hold (stream capture, graph replay with new ids).
+//   one token (mmid_stream: up to that many), quantized experts of streaming shape: one grouped
+//     k_mmv_stream launch, a member per pair (the decode hot path; it quantizes b itself)
+//   otherwise b is converted once through get_activations (gate and up of one block share the
+//     copy) and the generic GEMVs run pair by pair, or, for quantized experts from
+//     mmid_group_min_tokens() tokens on (mmid_group 1), over the pairs grouped by expert on the
+//     device: up to 4 gathered columns per workgroup, each expert's weights read once per 4 pairs.
+
+// pairs grouped by expert from this many tokens on (tools/mmid_gemv.py, profiles/mmid_gemv.txt, Q4_K
+// 4096 x 14336, 2 of 8 experts): the reference-order GEMV (8 rows per wave) in chunks of 4 pairs is
+// 0.90x the pairwise time at 8 tokens, 0.78x at 16, 0.57x at 512 (1.16x at 2); the tree-order GEMV
+// (a wave per row: 139 VGPRs at 4 columns, ~240 at 8) never gained (1.05x at 512, 1.95x at 2)
+static int64_t mmid_group_min_tokens() { return mi_mmv_order() == 1 ? 8 : INT64_MAX; }
+
+static size_t mmid_tables_bytes(int64_t n_as, int64_t pairs) {
+    const size_t chunks = ((size_t) mi_mmid_max_chunks(n_as, pairs, 4) * sizeof(int4) + kBufferAlign - 1) & ~(kBufferAlign - 1);
+    return chunks + (((size_t) pairs * sizeof(int32_t) + kBufferAlign - 1) & ~(kBufferAlign - 1));
+}
+
+static bool fused_weight_aligned(const ggml_tensor * a);
+
+// every expert matrix meets the streaming GEMV's weight alignment (fused_weight_aligned on the
+// stack's base and on the expert stride)
+static bool mmid_stream_eligible(const ggml_tensor * n) {
+    static const bool no_fuse = getenv("GGML_MI355X_NO_FUSED_MMV") != nullptr;
+    const ggml_tensor * as = n->src[0], * b = n->src[1], * ids = n->src[2];
+    if (no_fuse || b->ne[2] > g_mi_tuning.mmid_stream || ids->ne[0] * b->ne[2] > kMiMaxMembers) return false;
+    if (!mi_mmv_fused_supported(as->type, as->ne[0], 1)) return false;
+    if (!fused_weight_aligned(as) || as->nb[2] % 16 != 0) return false;
+    if (((uintptr_t) b->data | b->nb[1] | b->nb[2]) % 16 != 0 || ids->nb[0] != sizeof(int32_t)) return false;
+    return true;
+}
+
+static void op_mul_mat_id(mi_backend_ctx * ctx, ggml_tensor * dst) {
+    const ggml_tensor * as = dst->src[0], * b = dst->src[1], * ids = dst->src[2];
+    // (the scheduler does not consult supports_op: anything it refuses stops here)
+    MI_ASSERT(ids && ids->type == GGML_TYPE_I32 && ids->ne[2] == 1 && ids->ne[3] == 1);
+    MI_ASSERT(mm_src0_supported(as->type) && as->nb[0] == ggml_type_size(as->type) && as->ne[3] == 1);
+    MI_ASSERT(!is_split_tensor(as) && "MUL_MAT_ID: experts in a split buffer are not supported");
+    MI_ASSERT(b->type == GGML_TYPE_F32 && b->nb[0] == sizeof(float) && b->ne[3] == 1 && "MUL_MAT_ID: src1 must be F32");
+    MI_ASSERT(as->ne[0] == b->ne[0] && ids->ne[1] == b->ne[2] && ids->ne[0] % b->ne[1] == 0);
+    MI_ASSERT(dst->type == GGML_TYPE_F32 && dst->nb[0] == sizeof(float) && dst->ne[0] == as->ne[1] && dst->ne[1] == ids->ne[0] &&
+              dst->ne[2] == b->ne[2]);
+    const int64_t K = as->ne[0], N = as->ne[1], n_as = as->ne[2];
+    const int64_t ne11 = b->ne[1], n_tokens = b->ne[2], n_ids = ids->ne[0];
+    MI_ASSERT(n_as < INT32_MAX && n_ids * n_tokens < INT32_MAX);
+    if (n_ids == 0 || n_tokens == 0 || N == 0) return;
+
+    if (mmid_stream_eligible(dst)) {
+        mi_mmv_group g;
+        g.type = as->type;
+        g.n = (int) (n_ids * n_tokens);
+        g.ncols = 1;
+        g.K = K;
+        g.N = N;
+        g.nb01 = as->nb[1];
+        g.xcol = b->nb[1];
+        g.ycol = dst->nb[1];
+        g.ids_w = as->data;
+        g.ids_nb02 = as->nb[2];
+        g.ids_n_as = (int) n_as;
+        for (int64_t t = 0; t < n_tokens; t++) {
+            for (int64_t e = 0; e < n_ids; e++) {
+                mi_mmv_member & m = g.m[e + n_ids * t];
+                m.W = (const char *) ids->data + e * ids->nb[0] + t * ids->nb[1];  // the id's address: resolved by the kernel
+                m.X = (const char *) b->data + (e % ne11) * b->nb[1] + t * b->nb[2];
+                m.dst = (float *) ((char *) dst->data + e * dst->nb[1] + t * dst->nb[2]);
+            }
+        }
+        mi_mul_mat_q_fused(g, ctx->stream);
+        ctx->last_launches++;
+        return;
+    }
+
+    mi_mm_desc m{};
+    m.W = as->data;
+    m.type = as->type;
+    m.K = K;
+    m.N = N;
+    m.ne02 = n_as;
+    m.ne03 = 1;
+    m.nb01 = as->nb[1];
+    m.nb02 = as->nb[2];
+    m.nb03 = as->nb[3];
+    m.ne11 = ne11;
+    m.ne12 = n_tokens;
+    m.ne13 = 1;
+    m.dst = (float *) dst->data;
+    m.nb1 = dst->nb[1];
+    m.nb2 = dst->nb[2];
+    m.nb3 = dst->nb[3];
+    m.id.ids = (const int32_t *) ids->data;
+    m.id.nb0 = ids->nb[0];
+    m.id.nb1 = ids->nb[1];
+    m.id.n_as = (int) n_as;
+    m.id.n_ids = (int) n_ids;
+
+    const int kind = act_kind(as->type);
+    const int cap = g_mi_tuning.mmid_group == 8 ? 8 : 4;  // (chunks of 4 measured faster than 8 at every size, both orders)
+    const bool grouped = kind >= 0 && kind != 2 && g_mi_tuning.mmid_group && n_as <= kMiMmidMaxExperts &&
+                         n_tokens >= (g_mi_tuning.mmid_group > 1 ? 2 : mmid_group_min_tokens());
+    // blockIdx.y counts the pairs, or the chunks of up to `cap` pairs
+    MI_ASSERT((grouped ? mi_mmid_max_chunks(n_as, n_ids * n_tokens, cap) : n_ids * n_tokens) <= 65535 && "MUL_MAT_ID: too many pairs for one launch");
+    if (kind < 0) {
+        MI_ASSERT(as->type == GGML_TYPE_F32);
+        mi_mul_mat_f32(m, src_cols(b), ctx->stream);
+    } else {
+        void * xa = get_activations(ctx, b, kind, K);
+        if (kind == 2) {
+            mi_mul_mat_f16(m, (const uint16_t *) xa, ctx->stream);
+        } else {
+            if (grouped) {
+                const int64_t pairs = n_ids * n_tokens;
+                m.id.chunk_cap = cap;
+                int4 * chunks = (int4 *) scratch_take(ctx, (size_t) mi_mmid_max_chunks(n_as, pairs, cap) * sizeof(int4));
+                int32_t * plist = (int32_t *) scratch_take(ctx, (size_t) pairs * sizeof(int32_t));
+                mi_mmid_group(m.id, n_tokens, chunks, plist, ctx->stream);
+                ctx->last_launches++;
+                m.id.chunks = chunks;
+                m.id.pairs = plist;
+            }
+            mi_mul_mat_q(m, mi_act_q8_carve(xa, K, ne11 * n_tokens, kind == 1, kind == 10), ctx->stream);
+        }
+    }
+    ctx->last_launches++;
 }
 
 // Per-slot helper context of the split path: its own stream (on the slot's device), scratch and
@@ -1272,6 +1412,14 @@ static size_t graph_scratch_bytes(const ggml_cgraph * cgraph) {
     size_t total = 0;
     for (int i = 0; i < cgraph->n_nodes; i++) {
         const ggml_tensor * n = cgraph->nodes[i];
+        if (n->op == GGML_OP_MUL_MAT_ID) {
+            // the converted activations and the grouping tables (whichever path runs)
+            const ggml_tensor * b = n->src[1];
+            const int kind = act_kind(n->src[0]->type);
+            if (kind >= 0) total += (act_bytes(kind, b->ne[0], b->ne[1] * b->ne[2] * b->ne[3]) + kBufferAlign - 1) & ~(kBufferAlign - 1);
+            if (n->src[2]) total += mmid_tables_bytes(n->src[0]->ne[2], n->src[2]->ne[0] * n->src[2]->ne[1]);
+            continue;
+        }
         if (n->op != GGML_OP_MUL_MAT) continue;
         if (n->src[0]->type == GGML_TYPE_F16 && n->src[1]->ne[1] == 1) {
             // a possible attention output projection (whatever op merged the heads -- ggml_cont as
@@ -2585,7 +2733,7 @@ static int graph_decode_order(const ggml_cgraph * g) {
     const bool view = sched_split_view(g);
     for (int i = 0; i < g->n_nodes; i++) {
         const ggml_tensor * n = g->nodes[i];
-        if (n->op != GGML_OP_MUL_MAT || !ggml_is_quantized(n->src[0]->type)) continue;
+        if ((n->op != GGML_OP_MUL_MAT && n->op != GGML_OP_MUL_MAT_ID) || !ggml_is_quantized(n->src[0]->type)) continue;
         const ggml_tensor * x = n->src[1];
         while (x->view_src || x->op == GGML_OP_RESHAPE || x->op == GGML_OP_VIEW || x->op == GGML_OP_PERMUTE ||
                x->op == GGML_OP_TRANSPOSE) {
@@ -2719,6 +2867,10 @@ static enum ggml_status mi_graph_launch_nodes(mi_backend_ctx * ctx, ggml_cgraph 
                 op_mul_mat(ctx, node);
                 break;
             }
+            case GGML_OP_MUL_MAT_ID:
+                // always its own launch(es): no fusion pass absorbs it or takes it as producer / consumer
+                op_mul_mat_id(ctx, node);
+                break;
             default:
                 op_companion(ctx, node);
         }
@@ -3096,6 +3248,14 @@ bool ggml_backend_mi355x_set_tuning(const char * name, int value) {
     }
     if (strcmp(name, "mmv_pro4") == 0 && value >= 0 && value <= 1) {
         g_mi_tuning.mmv_pro4 = value;
+        return true;
+    }
+    if (strcmp(name, "mmid_group") == 0 && (value == 0 || value == 1 || value == 4 || value == 8)) {
+        g_mi_tuning.mmid_group = value;
+        return true;
+    }
+    if (strcmp(name, "mmid_stream") == 0 && value >= 0 && value <= 8) {
+        g_mi_tuning.mmid_stream = value;
         return true;
     }
     if (strcmp(name, "mmqt_short") == 0 && value >= 0) {

@@ -495,6 +495,27 @@ struct ggml_tensor * ggml_mul_mat(struct ggml_context * ctx, struct ggml_tensor 
     return r;
 }
 
+// src/ggml.c:4852-4897 ggml_mul_mat_id: as [K, N, n_as], b [K, ne11, n_tokens], ids i32 [n_ids, n_tokens]
+// -> dst f32 [N, n_ids, n_tokens]; dst[:, e, t] = as[:, :, ids[e, t]] . b[:, e % ne11, t]
+struct ggml_tensor * ggml_mul_mat_id(struct ggml_context * ctx, struct ggml_tensor * as, struct ggml_tensor * b,
+                                     struct ggml_tensor * ids) {
+    GGML_ASSERT(!ggml_is_transposed(as));
+    GGML_ASSERT(ids->type == GGML_TYPE_I32);
+    GGML_ASSERT(as->ne[3] == 1);                      // one matrix per expert
+    GGML_ASSERT(b->ne[3] == 1);
+    GGML_ASSERT(ids->ne[2] == 1 && ids->ne[3] == 1);
+    GGML_ASSERT(ids->ne[1] == b->ne[2]);              // an expert list per token
+    GGML_ASSERT(as->ne[0] == b->ne[0]);
+    GGML_ASSERT(ids->ne[0] % b->ne[1] == 0);          // b's columns broadcast over the used experts
+    const int64_t ne[4] = {as->ne[1], ids->ne[0], b->ne[2], 1};
+    ggml_tensor * r = ggml_new_tensor(ctx, GGML_TYPE_F32, 4, ne);
+    r->op = GGML_OP_MUL_MAT_ID;
+    r->src[0] = as;
+    r->src[1] = b;
+    r->src[2] = ids;
+    return r;
+}
+
 // src/ggml.c:4842-4850
 void ggml_mul_mat_set_prec(struct ggml_tensor * a, enum ggml_prec prec) {
     const int32_t p = (int32_t) prec;

@@ -27,6 +27,27 @@ struct mi_src_cols {
     size_t nb1, nb2, nb3;
 };
 
+// GGML_OP_MUL_MAT_ID: the id table of an expert-routed mul_mat (ids == nullptr: a plain mul_mat).
+// The weight-batch index is read by the kernels, never by the host. With it the batch coordinate
+// (e, t), e < n_ids, t < ne12 takes its weight matrix from ids[e, t] (W + id * nb02), its
+// activation column from index (e % ne11) + ne11 * t of the converted activations and its
+// destination from e * nb1 + t * nb2. A pair whose id is outside [0, n_as) is skipped.
+struct mi_mm_ids {
+    const int32_t * ids = nullptr;  // ids[e, t] at (char *) ids + e * nb0 + t * nb1
+    size_t nb0 = 0, nb1 = 0;
+    int n_as = 0, n_ids = 0;
+    // the pairs grouped by expert on the device (mi_mmid_group), or null: pairwise
+    const int4 * chunks = nullptr;     // [mi_mmid_max_chunks] {expert, first, count <= chunk_cap (0: unused), 0}
+    const int32_t * pairs = nullptr;   // pair indices e + n_ids * t, expert by expert, each list t-major
+    int chunk_cap = 4;                 // pairs per chunk at most: 4 or 8 (columns per workgroup of the grouped GEMV)
+};
+// worst-case chunk count of a grouped MUL_MAT_ID: every expert's last chunk may be partial
+inline int64_t mi_mmid_max_chunks(int64_t n_as, int64_t pairs, int cap) { return n_as + (pairs + cap - 1) / cap; }
+constexpr int kMiMmidMaxExperts = 1024;  // mi_mmid_group keeps a counter per expert in LDS
+// One launch, capturable: the counting sort of ggml_compute_forward_mul_mat_id (src/ggml.c:12169-12184)
+// on the device. Fills chunks [mi_mmid_max_chunks(n_as, n_ids * n_tokens, id.chunk_cap)] and pairs [n_ids * n_tokens].
+void mi_mmid_group(const mi_mm_ids & id, int64_t n_tokens, int4 * chunks, int32_t * pairs, hipStream_t s);
+
 // Weight matrix / output description shared by the mul_mat launchers.
 struct mi_mm_desc {
     const void * W;        // src0 data
@@ -37,6 +58,7 @@ struct mi_mm_desc {
     int64_t ne11, ne12, ne13;  // src1 columns / batch dims
     float * dst;
     size_t nb1, nb2, nb3;  // dst strides in bytes (nb0 == 4)
+    mi_mm_ids id;          // MUL_MAT_ID (then ne02 = n_as, ne12 = n_tokens, ne03 = ne13 = 1)
 };
 
 size_t mi_act_q8_bytes(int64_t K, int64_t ncols, bool is_q8K, bool is_q8_1 = false);
@@ -107,6 +129,12 @@ struct mi_mmv_group {
     int q0r = 0;       // Q4_0 / Q8_0: every member's W is its 16-byte-aligned repacked copy (mi_planes_get type 2 / 8), nb01 = K / 32 * 18 / 34
     int pro_q = 0;     // set by the launcher (g_mi_tuning.mmv_pro4): one Q8_K column's norm prologue quantizes from registers
     mi_mmv_member m[kMiMaxMembers];
+    // GGML_OP_MUL_MAT_ID decode (behind m: the other fields keep their places; ncols == 1, no prologue / epilogue): ids_w != nullptr makes every
+    // member's W a pointer to its int32 expert id in device memory; the kernel streams
+    // ids_w + id * ids_nb02 and skips a member whose id is outside [0, ids_n_as)
+    const void * ids_w = nullptr;
+    size_t ids_nb02 = 0;
+    int ids_n_as = 0;
 };
 // Diagnostic builds (make DIAG=1): when non-null, the decode kernels write s_memrealtime phase
 // stamps of wave 0 of every workgroup here (kMiStampSlots per workgroup); release builds never do
@@ -151,6 +179,10 @@ struct mi_tuning {
     int f16_mt;       // tall F16 GEMVs (lm_head) of 2..8 columns, K <= 768, on the matrix cores (k_gemv_f16_mt): 1 on (default), 0 k_gemv_f16_tall
     int f16_m8;       // plain F16 GEMVs of 2..8 columns (K <= 4096, K % 32 == 0) on the matrix cores (k_gemv_f16_m8): 0 off (default), 1 on (diagnostic builds: measured slower)
     int mmqt_short;   // Q4_K prompts of 33..128 columns on k_mmqt (128 x 64 tiles) when a launch has at least this many of its workgroups (default 192; 0: never)
+    int mmid_group;   // MUL_MAT_ID of quantized experts: 1 = prompts from the measured crossover on (reference order: 8 tokens; tree order: never) run
+                      // over the pairs grouped by expert on the device (mi_mmid_group; up to 4 gathered columns per workgroup), 0 = pair by pair;
+                      // 4 / 8: grouped from 2 tokens on in either order with chunks of that many pairs (A/B timing)
+    int mmid_stream;  // MUL_MAT_ID of quantized experts: up to this many tokens run on the streaming decode kernel, a member per pair (0: never)
 };
 extern mi_tuning g_mi_tuning;
 // the order of the graph being launched when mmv_order is -1 (set by the backend per graph)

@@ -35,6 +35,7 @@ struct mmv_geom {
     size_t nb01, nb02, nb03;
     size_t nb1, nb2, nb3;
     int64_t col_chunks;      // ceil(ne11 / NC)
+    mi_mm_ids id;            // MUL_MAT_ID (kernels instantiated with ID != 0)
 };
 
 // Decode blockIdx.y into (first column i11, i12, i13) and return the weight row pointer base.
@@ -50,31 +51,94 @@ __device__ __forceinline__ void mmv_coords(const mmv_geom & g, int NC, int64_t &
     i03 = i13 / g.r3;
 }
 
-template <int NC>
-__device__ __forceinline__ void mmv_store(const mmv_geom & g, float * dst, int64_t row, int64_t i11, int64_t i12, int64_t i13,
+// What one workgroup's blockIdx.y stands for. ID 0: a chunk of NC consecutive columns of one
+// (i12, i13) batch (mmv_coords). ID 1 (NC == 1): the MUL_MAT_ID pair (e, t) = (y % n_ids, y / n_ids).
+// ID 2: a chunk of up to NC pairs of one expert, gathered by mi_mmid_group. A gathered column is
+// only an index into the SoA activations and a destination address; each keeps its own accumulators.
+template <int NC, int ID> struct mmv_item {
+    int64_t i11, i12, i13;   // ID 0
+    int64_t col0;            // ID 0: the first column's index in the activations
+    int64_t wofs;            // byte offset of the weight matrix in W
+    int n;                   // ID 2: pairs of this chunk
+    int colx[ID ? NC : 1];   // ID 1 / 2: activation column per pair
+    int pair[ID ? NC : 1];   // ID 1 / 2: the pair e + n_ids * t (32-bit and uniform: scalar registers)
+
+    // false: nothing to do for this workgroup (an id outside [0, n_as), a chunk past the last one).
+    // Uniform over the workgroup (blockIdx.y alone decides) and taken before any cross-lane operation.
+    __device__ __forceinline__ bool init(const mmv_geom & g) {
+        if constexpr (ID == 0) {
+            int64_t i02, i03;
+            mmv_coords(g, NC, i11, i12, i13, i02, i03);
+            wofs = i02 * g.nb02 + i03 * g.nb03;
+            col0 = i11 + g.ne11 * (i12 + g.ne12 * i13);
+            return true;
+        } else {
+            int expert;
+            const unsigned n_ids = (unsigned) g.id.n_ids, ne11 = (unsigned) g.ne11;
+            if constexpr (ID == 1) {
+                static_assert(NC == 1, "pairwise MUL_MAT_ID: one column per workgroup");
+                n = 1;
+                const unsigned e = blockIdx.y % n_ids, t = blockIdx.y / n_ids;
+                expert = *(const int32_t *) ((const char *) g.id.ids + e * g.id.nb0 + t * g.id.nb1);
+                pair[0] = (int) blockIdx.y;
+                colx[0] = (int) (e % ne11 + ne11 * t);
+            } else {
+                const int4 ch = g.id.chunks[blockIdx.y];
+                expert = ch.x;
+                n = ch.z;
+                if (n <= 0) return false;
+#pragma unroll
+                for (int c = 0; c < NC; c++) {
+                    const unsigned p = (unsigned) g.id.pairs[ch.y + (c < n ? c : 0)];
+                    pair[c] = (int) p;
+                    colx[c] = (int) ((p % n_ids) % ne11 + ne11 * (p / n_ids));
+                }
+            }
+            if ((unsigned) expert >= (unsigned) g.id.n_as) return false;
+            wofs = (int64_t) expert * g.nb02;
+            return true;
+        }
+    }
+    // column c of this workgroup exists (callers test it only for NC > 1)
+    __device__ __forceinline__ bool has(const mmv_geom & g, int c) const {
+        if constexpr (ID == 0) return i11 + c < g.ne11;
+        else return c < n;
+    }
+    __device__ __forceinline__ int64_t col(int c) const {
+        if constexpr (ID == 0) return col0 + c;
+        else return colx[c];
+    }
+    __device__ __forceinline__ float * out(const mmv_geom & g, float * dst, int64_t row, int c) const {
+        if constexpr (ID == 0) return (float *) ((char *) dst + (i11 + c) * g.nb1 + i12 * g.nb2 + i13 * g.nb3 + row * sizeof(float));
+        else {
+            const unsigned e = (unsigned) pair[c] % (unsigned) g.id.n_ids, t = (unsigned) pair[c] / (unsigned) g.id.n_ids;
+            return (float *) ((char *) dst + e * g.nb1 + t * g.nb2 + row * sizeof(float));
+        }
+    }
+};
+
+template <int NC, int ID>
+__device__ __forceinline__ void mmv_store(const mmv_geom & g, float * dst, int64_t row, const mmv_item<NC, ID> & it,
                                           float (&acc)[NC], int lane) {
 #pragma unroll
     for (int c = 0; c < NC; c++) {
         const float v = mi_wave_sum(acc[c]);
-        if (lane == 0 && i11 + c < g.ne11) {
-            *(float *) ((char *) dst + (i11 + c) * g.nb1 + i12 * g.nb2 + i13 * g.nb3 + row * sizeof(float)) = v;
-        }
+        if (lane == 0 && it.has(g, c)) *it.out(g, dst, row, c) = v;
     }
 }
 
 // ---------------------------------------------------------------- Q4_K / Q5_K x Q8_K
 
-template <int NC, bool Q5>
+template <int NC, bool Q5, int ID = 0>
 __global__ __launch_bounds__(256) void k_mmv_kq(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t) blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
     if (row >= g.N) return;
-    int64_t i11, i12, i13, i02, i03;
-    mmv_coords(g, NC, i11, i12, i13, i02, i03);
+    mmv_item<NC, ID> bi;
+    if (!bi.init(g)) return;
     constexpr int BS = Q5 ? 176 : 144;
-    const uint8_t * wrow = W + i02 * g.nb02 + i03 * g.nb03 + row * g.nb01;
+    const uint8_t * wrow = W + bi.wofs + row * g.nb01;
     const int nsb = (int) (g.K / 256);
-    const int64_t col0 = i11 + g.ne11 * (i12 + g.ne12 * i13);
 
     float acc[NC];
 #pragma unroll
@@ -113,8 +177,8 @@ __global__ __launch_bounds__(256) void k_mmv_kq(const uint8_t * __restrict__ W, 
         mi_scale_min_k4(2 * j + 1, hdr.y, hdr.z, hdr.w, sc1, m1);
 #pragma unroll
         for (int c = 0; c < NC; c++) {
-            if (NC > 1 && i11 + c >= g.ne11) break;
-            const int64_t col = col0 + c;
+            if (NC > 1 && !bi.has(g, c)) break;
+            const int64_t col = bi.col(c);
             const int4 * a = (const int4 *) (act.qs + col * g.K + (int64_t) s * 256 + 64 * j);
             const int4 a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
             const int alo[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
@@ -132,7 +196,7 @@ __global__ __launch_bounds__(256) void k_mmv_kq(const uint8_t * __restrict__ W, 
             acc[c] += dy * (dw * (float) sumi - dmw * (float) summ);
         }
     }
-    mmv_store<NC>(g, dst, row, i11, i12, i13, acc, lane);
+    mmv_store<NC, ID>(g, dst, row, bi, acc, lane);
 }
 
 // ---------------------------------------------------------------- 32-element blocks x Q8_0 / Q8_1
@@ -171,19 +235,18 @@ __device__ __forceinline__ void load_qs_unaligned(const uint8_t * p, uint32_t (&
     for (int i = 0; i < NBYTES / 4; i++) out[i] = __builtin_amdgcn_alignbyte(raw[i + 1], raw[i], shift);
 }
 
-template <int NC, int T>
+template <int NC, int T, int ID = 0>
 __global__ __launch_bounds__(256) void k_mmv_q0(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
     using F = q32_fmt<T>;
     constexpr bool Q8 = F::Q8;
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t) blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
     if (row >= g.N) return;
-    int64_t i11, i12, i13, i02, i03;
-    mmv_coords(g, NC, i11, i12, i13, i02, i03);
+    mmv_item<NC, ID> bi;
+    if (!bi.init(g)) return;
     constexpr int BS = F::BS;
-    const uint8_t * wrow = W + i02 * g.nb02 + i03 * g.nb03 + row * g.nb01;
+    const uint8_t * wrow = W + bi.wofs + row * g.nb01;
     const int nb = (int) (g.K / 32);
-    const int64_t col0 = i11 + g.ne11 * (i12 + g.ne12 * i13);
 
     float acc[NC];
 #pragma unroll
@@ -217,8 +280,8 @@ __global__ __launch_bounds__(256) void k_mmv_q0(const uint8_t * __restrict__ W, 
         if constexpr (F::HAS_M) mw = mi_h2f(*(const uint16_t *) (blk + 2));
 #pragma unroll
         for (int c = 0; c < NC; c++) {
-            if (NC > 1 && i11 + c >= g.ne11) break;
-            const int64_t col = col0 + c;
+            if (NC > 1 && !bi.has(g, c)) break;
+            const int64_t col = bi.col(c);
             const int4 * a = (const int4 *) (act.qs + col * g.K + (int64_t) b * 32);
             const int4 a0 = a[0], a1 = a[1];
             const int av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
@@ -236,7 +299,7 @@ __global__ __launch_bounds__(256) void k_mmv_q0(const uint8_t * __restrict__ W, 
             if constexpr (F::HAS_M) acc[c] += mw * mi_h2f((uint16_t) act.s32[col * nb + b]);  // m * s, the fp16-rounded s
         }
     }
-    mmv_store<NC>(g, dst, row, i11, i12, i13, acc, lane);
+    mmv_store<NC, ID>(g, dst, row, bi, acc, lane);
 }
 
 // Reference CPU order (mmv_order 1) for the Q4_0 / Q8_0 rows this generic path serves -- K % 256
@@ -253,7 +316,7 @@ __global__ __launch_bounds__(256) void k_mmv_q0(const uint8_t * __restrict__ W, 
 // levels in the lanes and one scalar chain summs += fp16(x.m) * fp16(y.s) over the blocks in order
 // (the product of two fp16 values is exact in f32, so a contracted fma gives the same bits); the
 // result is hsum_float_8(acc) + summs.
-template <int NC, int T>
+template <int NC, int T, int ID = 0>
 __global__ __launch_bounds__(256) void k_mmv_q0_ord(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
     using F = q32_fmt<T>;
     constexpr bool Q8 = F::Q8;
@@ -261,12 +324,11 @@ __global__ __launch_bounds__(256) void k_mmv_q0_ord(const uint8_t * __restrict__
     const int64_t row = (int64_t) blockIdx.x * 32 + (threadIdx.x >> 3);
     const bool live = row < g.N;
     const int64_t rc = live ? row : g.N - 1;  // (dead groups run a valid row: no early exit before the shuffles)
-    int64_t i11, i12, i13, i02, i03;
-    mmv_coords(g, NC, i11, i12, i13, i02, i03);
+    mmv_item<NC, ID> bi;
+    if (!bi.init(g)) return;
     constexpr int BS = F::BS;
-    const uint8_t * wrow = W + i02 * g.nb02 + i03 * g.nb03 + rc * g.nb01;
+    const uint8_t * wrow = W + bi.wofs + rc * g.nb01;
     const int nb = (int) (g.K / 32);
-    const int64_t col0 = i11 + g.ne11 * (i12 + g.ne12 * i13);
     // the lane's 4 quant bytes: block byte 2 + 4 l (nibble formats: QS + 4 (l & 3), nibble half l >> 2)
     const int qoff = F::QS + 4 * (Q8 ? l : (l & 3));
 
@@ -295,8 +357,8 @@ __global__ __launch_bounds__(256) void k_mmv_q0_ord(const uint8_t * __restrict__
         }
 #pragma unroll
         for (int c = 0; c < NC; c++) {
-            if (NC > 1 && i11 + c >= g.ne11) break;
-            const int64_t col = col0 + c;
+            if (NC > 1 && !bi.has(g, c)) break;
+            const int64_t col = bi.col(c);
             const int av = *(const int *) (act.qs + col * g.K + (int64_t) b * 32 + 4 * l);
             // Q4_0: (q - 8) . y, exact (0xF8 = -8 per byte); Q5_0: (q - 16) . y (0xF0)
             constexpr int kSub = (int) (F::SUB == 16 ? 0xF0F0F0F0u : 0xF8F8F8F8u);
@@ -312,8 +374,7 @@ __global__ __launch_bounds__(256) void k_mmv_q0_ord(const uint8_t * __restrict__
         z = z + __shfl_xor(z, 2, 8);
         z = z + __shfl_xor(z, 1, 8);
         if constexpr (F::HAS_M) z = z + M[c];
-        if (l == 0 && live && i11 + c < g.ne11)
-            *(float *) ((char *) dst + (i11 + c) * g.nb1 + i12 * g.nb2 + i13 * g.nb3 + row * sizeof(float)) = z;
+        if (l == 0 && live && bi.has(g, c)) *bi.out(g, dst, row, c) = z;
     }
 }
 
@@ -327,18 +388,17 @@ __global__ __launch_bounds__(256) void k_mmv_q0_ord(const uint8_t * __restrict__
 // contracts, summs = fma(dmin, (float) sum_k prod[k], summs) (Q5_K). Result hsum_float_8(acc) +
 // ((acc_m0 + acc_m2) + (acc_m1 + acc_m3)), resp. + summs. Here eight lanes are the eight CPU lanes
 // of one row (8 rows per wave), lanes 0..3 also the four acc_m lanes.
-template <int NC, bool Q5>
+template <int NC, bool Q5, int ID = 0>
 __global__ __launch_bounds__(256) void k_mmv_kq_ord(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
     const int l = threadIdx.x & 7;
     const int64_t row = (int64_t) blockIdx.x * 32 + (threadIdx.x >> 3);
     const bool live = row < g.N;
     const int64_t rc = live ? row : g.N - 1;  // (dead groups run a valid row: no early exit before the shuffles)
-    int64_t i11, i12, i13, i02, i03;
-    mmv_coords(g, NC, i11, i12, i13, i02, i03);
+    mmv_item<NC, ID> bi;
+    if (!bi.init(g)) return;
     constexpr int BS = Q5 ? 176 : 144;
-    const uint8_t * wrow = W + i02 * g.nb02 + i03 * g.nb03 + rc * g.nb01;
+    const uint8_t * wrow = W + bi.wofs + rc * g.nb01;
     const int nsb = (int) (g.K / 256);
-    const int64_t col0 = i11 + g.ne11 * (i12 + g.ne12 * i13);
 
     float A[NC], M[NC];
 #pragma unroll
@@ -366,8 +426,8 @@ __global__ __launch_bounds__(256) void k_mmv_kq_ord(const uint8_t * __restrict__
         }
 #pragma unroll
         for (int c = 0; c < NC; c++) {
-            if (NC > 1 && i11 + c >= g.ne11) break;
-            const int64_t col = col0 + c;
+            if (NC > 1 && !bi.has(g, c)) break;
+            const int64_t col = bi.col(c);
             const int8_t * aq = act.qs + col * g.K + (int64_t) s * 256 + 4 * l;
             int sumi = 0;
 #pragma unroll
@@ -405,8 +465,7 @@ __global__ __launch_bounds__(256) void k_mmv_kq_ord(const uint8_t * __restrict__
             m = m + __shfl_xor(m, 2, 8);
             m = m + __shfl_xor(m, 1, 8);
         }
-        if (l == 0 && live && i11 + c < g.ne11)
-            *(float *) ((char *) dst + (i11 + c) * g.nb1 + i12 * g.nb2 + i13 * g.nb3 + row * sizeof(float)) = z + m;
+        if (l == 0 && live && bi.has(g, c)) *bi.out(g, dst, row, c) = z + m;
     }
 }
 
@@ -438,16 +497,15 @@ __device__ __forceinline__ uint32_t ld32_a2(const uint8_t * p) {
 // four 16-element sub-blocks at elements 128h + 32t + 16u (t = 0..3), scale index 8h + 2t + u.
 // Four items per superblock, so a K = 4096 row is one item per lane. The item's integer sum
 // (up to 4 * 8,323,072, over 2^24) is accumulated in int32 and converted once.
-template <int NC>
+template <int NC, int ID = 0>
 __global__ __launch_bounds__(256) void k_mmv_q6k(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t) blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
     if (row >= g.N) return;
-    int64_t i11, i12, i13, i02, i03;
-    mmv_coords(g, NC, i11, i12, i13, i02, i03);
-    const uint8_t * wrow = W + i02 * g.nb02 + i03 * g.nb03 + row * g.nb01;
+    mmv_item<NC, ID> bi;
+    if (!bi.init(g)) return;
+    const uint8_t * wrow = W + bi.wofs + row * g.nb01;
     const int nsb = (int) (g.K / 256);
-    const int64_t col0 = i11 + g.ne11 * (i12 + g.ne12 * i13);
 
     float acc[NC];
 #pragma unroll
@@ -475,8 +533,8 @@ __global__ __launch_bounds__(256) void k_mmv_q6k(const uint8_t * __restrict__ W,
         const float dw = mi_h2f(*(const uint16_t *) (blk + 208));
 #pragma unroll
         for (int c = 0; c < NC; c++) {
-            if (NC > 1 && i11 + c >= g.ne11) break;
-            const int64_t col = col0 + c;
+            if (NC > 1 && !bi.has(g, c)) break;
+            const int64_t col = bi.col(c);
             const int4 * a = (const int4 *) (act.qs + col * g.K + (int64_t) s * 256 + 128 * h + 16 * u);
             int sumi = 0;
 #pragma unroll
@@ -491,7 +549,7 @@ __global__ __launch_bounds__(256) void k_mmv_q6k(const uint8_t * __restrict__ W,
             acc[c] += (act.d[col * nsb + s] * dw) * (float) sumi;
         }
     }
-    mmv_store<NC>(g, dst, row, i11, i12, i13, acc, lane);
+    mmv_store<NC, ID>(g, dst, row, bi, acc, lane);
 }
 
 // Reference order: the AVX2 dot keeps eight int32 lanes per superblock, lane l = sum over the
@@ -501,17 +559,16 @@ __global__ __launch_bounds__(256) void k_mmv_q6k(const uint8_t * __restrict__ W,
 // (float) sumi[l], acc[l]) over the superblocks in order and hsum_float_8. A lane sum is at most
 // 8 * 128 * 4 * 32 * 127 = 16,646,144 < 2^24, so the conversion is exact. Here eight lanes are the
 // eight CPU lanes of one row (8 rows per wave), as k_mmv_kq_ord.
-template <int NC>
+template <int NC, int ID = 0>
 __global__ __launch_bounds__(256) void k_mmv_q6k_ord(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
     const int l = threadIdx.x & 7;
     const int64_t row = (int64_t) blockIdx.x * 32 + (threadIdx.x >> 3);
     const bool live = row < g.N;
     const int64_t rc = live ? row : g.N - 1;  // (dead groups run a valid row: no early exit before the shuffles)
-    int64_t i11, i12, i13, i02, i03;
-    mmv_coords(g, NC, i11, i12, i13, i02, i03);
-    const uint8_t * wrow = W + i02 * g.nb02 + i03 * g.nb03 + rc * g.nb01;
+    mmv_item<NC, ID> bi;
+    if (!bi.init(g)) return;
+    const uint8_t * wrow = W + bi.wofs + rc * g.nb01;
     const int nsb = (int) (g.K / 256);
-    const int64_t col0 = i11 + g.ne11 * (i12 + g.ne12 * i13);
     const int hi = l >> 2;  // which 16-element half of each 32-group the lane's elements lie in
 
     float A[NC];
@@ -536,8 +593,8 @@ __global__ __launch_bounds__(256) void k_mmv_q6k_ord(const uint8_t * __restrict_
         for (int j = 0; j < 8; j++) sc[j] = ((const int8_t *) blk)[192 + 2 * j + hi];
 #pragma unroll
         for (int c = 0; c < NC; c++) {
-            if (NC > 1 && i11 + c >= g.ne11) break;
-            const int64_t col = col0 + c;
+            if (NC > 1 && !bi.has(g, c)) break;
+            const int64_t col = bi.col(c);
             const int8_t * aq = act.qs + col * g.K + (int64_t) s * 256 + 4 * l;
             int sumi = 0;
 #pragma unroll
@@ -551,8 +608,7 @@ __global__ __launch_bounds__(256) void k_mmv_q6k_ord(const uint8_t * __restrict_
         float z = A[c] + __shfl_xor(A[c], 4, 8);
         z = z + __shfl_xor(z, 2, 8);
         z = z + __shfl_xor(z, 1, 8);
-        if (l == 0 && live && i11 + c < g.ne11)
-            *(float *) ((char *) dst + (i11 + c) * g.nb1 + i12 * g.nb2 + i13 * g.nb3 + row * sizeof(float)) = z;
+        if (l == 0 && live && bi.has(g, c)) *bi.out(g, dst, row, c) = z;
     }
 }
 
@@ -572,6 +628,7 @@ mmv_geom make_geom(const mi_mm_desc & m, int NC) {
     g.nb2 = m.nb2;
     g.nb3 = m.nb3;
     g.col_chunks = (m.ne11 + NC - 1) / NC;
+    g.id = m.id;
     return g;
 }
 
@@ -595,7 +652,117 @@ mmv_geom make_geom(const mi_mm_desc & m, int NC) {
         default: MI_MMV_LAUNCH(KERNEL, 8, ##__VA_ARGS__); break;    \
     }
 
+// GGML_OP_MUL_MAT_ID: pair by pair (ID 1, one column per workgroup), or, with the device-built
+// chunk table, up to chunk_cap (8 or 4) gathered columns of one expert per workgroup (ID 2; the grid covers the
+// worst-case chunk count, workgroups past the real one exit at once). Same per-column arithmetic as
+// the plain kernels in both orders.
+static void mi_mul_mat_q_ids(const mi_mm_desc & m, const mi_act_q8 & act, hipStream_t s) {
+    const bool grouped = m.id.chunks != nullptr;
+    const bool cap4 = m.id.chunk_cap == 4;
+    const int64_t pairs = (int64_t) m.id.n_ids * m.ne12;
+    const unsigned gy = (unsigned) (grouped ? mi_mmid_max_chunks(m.id.n_as, pairs, m.id.chunk_cap) : pairs);
+    const bool ord = mi_mmv_order() == 1;
+    const mmv_geom g = make_geom(m, 1);
+    const dim3 grid((unsigned) (ord ? (m.N + 31) / 32 : (m.N + kRowsPerBlock - 1) / kRowsPerBlock), gy);
+#define MI_MMID_LAUNCH(KERNEL, ...)                                                                                       \
+    do {                                                                                                                   \
+        if (grouped && cap4) hipLaunchKernelGGL((KERNEL<4, ##__VA_ARGS__, 2>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); \
+        else if (grouped) hipLaunchKernelGGL((KERNEL<8, ##__VA_ARGS__, 2>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); \
+        else hipLaunchKernelGGL((KERNEL<1, ##__VA_ARGS__, 1>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); \
+    } while (0)
+#define MI_MMID_LAUNCH0(KERNEL)                                                                                            \
+    do {                                                                                                                   \
+        if (grouped && cap4) hipLaunchKernelGGL((KERNEL<4, 2>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); \
+        else if (grouped) hipLaunchKernelGGL((KERNEL<8, 2>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g);     \
+        else hipLaunchKernelGGL((KERNEL<1, 1>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g);             \
+    } while (0)
+    switch (m.type) {
+        case 12: if (ord) MI_MMID_LAUNCH(k_mmv_kq_ord, false); else MI_MMID_LAUNCH(k_mmv_kq, false); break;
+        case 13: if (ord) MI_MMID_LAUNCH(k_mmv_kq_ord, true); else MI_MMID_LAUNCH(k_mmv_kq, true); break;
+        case 14: if (ord) MI_MMID_LAUNCH0(k_mmv_q6k_ord); else MI_MMID_LAUNCH0(k_mmv_q6k); break;
+        case 2: if (ord) MI_MMID_LAUNCH(k_mmv_q0_ord, 2); else MI_MMID_LAUNCH(k_mmv_q0, 2); break;
+        case 8: if (ord) MI_MMID_LAUNCH(k_mmv_q0_ord, 8); else MI_MMID_LAUNCH(k_mmv_q0, 8); break;
+        case 3: if (ord) MI_MMID_LAUNCH(k_mmv_q0_ord, 3); else MI_MMID_LAUNCH(k_mmv_q0, 3); break;
+        case 6: if (ord) MI_MMID_LAUNCH(k_mmv_q0_ord, 6); else MI_MMID_LAUNCH(k_mmv_q0, 6); break;
+        case 7: if (ord) MI_MMID_LAUNCH(k_mmv_q0_ord, 7); else MI_MMID_LAUNCH(k_mmv_q0, 7); break;
+        default: break;
+    }
+#undef MI_MMID_LAUNCH
+#undef MI_MMID_LAUNCH0
+}
+
+// The counting sort of the reference's MUL_MAT_ID (src/ggml.c:12169-12184: per-expert row lists in
+// (t, e) order) as one workgroup. The ids are staged through LDS in tiles; thread x scans them for
+// the experts x, x + 256, ... (every thread reads the same LDS word: a broadcast), first counting,
+// then, after the exclusive sums over the experts, writing its experts' pair lists in the
+// reference's order and their chunks of at most `cap` pairs. Chunk entries past the last real one get
+// count 0. Ids outside [0, n_as) are in no list.
+constexpr int kMmidTile = 4096;
+__global__ __launch_bounds__(256) void k_mmid_group(mi_mm_ids id, int n_tokens, int max_chunks, int cap, int4 * __restrict__ chunks,
+                                                    int32_t * __restrict__ pairs) {
+    __shared__ int tile[kMmidTile];
+    __shared__ int cnt[kMiMmidMaxExperts];
+    __shared__ int first[kMiMmidMaxExperts];   // start of the expert's pair list
+    __shared__ int chunk0[kMiMmidMaxExperts];  // its first chunk
+    __shared__ int nchunks;
+    const int tid = threadIdx.x;
+    const int P = id.n_ids * n_tokens;
+    for (int x = tid; x < id.n_as; x += 256) cnt[x] = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        for (int base = 0; base < P; base += kMmidTile) {
+            const int nt = P - base < kMmidTile ? P - base : kMmidTile;
+            __syncthreads();
+            for (int i = tid; i < nt; i += 256) {
+                const int p = base + i;
+                const int64_t e = p % id.n_ids, t = p / id.n_ids;
+                tile[i] = *(const int32_t *) ((const char *) id.ids + e * id.nb0 + t * id.nb1);
+            }
+            __syncthreads();
+            for (int x = tid; x < id.n_as; x += 256) {
+                int c = cnt[x];
+                if (pass == 0) {
+                    for (int i = 0; i < nt; i++) c += tile[i] == x;
+                } else {
+                    for (int i = 0; i < nt; i++) {
+                        if (tile[i] == x) pairs[c++] = base + i;
+                    }
+                }
+                cnt[x] = c;
+            }
+        }
+        __syncthreads();
+        if (pass == 0) {
+            if (tid == 0) {
+                int f = 0, ch = 0;
+                for (int x = 0; x < id.n_as; x++) {
+                    first[x] = f;
+                    chunk0[x] = ch;
+                    f += cnt[x];
+                    ch += (cnt[x] + cap - 1) / cap;
+                }
+                nchunks = ch;
+            }
+            __syncthreads();
+            for (int x = tid; x < id.n_as; x += 256) {
+                const int n = cnt[x];
+                for (int k = 0; cap * k < n; k++) chunks[chunk0[x] + k] = make_int4(x, first[x] + cap * k, n - cap * k < cap ? n - cap * k : cap, 0);
+                cnt[x] = first[x];  // pass 1: the write cursor
+            }
+            for (int k = nchunks + tid; k < max_chunks; k += 256) chunks[k] = make_int4(0, 0, 0, 0);
+        }
+    }
+}
+
+void mi_mmid_group(const mi_mm_ids & id, int64_t n_tokens, int4 * chunks, int32_t * pairs, hipStream_t s) {
+    hipLaunchKernelGGL(k_mmid_group, dim3(1), dim3(256), 0, s, id, (int) n_tokens,
+                       (int) mi_mmid_max_chunks(id.n_as, (int64_t) id.n_ids * n_tokens, id.chunk_cap), id.chunk_cap, chunks, pairs);
+}
+
 void mi_mul_mat_q(const mi_mm_desc & m, const mi_act_q8 & act, hipStream_t s) {
+    if (m.id.ids) {
+        mi_mul_mat_q_ids(m, act, s);
+        return;
+    }
     const int nc = m.ne11 >= 5 ? 8 : (int) m.ne11;
     const mi_act_q8 act_or_x = act;
     const bool q32 = m.type == 2 || m.type == 8 || m.type == 3 || m.type == 6 || m.type == 7;

@@ -1328,7 +1328,10 @@ __device__ __forceinline__ void store_out(const mi_mmv_group & g, float * dst, i
 // MR > 1 (one column, rows of at most 16 items: tall short-K matrices such as GPT-2's lm_head,
 // K = 768 = 12 Q4_K items): each wave step covers MR rows, 16 lanes per row (lane 16 r + i: item i
 // of the step's row r) instead of one row on 64 lanes of which K / ITEM do work
-template <class F, int NC, int PD, int IPL, bool TAIL, bool ORD, bool PRO, bool XF, int MR = 1>
+// IDS (GGML_OP_MUL_MAT_ID decode): the member's W field points at its expert id in device memory;
+// the workgroup reads it at entry and streams expert id's matrix of the stack g.ids_w (stride
+// g.ids_nb02). An id outside [0, g.ids_n_as) ends the workgroup here, before any barrier.
+template <class F, int NC, int PD, int IPL, bool TAIL, bool ORD, bool PRO, bool XF, int MR = 1, bool IDS = false>
 __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     MI_STAMP(g.stamps, 0);
@@ -1339,6 +1342,11 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
     const int member = blockIdx.x / g.blocks_per_member;
     const int rb = blockIdx.x - member * g.blocks_per_member;
     const uint8_t * W = (const uint8_t *) g.m[member].W;
+    if constexpr (IDS) {
+        const int expert = __builtin_amdgcn_readfirstlane(*(const int32_t *) W);
+        if ((unsigned) expert >= (unsigned) g.ids_n_as) return;
+        W = (const uint8_t *) g.ids_w + (size_t) expert * g.ids_nb02;
+    }
     const char * X = g.m[member].X;
     float * dst = g.m[member].dst;
     const int64_t K = g.K;
@@ -1847,7 +1855,7 @@ static int mi_cu_count() {
     return n;
 }
 
-template <class F, int NC, int PD, int IPL, bool TAIL, bool ORD, bool PRO = false, bool XF = false, int MR = 1>
+template <class F, int NC, int PD, int IPL, bool TAIL, bool ORD, bool PRO = false, bool XF = false, int MR = 1, bool IDS = false>
 void launch_one(mi_mmv_group g, hipStream_t s) {
     const size_t act = lds_bytes<F::QKA>(NC, g.K);
     size_t lds = act;
@@ -1873,7 +1881,7 @@ void launch_one(mi_mmv_group g, hipStream_t s) {
     }
     if constexpr (MR > 1 && ORD) {
         if (g.ord_rows < MR) {  // a chain pass must hold whole multi-row steps: the one-row form
-            launch_one<F, NC, PD, IPL, TAIL, ORD, PRO, XF, 1>(g, s);
+            launch_one<F, NC, PD, IPL, TAIL, ORD, PRO, XF, 1, IDS>(g, s);
             return;
         }
     }
@@ -1882,7 +1890,7 @@ void launch_one(mi_mmv_group g, hipStream_t s) {
         g.pro_off = (int) ord_offset(lds);
         lds = (size_t) g.pro_off + (size_t) NC * g.K * sizeof(float);
     }
-    const void * fn = (const void *) k_mmv_stream<F, NC, PD, IPL, TAIL, ORD, PRO, XF, MR>;
+    const void * fn = (const void *) k_mmv_stream<F, NC, PD, IPL, TAIL, ORD, PRO, XF, MR, IDS>;
     if (lds > 64 * 1024) {
         static bool attr_set = false;  // per instance
         if (!attr_set) {
@@ -1909,7 +1917,7 @@ void launch_one(mi_mmv_group g, hipStream_t s) {
     g.rows_per_block = rows;
     g.blocks_per_member = (int) ((g.N + rows - 1) / rows);
     g.stamps = mi_stamp_take(ORD ? "k_mmv_stream_ord" : "k_mmv_stream", (unsigned) (g.blocks_per_member * g.n));
-    hipLaunchKernelGGL((k_mmv_stream<F, NC, PD, IPL, TAIL, ORD, PRO, XF, MR>), dim3((unsigned) (g.blocks_per_member * g.n)), dim3(256), lds,
+    hipLaunchKernelGGL((k_mmv_stream<F, NC, PD, IPL, TAIL, ORD, PRO, XF, MR, IDS>), dim3((unsigned) (g.blocks_per_member * g.n)), dim3(256), lds,
                        s, g);
 }
 
@@ -1955,6 +1963,9 @@ void launch_tail(const mi_mmv_group & g, hipStream_t s) {
     else launch_one<F, NC, PD, IPL, false, ORD, false, XF>(g, s);
 }
 
+// formats that read the canonical blocks (MUL_MAT_ID has no repacked copies: those need 2-D leaves)
+template <class F> constexpr bool kFmtCanonical = !std::is_same<F, FmtQ0R>::value && !std::is_same<F, FmtQ8R>::value;
+
 template <class F, int NC, bool ORD>
 void launch_stream(const mi_mmv_group & g, int variant, hipStream_t s) {
     const int items = (int) (g.K / F::ITEM);
@@ -1966,6 +1977,18 @@ void launch_stream(const mi_mmv_group & g, int variant, hipStream_t s) {
     // them: 5.45 -> 4.95 us per graph without it (profiles/r05xf_xfirst_ab.txt)
     const bool xf = g.n == 1 && g_mi_tuning.xfirst == 1;
     const bool pro_epi = g.pro.mode || e.bias || e.resid || e.gelu_table || e.copy[0].ptr || e.copy[1].ptr;
+    if constexpr (NC == 1 && kFmtCanonical<F>) {
+        // MUL_MAT_ID decode: the plain one-column forms with the device-resolved weight base
+        // (no prologue / epilogue, no repacked copies)
+        if (g.ids_w) {
+            if (items > 128) launch_one<F, 1, 2, 2, true, ORD, false, false, 1, true>(g, s);
+            else if (items > 64) launch_one<F, 1, 2, 2, false, ORD, false, false, 1, true>(g, s);
+            else if (variant / 10 == 1) launch_one<F, 1, 1, 1, false, ORD, false, false, 1, true>(g, s);
+            else if (variant / 10 == 3) launch_one<F, 1, 3, 1, false, ORD, false, false, 1, true>(g, s);
+            else launch_one<F, 1, 2, 1, false, ORD, false, false, 1, true>(g, s);
+            return;
+        }
+    }
 #if MI_DIAG  // measured slower (profiles/r06h_gemv_lds_dma_ab.txt): diagnostic builds only
     if constexpr (NC == 1 && !ORD && std::is_same<F, FmtKQ<false>>::value) {
         if (!pro_epi && g_mi_tuning.mmv_dma > 0 && launch_dma(g, s)) return;

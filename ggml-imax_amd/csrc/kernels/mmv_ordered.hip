@@ -55,7 +55,18 @@ struct ord_geom {
     size_t nb01, nb02, nb03;
     size_t nb1, nb2, nb3;
     int64_t col_chunks;
+    mi_mm_ids id;  // MUL_MAT_ID (kernels instantiated with IDS)
 };
+
+// MUL_MAT_ID, pair by pair: blockIdx.y is the pair (e, t) = (y % n_ids, y / n_ids). Returns the
+// expert's weight offset, or -1 for an id outside [0, n_as) (the workgroup then exits: blockIdx.y
+// alone decides, before any cross-lane operation).
+__device__ __forceinline__ int64_t ord_pair(const ord_geom & g, int64_t & e, int64_t & t) {
+    e = blockIdx.y % g.id.n_ids;
+    t = blockIdx.y / g.id.n_ids;
+    const int expert = *(const int32_t *) ((const char *) g.id.ids + e * g.id.nb0 + t * g.id.nb1);
+    return (unsigned) expert < (unsigned) g.id.n_as ? (int64_t) expert * (int64_t) g.nb02 : -1;
+}
 
 // 8 halves at p: one 16-byte load, or (ALIGNED false: rows of K % 8 != 0 halves, or a weight row
 // stride / base that is not a 16-byte multiple) eight 2-byte loads
@@ -71,22 +82,33 @@ __device__ __forceinline__ void ld_h8(const uint16_t * p, float (&f)[8]) {
 
 // F16 weights x f16 activation columns (xh: [ncols][K], the CPU's from_float rows).
 // One quad per (row, chunk of NC columns).
-template <int NC, bool ALIGNED>
+template <int NC, bool ALIGNED, bool IDS = false>
 __global__ __launch_bounds__(256) void k_mmv_f16_ord(const uint8_t * __restrict__ W, const uint16_t * __restrict__ xh,
                                                      float * __restrict__ dst, ord_geom g) {
     const int q = threadIdx.x & 3;
     const int64_t row = (int64_t) blockIdx.x * kQuadsPerBlock + (threadIdx.x >> 2);
     const bool live = row < g.N;
-    const int64_t y = blockIdx.y;
-    const int64_t chunk = y % g.col_chunks;
-    const int64_t z = y / g.col_chunks;
-    const int64_t i12 = z % g.ne12, i13 = z / g.ne12;
-    const int64_t i11 = chunk * NC;
-    const int64_t i02 = i12 / g.r2, i03 = i13 / g.r3;
-    const uint16_t * wrow = (const uint16_t *) (W + i02 * g.nb02 + i03 * g.nb03 + (live ? row : 0) * g.nb01);
-    const int64_t col0 = i11 + g.ne11 * (i12 + g.ne12 * i13);
-    int nc = (int) (g.ne11 - i11);
-    nc = nc > NC ? NC : nc;
+    int64_t i11, i12, i13, wofs, col0;
+    int nc;
+    if constexpr (IDS) {
+        static_assert(NC == 1, "MUL_MAT_ID: one column per workgroup");
+        wofs = ord_pair(g, i11, i12);  // the destination column (e, t)
+        if (wofs < 0) return;
+        i13 = 0;
+        col0 = i11 % g.ne11 + g.ne11 * i12;
+        nc = 1;
+    } else {
+        const int64_t y = blockIdx.y;
+        const int64_t chunk = y % g.col_chunks;
+        const int64_t z = y / g.col_chunks;
+        i12 = z % g.ne12, i13 = z / g.ne12;
+        i11 = chunk * NC;
+        wofs = (i12 / g.r2) * g.nb02 + (i13 / g.r3) * g.nb03;
+        col0 = i11 + g.ne11 * (i12 + g.ne12 * i13);
+        nc = (int) (g.ne11 - i11);
+        nc = nc > NC ? NC : nc;
+    }
+    const uint16_t * wrow = (const uint16_t *) (W + wofs + (live ? row : 0) * g.nb01);
 
     float acc[NC][8];
 #pragma unroll
@@ -123,18 +145,28 @@ __global__ __launch_bounds__(256) void k_mmv_f16_ord(const uint8_t * __restrict_
 
 // F32 x F32, both operands strided (KQ = K^T Q and KQV = V^T softmax of the attention).
 // One quad per output element.
+template <bool IDS = false>
 __global__ __launch_bounds__(256) void k_mm_f32_ord(const uint8_t * __restrict__ W, mi_src_cols x, float * __restrict__ dst,
                                                     ord_geom g) {
     const int q = threadIdx.x & 3;
     const int64_t row = (int64_t) blockIdx.x * kQuadsPerBlock + (threadIdx.x >> 2);
     const bool live = row < g.N;
-    const int64_t y = blockIdx.y;
-    const int64_t i11 = y % g.ne11;
-    const int64_t z = y / g.ne11;
-    const int64_t i12 = z % g.ne12, i13 = z / g.ne12;
-    const int64_t i02 = i12 / g.r2, i03 = i13 / g.r3;
-    const float * w = (const float *) (W + i02 * g.nb02 + i03 * g.nb03 + (live ? row : 0) * g.nb01);
-    const float * xc = (const float *) (x.base + i11 * x.nb1 + i12 * x.nb2 + i13 * x.nb3);
+    int64_t i11, i12, i13, wofs;
+    const float * xc;
+    if constexpr (IDS) {
+        wofs = ord_pair(g, i11, i12);  // the destination column (e, t)
+        if (wofs < 0) return;
+        i13 = 0;
+        xc = (const float *) (x.base + (i11 % g.ne11) * x.nb1 + i12 * x.nb2);
+    } else {
+        const int64_t y = blockIdx.y;
+        i11 = y % g.ne11;
+        const int64_t z = y / g.ne11;
+        i12 = z % g.ne12, i13 = z / g.ne12;
+        wofs = (i12 / g.r2) * g.nb02 + (i13 / g.r3) * g.nb03;
+        xc = (const float *) (x.base + i11 * x.nb1 + i12 * x.nb2 + i13 * x.nb3);
+    }
+    const float * w = (const float *) (W + wofs + (live ? row : 0) * g.nb01);
 
     float acc[8];
 #pragma unroll
@@ -837,6 +869,7 @@ ord_geom make_ord_geom(const mi_mm_desc & m, int NC) {
     g.nb2 = m.nb2;
     g.nb3 = m.nb3;
     g.col_chunks = (m.ne11 + NC - 1) / NC;
+    g.id = m.id;
     return g;
 }
 
@@ -851,6 +884,14 @@ template <int NC> void launch_f16(const mi_mm_desc & m, const uint16_t * xh, hip
 } // namespace
 
 void mi_mul_mat_f16(const mi_mm_desc & m, const uint16_t * xh, hipStream_t s) {
+    if (m.id.ids) {  // MUL_MAT_ID: pair by pair
+        const ord_geom g = make_ord_geom(m, 1);
+        const dim3 grid((unsigned) ((m.N + kQuadsPerBlock - 1) / kQuadsPerBlock), (unsigned) ((int64_t) m.id.n_ids * m.ne12));
+        const bool aligned = m.K % 8 == 0 && ((uintptr_t) m.W | m.nb01 | m.nb02 | (uintptr_t) xh) % 16 == 0;
+        if (aligned) hipLaunchKernelGGL((k_mmv_f16_ord<1, true, true>), grid, dim3(256), 0, s, (const uint8_t *) m.W, xh, m.dst, g);
+        else hipLaunchKernelGGL((k_mmv_f16_ord<1, false, true>), grid, dim3(256), 0, s, (const uint8_t *) m.W, xh, m.dst, g);
+        return;
+    }
     switch (m.ne11 >= 4 ? 4 : (int) m.ne11) {
         case 1: launch_f16<1>(m, xh, s); break;
         case 2: launch_f16<2>(m, xh, s); break;
@@ -861,8 +902,13 @@ void mi_mul_mat_f16(const mi_mm_desc & m, const uint16_t * xh, hipStream_t s) {
 
 void mi_mul_mat_f32(const mi_mm_desc & m, const mi_src_cols & x, hipStream_t s) {
     const ord_geom g = make_ord_geom(m, 1);
+    if (m.id.ids) {  // MUL_MAT_ID: pair by pair
+        const dim3 grid((unsigned) ((m.N + kQuadsPerBlock - 1) / kQuadsPerBlock), (unsigned) ((int64_t) m.id.n_ids * m.ne12));
+        hipLaunchKernelGGL(k_mm_f32_ord<true>, grid, dim3(256), 0, s, (const uint8_t *) m.W, x, m.dst, g);
+        return;
+    }
     const dim3 grid((unsigned) ((m.N + kQuadsPerBlock - 1) / kQuadsPerBlock), (unsigned) (m.ne11 * m.ne12 * m.ne13));
-    hipLaunchKernelGGL(k_mm_f32_ord, grid, dim3(256), 0, s, (const uint8_t *) m.W, x, m.dst, g);
+    hipLaunchKernelGGL(k_mm_f32_ord<false>, grid, dim3(256), 0, s, (const uint8_t *) m.W, x, m.dst, g);
 }
 
 bool mi_mul_mat_f16_fused_supported(int64_t K, int64_t ncols) { return ncols >= 1 && K >= 8 && K % 8 == 0 && K <= 10240; }

@@ -98,6 +98,7 @@ _SIGS = {
     "ggml_op_desc": ([T], c_char_p),
     "ggml_is_contiguous": ([T], c_bool),
     "ggml_mul_mat": ([c_void_p, T, T], T),
+    "ggml_mul_mat_id": ([c_void_p, T, T, T], T),
     "ggml_add": ([c_void_p, T, T], T),
     "ggml_mul": ([c_void_p, T, T], T),
     "ggml_scale": ([c_void_p, T, c_float], T),
