@@ -567,6 +567,12 @@ static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
             return is_f16_or_f32(a) && is_f16_or_f32(b) && is_f16_or_f32(op);
         case GGML_OP_SCALE:
             return is_f32(a) && is_f32(op);
+        case GGML_OP_SUM_ROWS:
+            return is_f32(a) && is_f32(op) && a->nb[0] == sizeof(float) && op->nb[0] == sizeof(float);
+        case GGML_OP_ARGSORT:
+            // f32 rows that one workgroup holds a position per thread (router.hip)
+            return is_f32(a) && op->type == GGML_TYPE_I32 && a->nb[0] == sizeof(float) && op->nb[0] == sizeof(int32_t) &&
+                   a->ne[0] <= kMiArgsortMaxRow;
         case GGML_OP_NORM:
         case GGML_OP_RMS_NORM:
             // rows longer than the kernel's LDS staging (12288 floats) stage in a contiguous dst
@@ -1369,6 +1375,10 @@ static void op_companion(mi_backend_ctx * ctx, ggml_tensor * node) {
             break;
         }
         case GGML_OP_GET_ROWS: mi_op_get_rows(desc(node), desc(a), desc(b), st); break;
+        case GGML_OP_SUM_ROWS: mi_op_sum_rows(desc(node), desc(a), st); break;
+        case GGML_OP_ARGSORT:
+            mi_op_argsort(desc(node), desc(a), ((const int32_t *) node->op_params)[0] == (int32_t) GGML_SORT_ORDER_DESC, st);
+            break;
         case GGML_OP_CPY:
         case GGML_OP_DUP:
         case GGML_OP_CONT:
@@ -2287,6 +2297,111 @@ static int try_fuse_embedding(mi_backend_ctx * ctx, ggml_cgraph * g, int i, cons
     return k;
 }
 
+// The router of a mixture-of-experts layer as one launch (router.hip k_router), entered at its SOFT_MAX:
+//   probs = soft_max(logits)                    no mask, scale 1, max_bias 0, at most 64 experts
+//   order = argsort(probs, DESC); sel = view(order, first k of each row)
+//   w     = get_rows(reshape_3d(probs, 1, n_expert, T), sel)
+//   [ w2 = reshape_2d(w, k, T); s = sum_rows(w2); wn = div(w2, s) ]
+// The chain's nodes need not be adjacent (the expert mul_mats that read `sel` usually sit between the
+// top-k and the weights), so the later ones are found through their sources within a window and
+// marked absorbed. They are then written earlier than their place in the graph: none of them may
+// overlap anything that a node in between reads or writes (an allocator may have given a later
+// tensor the memory of an earlier one that is still live). Every tensor is written in full, as its
+// own node writes it -- except the argsort rows past k when the top-k view is the argsort's only
+// reader. MUL_MAT_ID is neither absorbed nor a producer here.
+static constexpr int kRouterWindow = 64;
+
+static int try_fuse_router(mi_backend_ctx * ctx, ggml_cgraph * g, int i, const mi_uses & u, std::vector<uint8_t> & absorbed_nodes) {
+    if (!g_mi_tuning.fuse_router) return -1;
+    ggml_tensor * sm = g->nodes[i];
+    const ggml_tensor * logits = sm->src[0];
+    if (sm->src[1] || op_param_f(sm, 0) != 1.0f || op_param_f(sm, 1) != 0.0f) return -1;
+    const int64_t n_expert = sm->ne[0], T = sm->ne[1];
+    if (n_expert > kMiRouterMaxExperts || sm->ne[2] != 1 || sm->ne[3] != 1) return -1;
+    if (!is_f32(sm) || !is_f32(logits) || !ggml_is_contiguous(sm) || !ggml_is_contiguous(logits) || !safe_alias(sm, logits)) return -1;
+    const int end = std::min(g->n_nodes, i + kRouterWindow);
+    int i_as = -1, i_v = -1, i_r3 = -1, i_gr = -1, i_r2 = -1, i_sr = -1, i_dv = -1;
+    for (int j = i + 1; j < end; j++) {
+        const ggml_tensor * n = g->nodes[j];
+        if (absorbed(j)) continue;
+        if (i_as < 0 && n->op == GGML_OP_ARGSORT && n->src[0] == sm) i_as = j;
+        else if (i_v < 0 && i_as >= 0 && n->op == GGML_OP_VIEW && n->src[0] == g->nodes[i_as]) i_v = j;
+        else if (i_r3 < 0 && n->op == GGML_OP_RESHAPE && n->src[0] == sm && n->ne[0] == 1 && n->ne[1] == n_expert) i_r3 = j;
+        else if (i_gr < 0 && i_v >= 0 && i_r3 >= 0 && n->op == GGML_OP_GET_ROWS && n->src[0] == g->nodes[i_r3] && n->src[1] == g->nodes[i_v]) i_gr = j;
+        else if (i_r2 < 0 && i_gr >= 0 && n->op == GGML_OP_RESHAPE && n->src[0] == g->nodes[i_gr]) i_r2 = j;
+        else if (i_sr < 0 && i_r2 >= 0 && n->op == GGML_OP_SUM_ROWS && n->src[0] == g->nodes[i_r2]) i_sr = j;
+        else if (i_dv < 0 && i_sr >= 0 && n->op == GGML_OP_DIV && n->src[0] == g->nodes[i_r2] && n->src[1] == g->nodes[i_sr]) i_dv = j;
+    }
+    if (i_gr < 0) return -1;
+    ggml_tensor * as = g->nodes[i_as];
+    const ggml_tensor * v = g->nodes[i_v];
+    const ggml_tensor * r3 = g->nodes[i_r3];
+    ggml_tensor * gr = g->nodes[i_gr];
+    const int64_t k = v->ne[0];
+    if (((const int32_t *) as->op_params)[0] != (int32_t) GGML_SORT_ORDER_DESC || as->type != GGML_TYPE_I32 || !ggml_is_contiguous(as)) return -1;
+    if (v->view_src != as || v->view_offs != 0 || v->type != GGML_TYPE_I32 || k < 1 || k > n_expert || v->ne[1] != T || v->ne[2] != 1 ||
+        v->ne[3] != 1 || v->nb[0] != sizeof(int32_t) || v->nb[1] != as->nb[1]) return -1;
+    if (r3->ne[2] != T || r3->ne[3] != 1 || r3->view_src != sm || r3->view_offs != 0) return -1;
+    if (!is_f32(gr) || !ggml_is_contiguous(gr) || gr->ne[0] != 1 || gr->ne[1] != k || gr->ne[2] != T || gr->ne[3] != 1) return -1;
+    const bool tail = i_dv >= 0;
+    ggml_tensor * sr = tail ? g->nodes[i_sr] : nullptr;
+    ggml_tensor * dv = tail ? g->nodes[i_dv] : nullptr;
+    if (tail) {
+        const ggml_tensor * r2 = g->nodes[i_r2];
+        if (r2->ne[0] != k || r2->ne[1] != T || r2->ne[2] != 1 || r2->ne[3] != 1 || r2->view_src != gr || r2->view_offs != 0) return -1;
+        if (!is_f32(sr) || !is_f32(dv) || !ggml_is_contiguous(sr) || !ggml_is_contiguous(dv) || !ggml_are_same_shape(dv, r2)) return -1;
+    }
+    // the written tensors: disjoint from each other and from the logits (soft_max in place excepted)
+    const ggml_tensor * outs[5] = {sm, as, gr, sr, dv};
+    const int at[5] = {i, i_as, i_gr, tail ? i_sr : -1, tail ? i_dv : -1};
+    const int n_out = tail ? 5 : 3;
+    for (int a = 0; a < n_out; a++) {
+        if (a > 0 && overlaps(outs[a], logits)) return -1;
+        for (int b = a + 1; b < n_out; b++) {
+            if (overlaps(outs[a], outs[b])) return -1;
+        }
+    }
+    // written ahead of their place: nothing a node in between touches may lie under them
+    auto in_chain = [&](const ggml_tensor * t) {
+        const ggml_tensor * root = t->view_src ? t->view_src : t;
+        for (int a = 0; a < n_out; a++) {
+            if (root == outs[a]) return true;
+        }
+        return false;
+    };
+    for (int a = 1; a < n_out; a++) {
+        for (int j = i + 1; j < at[a]; j++) {
+            const ggml_tensor * n = g->nodes[j];
+            if (is_noop(n) || in_chain(n)) continue;
+            if (overlaps(outs[a], n)) return -1;
+            for (int s = 0; s < GGML_MAX_SRC; s++) {
+                if (n->src[s] && n->src[s]->data && !in_chain(n->src[s]) && overlaps(outs[a], n->src[s])) return -1;
+            }
+        }
+    }
+    mi_router_desc r;
+    r.logits = (const float *) logits->data;
+    r.probs = (float *) sm->data;
+    r.sorted = (int32_t *) as->data;
+    r.weights = (float *) gr->data;
+    r.sums = tail ? (float *) sr->data : nullptr;
+    r.normed = tail ? (float *) dv->data : nullptr;
+    r.n_expert = (int) n_expert;
+    r.k = (int) k;
+    // the rows' tails stay unwritten only where the top-k view is provably the argsort's one reader
+    // (its two uses: the view's source and its view_src)
+    r.n_sorted = u.of(as) == 2 && !(as->flags & GGML_TENSOR_FLAG_OUTPUT) ? (int) k : (int) n_expert;
+    r.T = T;
+    mi_router_fused(r, op_tables(ctx), ctx->stream);
+    ctx->last_launches++;
+    if (absorbed_nodes.size() < (size_t) g->n_nodes) absorbed_nodes.resize((size_t) g->n_nodes, 0);
+    for (int a = 1; a < n_out; a++) {
+        absorbed_nodes[at[a]] = 1;
+        invalidate_activations(ctx, outs[a]);
+    }
+    return i;
+}
+
 // consecutive independent copies (GPT-2: K -> cache, V -> cache, cont(Q)) as one launch
 static int try_fuse_copies(mi_backend_ctx * ctx, ggml_cgraph * g, int i) {
     std::vector<ggml_tensor *> grp = {g->nodes[i]};
@@ -2718,8 +2833,9 @@ static enum ggml_status mi_graph_plan_compute(ggml_backend_t backend, ggml_backe
 // in the graph re-quantizes it (quantize_row_q8_*: round(x / d)), so a 1-ulp difference upstream can
 // move a quant by a whole step and the logits of a quantized model by ~1e-2
 // (tests/test_gpt2.py::test_reference_quantized_gpt2_is_ulp_sensitive): such graphs run every decode
-// reduction in the reference CPU's order (bit-identical). Any other graph (F16 models, a mul_mat of
-// input data) keeps the tree order, within 1e-5 of the reference per op.
+// reduction in the reference CPU's order (bit-identical), and so do graphs whose ARGSORT orders a
+// computed value (below). Any other graph (F16 models, a mul_mat of input data) keeps the tree order,
+// within 1e-5 of the reference per op.
 // A split input of the reference scheduler is a NONE tensor holding a value another split computed
 // (ggml_backend_sched_split_graph creates it with ggml_dup_tensor_layout, ggml-backend.c:1498-1523).
 // It cannot be told from a true graph input by its own fields (flags are set only when n_copies > 1,
@@ -2733,8 +2849,12 @@ static int graph_decode_order(const ggml_cgraph * g) {
     const bool view = sched_split_view(g);
     for (int i = 0; i < g->n_nodes; i++) {
         const ggml_tensor * n = g->nodes[i];
-        if ((n->op != GGML_OP_MUL_MAT && n->op != GGML_OP_MUL_MAT_ID) || !ggml_is_quantized(n->src[0]->type)) continue;
-        const ggml_tensor * x = n->src[1];
+        // An ARGSORT (a router's top-k) is the same kind of discrete decision: a 1-ulp difference in a
+        // value it orders can exchange two experts, and every weight multiplied after it. So a graph
+        // whose ARGSORT consumes a value the graph computes runs in the reference order as well.
+        const bool requant = (n->op == GGML_OP_MUL_MAT || n->op == GGML_OP_MUL_MAT_ID) && ggml_is_quantized(n->src[0]->type);
+        if (!requant && n->op != GGML_OP_ARGSORT) continue;
+        const ggml_tensor * x = requant ? n->src[1] : n->src[0];
         while (x->view_src || x->op == GGML_OP_RESHAPE || x->op == GGML_OP_VIEW || x->op == GGML_OP_PERMUTE ||
                x->op == GGML_OP_TRANSPOSE) {
             x = x->view_src ? x->view_src : x->src[0];
@@ -2758,8 +2878,8 @@ static enum ggml_status mi_graph_launch_nodes(mi_backend_ctx * ctx, ggml_cgraph 
     static const bool no_fuse = getenv("GGML_MI355X_NO_FUSED_MMV") != nullptr;
     static const bool no_node_fusion = getenv("GGML_MI355X_NO_NODE_FUSION") != nullptr;
     // bit mask of enabled node fusions (debug/A-B): 1 norm, 2 softmax, 4 f16 GEMV, 8 copies, 16 attention,
-    // 64 embedding, 128 attention + output projection
-    static const int fuse_mask = getenv("GGML_MI355X_FUSE_MASK") ? atoi(getenv("GGML_MI355X_FUSE_MASK")) : 0xff;
+    // 64 embedding, 128 attention + output projection, 256 mixture-of-experts router chain (also set_tuning fuse_router)
+    static const int fuse_mask = getenv("GGML_MI355X_FUSE_MASK") ? atoi(getenv("GGML_MI355X_FUSE_MASK")) : 0x1ff;
     ctx->pend = {};
     mi_uses uses;
     std::vector<uint8_t> absorbed_nodes;
@@ -2840,6 +2960,7 @@ static enum ggml_status mi_graph_launch_nodes(mi_backend_ctx * ctx, ggml_cgraph 
                 case GGML_OP_DUP:
                 case GGML_OP_CONT: last = (fuse_mask & 8) ? try_fuse_copies(ctx, cgraph, i) : -1; break;
                 case GGML_OP_GET_ROWS: last = (fuse_mask & 64) ? try_fuse_embedding(ctx, cgraph, i, uses) : -1; break;
+                case GGML_OP_SOFT_MAX: last = (fuse_mask & 256) ? try_fuse_router(ctx, cgraph, i, uses, absorbed_nodes) : -1; break;
                 default: break;
             }
         }
@@ -3256,6 +3377,10 @@ bool ggml_backend_mi355x_set_tuning(const char * name, int value) {
     }
     if (strcmp(name, "mmid_stream") == 0 && value >= 0 && value <= 8) {
         g_mi_tuning.mmid_stream = value;
+        return true;
+    }
+    if (strcmp(name, "fuse_router") == 0 && value >= 0 && value <= 1) {
+        g_mi_tuning.fuse_router = value;
         return true;
     }
     if (strcmp(name, "mmqt_short") == 0 && value >= 0) {

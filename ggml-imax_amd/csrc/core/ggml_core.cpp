@@ -552,6 +552,39 @@ struct ggml_tensor * ggml_add_inplace(struct ggml_context * ctx, struct ggml_ten
 struct ggml_tensor * ggml_mul(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b) { return binary_bcast(ctx, a, b, GGML_OP_MUL, false); }
 struct ggml_tensor * ggml_mul_inplace(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b) { return binary_bcast(ctx, a, b, GGML_OP_MUL, true); }
 
+// src/ggml.c:4186 ggml_div (b broadcast over a) / :4098 ggml_sub (same shapes only)
+struct ggml_tensor * ggml_div(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b) { return binary_bcast(ctx, a, b, GGML_OP_DIV, false); }
+struct ggml_tensor * ggml_sub(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b) {
+    GGML_ASSERT(ggml_are_same_shape(a, b));
+    return binary_bcast(ctx, a, b, GGML_OP_SUB, false);
+}
+
+// src/ggml.c:4321 ggml_sum_rows: dst [1, a->ne1, a->ne2, a->ne3] of a's type
+struct ggml_tensor * ggml_sum_rows(struct ggml_context * ctx, struct ggml_tensor * a) {
+    const int64_t ne[4] = {1, a->ne[1], a->ne[2], a->ne[3]};
+    ggml_tensor * r = ggml_new_tensor(ctx, a->type, 4, ne);
+    r->op = GGML_OP_SUM_ROWS;
+    r->src[0] = a;
+    return r;
+}
+
+// src/ggml.c:6425 ggml_argsort: dst i32 of a's shape, op_params[0] = order
+struct ggml_tensor * ggml_argsort(struct ggml_context * ctx, struct ggml_tensor * a, enum ggml_sort_order order) {
+    ggml_tensor * r = ggml_new_tensor(ctx, GGML_TYPE_I32, GGML_MAX_DIMS, a->ne);
+    const int32_t p = (int32_t) order;
+    set_op_params(r, &p, sizeof(p));
+    r->op = GGML_OP_ARGSORT;
+    r->src[0] = a;
+    return r;
+}
+
+// src/ggml.c:6444 ggml_top_k: the first k entries of every row of the descending argsort, as a view
+struct ggml_tensor * ggml_top_k(struct ggml_context * ctx, struct ggml_tensor * a, int k) {
+    GGML_ASSERT(a->ne[0] >= k);
+    ggml_tensor * r = ggml_argsort(ctx, a, GGML_SORT_ORDER_DESC);
+    return ggml_view_4d(ctx, r, k, r->ne[1], r->ne[2], r->ne[3], r->nb[1], r->nb[2], r->nb[3], 0);
+}
+
 // src/ggml.c:5092 ggml_scale_impl: op_params[0] = s
 static ggml_tensor * scale_impl(ggml_context * ctx, ggml_tensor * a, float s, bool inplace) {
     ggml_tensor * r = unary_like(ctx, a, GGML_OP_SCALE, inplace);

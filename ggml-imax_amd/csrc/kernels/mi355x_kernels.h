@@ -183,6 +183,7 @@ struct mi_tuning {
                       // over the pairs grouped by expert on the device (mi_mmid_group; up to 4 gathered columns per workgroup), 0 = pair by pair;
                       // 4 / 8: grouped from 2 tokens on in either order with chunks of that many pairs (A/B timing)
     int mmid_stream;  // MUL_MAT_ID of quantized experts: up to this many tokens run on the streaming decode kernel, a member per pair (0: never)
+    int fuse_router;  // a mixture-of-experts router chain (soft_max, argsort DESC, top-k view, get_rows, sum_rows, div; at most 64 experts) as one launch: 1 on (default), 0 off
 };
 extern mi_tuning g_mi_tuning;
 // the order of the graph being launched when mmv_order is -1 (set by the backend per graph)
@@ -327,6 +328,28 @@ void mi_op_rope(const mi_tensor_desc & d, const mi_tensor_desc & a, const int32_
 // soft_max (max_bias 0); n_past >= 0 fuses the preceding scale(pre_scale) + diag_mask_inf(n_past)
 void mi_op_soft_max(const mi_tensor_desc & d, const mi_tensor_desc & a, const mi_tensor_desc & mask, float scale,
                     const uint16_t * exp_table, float pre_scale, int n_past, hipStream_t s);
+
+// ---- mixture-of-experts router ops (router.hip) ----
+// sum_rows f32 (src/ggml.c:10159-10192): d[0, i1, i2, i3] = the row's sequential double sum, rounded once
+void mi_op_sum_rows(const mi_tensor_desc & d, const mi_tensor_desc & a, hipStream_t s);
+// argsort f32 -> i32 (src/ggml.c:15064-15105), ne0 <= kMiArgsortMaxRow: the permutation the reference's
+// exchange sort leaves, ties included. Row r of src / dst at r * nb[1], as the reference addresses them.
+constexpr int kMiArgsortMaxRow = 1024;
+void mi_op_argsort(const mi_tensor_desc & d, const mi_tensor_desc & a, bool descending, hipStream_t s);
+// soft_max -> argsort DESC -> first k -> get_rows of the probabilities -> (sum_rows -> div) of one
+// router, one wave per token, every tensor as its own node would write it. All contiguous.
+constexpr int kMiRouterMaxExperts = 64;
+struct mi_router_desc {
+    const float * logits;  // [n_expert, T]
+    float * probs;         // [n_expert, T]
+    int32_t * sorted;      // [n_expert, T] argsort rows: the first n_sorted entries of each are written
+    float * weights;       // [k, T] probs[sorted[j, t], t]
+    float * sums;          // [T], or null: no normalisation tail
+    float * normed;        // [k, T] weights / sums
+    int n_expert, k, n_sorted;  // n_sorted = k, or n_expert where the argsort has other readers
+    int64_t T;
+};
+void mi_router_fused(const mi_router_desc & r, const uint16_t * exp_table, hipStream_t s);
 
 // Decode-regime F16 mul_mat (2-D weights, few f32 src1 columns of contiguous K) that converts the
 // activations itself and applies the graph's following bias add / residual add / GELU.

@@ -101,6 +101,11 @@ _SIGS = {
     "ggml_mul_mat_id": ([c_void_p, T, T, T], T),
     "ggml_add": ([c_void_p, T, T], T),
     "ggml_mul": ([c_void_p, T, T], T),
+    "ggml_sub": ([c_void_p, T, T], T),
+    "ggml_div": ([c_void_p, T, T], T),
+    "ggml_sum_rows": ([c_void_p, T], T),
+    "ggml_argsort": ([c_void_p, T, c_int], T),
+    "ggml_top_k": ([c_void_p, T, c_int], T),
     "ggml_scale": ([c_void_p, T, c_float], T),
     "ggml_norm": ([c_void_p, T, c_float], T),
     "ggml_rms_norm": ([c_void_p, T, c_float], T),
@@ -120,6 +125,8 @@ _SIGS = {
     "ggml_cont_2d": ([c_void_p, T, c_int64, c_int64], T),
     "ggml_cont_3d": ([c_void_p, T, c_int64, c_int64, c_int64], T),
     "ggml_view_3d": ([c_void_p, T, c_int64, c_int64, c_int64, c_size_t, c_size_t, c_size_t], T),
+    "ggml_view_4d": ([c_void_p, T, c_int64, c_int64, c_int64, c_int64, c_size_t, c_size_t, c_size_t, c_size_t], T),
+    "ggml_reshape_2d": ([c_void_p, T, c_int64, c_int64], T),
     "ggml_reshape_3d": ([c_void_p, T, c_int64, c_int64, c_int64], T),
     "ggml_new_graph": ([c_void_p], POINTER(ggml_cgraph)),
     "ggml_new_graph_custom": ([c_void_p, c_size_t, c_bool], POINTER(ggml_cgraph)),
