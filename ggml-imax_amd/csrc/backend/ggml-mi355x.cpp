@@ -765,9 +765,9 @@ static int mm_act_kind(const mi_mm_desc & m, const ggml_tensor * src1) {
         return mm_batched(m, src1) && mi_mmqx_supported(m.type, m.K, m.nb1, ncols, m.nb01) ? (kind == 1 ? 8 : 9) : kind;
     }
     if (!mm_batched(m, src1)) return kind;
-    // GGML_MI355X_MMQ_VARIANT bit 2^30 selects the f16 GEMM for the quantized types too (A/B
+    // mmq_variant bit kMmqF16Gemm selects the f16 GEMM for the quantized types too (A/B
     // timing; the low bits are mmq_exact.hip's own kernel variants)
-    if (kind <= 1 && (g_mi_tuning.mmq_variant & (1 << 30)) == 0 && mi_mmqx_supported(m.type, m.K, m.nb1, ncols, m.nb01)) return kind == 1 ? 8 : 9;
+    if (kind <= 1 && (g_mi_tuning.mmq_variant & kMmqF16Gemm) == 0 && mi_mmqx_supported(m.type, m.K, m.nb1, ncols, m.nb01)) return kind == 1 ? 8 : 9;
     return (kind == 2 ? 2 : kind + 3) + (mi_mmq_wants_blocked() ? 3 : 0);
 }
 
@@ -846,14 +846,6 @@ static void mul_mat_run(mi_backend_ctx * ctx, const ggml_tensor * src0, const vo
     m.nb3 = nb3;
 
     const int xkind = mm_act_kind(m, src1);
-    if (xkind == 5 && m.type == GGML_TYPE_F16 && src1->type == GGML_TYPE_F32 && src1->ne[2] == 1 && src1->ne[3] == 1 &&
-        mi_mmf16p_f32_supported(m.K, m.N, m.nb01, src1->ne[1], m.nb1, src1->data, src1->nb[1])) {
-        // F16 weights, a short prompt of plain f32 columns: one launch, activations rounded to f16
-        // inside the GEMM (k_mmf16p<F32X>)
-        mi_mul_mat_f16p_f32(m.W, m.nb01, m.K, m.N, (const float *) src1->data, src1->nb[1], src1->ne[1], m.dst, m.nb1, ctx->stream);
-        ctx->last_launches++;
-        return;
-    }
     if (xkind < 0) {
         MI_ASSERT(src0->type == GGML_TYPE_F32);
         mi_mul_mat_f32(m, src_cols(src1), ctx->stream);
@@ -2122,20 +2114,14 @@ static int try_fuse_attn_proj(mi_backend_ctx * ctx, ggml_cgraph * g, int i, cons
 // chains, bit-identical; ggml.c:12056-12096 runs every column through the same vec_dot) over
 // 8-column chunks, up to kMiMaxMembers chunks per launch: each chunk is a member of one grouped
 // launch over the same weight rows, so a 512-column prompt is one launch whose chunks re-read the
-// weights from the caches rather than 64 dependent launches. GGML_MI355X_ORD_PREFILL_COLS /
-// set_tuning("ord_prefill_cols", n) caps the column count (longer prompts take the MFMA GEMMs);
-// 0 turns it off.
-static int g_ord_prefill_cols = getenv("GGML_MI355X_ORD_PREFILL_COLS") ? atoi(getenv("GGML_MI355X_ORD_PREFILL_COLS")) : INT_MAX;
-
-// (tree order: prompts of up to g_tree_prefill_cols columns take the same 8-column GEMV chunks;
-// set_tuning("tree_prefill_cols", n), 0 = off)
-static int g_tree_prefill_cols = getenv("GGML_MI355X_TREE_PREFILL_COLS") ? atoi(getenv("GGML_MI355X_TREE_PREFILL_COLS")) : 0;
-
+// weights from the caches rather than 64 dependent launches. The knob ord_prefill_cols caps the
+// column count (longer prompts take the MFMA GEMMs), 0 turns it off; in tree order prompts of up to
+// tree_prefill_cols columns take the same 8-column GEMV chunks.
 static bool ord_prefill_chunked(const ggml_tensor * n) {
     if (n->op != GGML_OP_MUL_MAT || is_split_tensor(n->src[0])) return false;
     const ggml_tensor * a = n->src[0];
     const ggml_tensor * b = n->src[1];
-    if (b->type != GGML_TYPE_F32 || b->ne[1] <= 8 || b->ne[1] > (mi_mmv_order() == 1 ? g_ord_prefill_cols : g_tree_prefill_cols)) return false;
+    if (b->type != GGML_TYPE_F32 || b->ne[1] <= 8 || b->ne[1] > (mi_mmv_order() == 1 ? g_mi_tuning.ord_prefill_cols : g_mi_tuning.tree_prefill_cols)) return false;
     if (a->type != GGML_TYPE_Q4_K && a->type != GGML_TYPE_Q5_K && a->type != GGML_TYPE_Q6_K && a->type != GGML_TYPE_Q4_0 &&
         a->type != GGML_TYPE_Q8_0 && !is_legacy_q1(a->type))
         return false;
@@ -2553,7 +2539,6 @@ static void graph_key(const mi_backend_ctx * ctx, const ggml_cgraph * g, std::ve
     // planes entry created or dropped since (a weight buffer freed and another allocated at the same
     // address) must not replay a graph that reads freed planes
     k.push_back(mi_planes_generation());
-    k.push_back((uint64_t) (uint32_t) g_ord_prefill_cols | ((uint64_t) (uint32_t) g_tree_prefill_cols << 32));  // (chunked prompt GEMVs)
     {
         uint64_t tw[(sizeof(mi_tuning) + 7) / 8] = {};
         memcpy(tw, &g_mi_tuning, sizeof(mi_tuning));
@@ -3288,133 +3273,7 @@ int ggml_backend_mi355x_graph_stats_ex(ggml_backend_t backend, int64_t * stats, 
     return m;
 }
 
-bool ggml_backend_mi355x_set_tuning(const char * name, int value) {
-    if (strcmp(name, "mmv_dma") == 0 && (value == 0 || (mi_diag_build() && ((value >= 1 && value <= 3) || (value >= 11 && value <= 13))))) {
-        // (diagnostic builds only: measured slower than k_mmv_stream, profiles/r06h_gemv_lds_dma_ab.txt)
-        g_mi_tuning.mmv_dma = value;
-        return true;
-    }
-    if (strcmp(name, "f16_bp") == 0 && (value == 0 || (value == 1 && mi_diag_build()))) {  // (1: measured slower, diagnostic builds)
-        g_mi_tuning.f16_bp = value;
-        return true;
-    }
-    if (strcmp(name, "f16_bn") == 0 && value >= 0 && value % 10 <= 5 && value <= 15) {
-        g_mi_tuning.f16_bn = value;
-        return true;
-    }
-    if (strcmp(name, "mmv_blocks") == 0 && value >= 0) {
-        g_mi_tuning.mmv_blocks = value;
-        return true;
-    }
-    if (strcmp(name, "mmv_variant") == 0) {
-        g_mi_tuning.mmv_variant = value;
-        return true;
-    }
-    if (strcmp(name, "f16_variant") == 0) {
-        g_mi_tuning.f16_variant = value;
-        return true;
-    }
-    if (strcmp(name, "mmq_variant") == 0) {
-        // the opt-in forms measured slower than the defaults (k_mmqp weight ring 4 2^19, k_mmqp
-        // 64-column tiles 2^26; the k_mmf16p f32 fold behind 2^17) are compiled into diagnostic builds only
-        if (!mi_diag_build() && (value & kMiMmqDiagBits)) return false;
-        g_mi_tuning.mmq_variant = value;
-        return true;
-    }
-    if (strcmp(name, "mmq_long") == 0 && (value == 0 || value == 2 || (mi_diag_build() && (value == 1 || value == 3 || value == 4 || value == 5 || (value >= 16 && value <= 24))))) {
-        // 0 auto, 2 k_mmqt; diagnostic builds: 5 k_mmqt with the high half staggered, 3 k_mmqt with per-half stage synchronization, 4 k_mmqv: 1 k_mmqw for Q4_K, 16-23 k_mmqt stamps / ablations,
-        // 24 k_mmqr per-step stamps
-        g_mi_tuning.mmq_long = value;
-        return true;
-    }
-    if (strcmp(name, "mmv_order") == 0 && value >= -1 && value <= 1) {
-        g_mi_tuning.mmv_order = value;
-        return true;
-    }
-    if (strcmp(name, "ord_prefill_cols") == 0 && value >= 0) {
-        g_ord_prefill_cols = value;
-        return true;
-    }
-    if (strcmp(name, "tree_prefill_cols") == 0 && value >= 0) {
-        g_tree_prefill_cols = value;
-        return true;
-    }
-    if (strcmp(name, "xfirst") == 0 && value >= -1 && value <= 1) {
-        g_mi_tuning.xfirst = value;
-        return true;
-    }
-    if (strcmp(name, "f16_nc") == 0 && value >= 0 && value <= 88 && value % 10 <= 8) {
-        g_mi_tuning.f16_nc = value;
-        return true;
-    }
-    if (strcmp(name, "planes") == 0 && value >= 0 && value <= 1) {
-        g_mi_tuning.planes = value;
-        return true;
-    }
-    if (strcmp(name, "q40r") == 0 && value >= 0 && value <= 1) {
-        g_mi_tuning.q40r = value;
-        return true;
-    }
-    if (strcmp(name, "q80r") == 0 && value >= 0 && value <= 1) {
-        g_mi_tuning.q80r = value;
-        return true;
-    }
-    if (strcmp(name, "f16_m8") == 0 && (value == 0 || (value == 1 && mi_diag_build()))) {  // (1: measured slower, diagnostic builds)
-        g_mi_tuning.f16_m8 = value;
-        return true;
-    }
-    if (strcmp(name, "f16_mt") == 0 && value >= 0 && value <= 1) {
-        g_mi_tuning.f16_mt = value;
-        return true;
-    }
-    if (strcmp(name, "mmv_pro4") == 0 && value >= 0 && value <= 1) {
-        g_mi_tuning.mmv_pro4 = value;
-        return true;
-    }
-    if (strcmp(name, "mmid_group") == 0 && (value == 0 || value == 1 || value == 4 || value == 8)) {
-        g_mi_tuning.mmid_group = value;
-        return true;
-    }
-    if (strcmp(name, "mmid_stream") == 0 && value >= 0 && value <= 8) {
-        g_mi_tuning.mmid_stream = value;
-        return true;
-    }
-    if (strcmp(name, "fuse_router") == 0 && value >= 0 && value <= 1) {
-        g_mi_tuning.fuse_router = value;
-        return true;
-    }
-    if (strcmp(name, "mmqt_short") == 0 && value >= 0) {
-        g_mi_tuning.mmqt_short = value;
-        return true;
-    }
-    if (strcmp(name, "f16_waves") == 0 && value >= 0) {
-        g_mi_tuning.f16_waves = value;
-        return true;
-    }
-    if (strcmp(name, "f16_norm_waves") == 0 && value >= 0 && value <= 8) {
-        g_mi_tuning.f16_norm_waves = value;
-        return true;
-    }
-    if (strcmp(name, "f16_ps_waves") == 0 && (value == 0 || value == 2 || value == 4 || value == 8)) {
-        g_mi_tuning.f16_ps_waves = value;
-        return true;
-    }
-    if (strcmp(name, "f16_rgs") == 0 && value >= 0 && value <= 8) {
-        g_mi_tuning.f16_rgs = value;
-        return true;
-    }
-    if (strcmp(name, "f16_threads") == 0 && (value == 0 || value == 64 || value == 128 || value == 256)) {
-        g_mi_tuning.f16_threads = value;
-        return true;
-    }
-    return false;
-}
-
-bool ggml_backend_mi355x_stamps_enable(size_t slots) { return mi_stamps_enable(slots); }
-void ggml_backend_mi355x_stamps_reset(void) { mi_stamps_reset(); }
-size_t ggml_backend_mi355x_stamps_read(uint64_t * words, size_t n, char * log, size_t log_size) {
-    return mi_stamps_read(words, n, log, log_size);
-}
+bool ggml_backend_mi355x_set_tuning(const char * name, int value) { return mi_tuning_set(name, value); }
 
 size_t ggml_backend_mi355x_planes_stats(size_t * bytes) {
     if (bytes) *bytes = mi_planes_bytes();

@@ -37,9 +37,7 @@ __device__ __forceinline__ float group_sum(float v) {  // sum over each aligned 
 // KPG: keys per lane group held in registers per pass. sm: LDS of n_kv + 8 (D + 8) floats.
 // Returns, in threads d < D, element d of the head's output (num / den); other threads return 0.
 template <int D, int KPG>
-// st (diagnostic builds): phase stamps of the calling workgroup -- slot 2 the first chunk scored
-// (q and the first K rows landed), 3 the max known (first barrier), 4 the p.v sums done
-__device__ __forceinline__ float attn_head(const mi_attn_desc & a, int h, int t, float * sm, float * shm, uint64_t * st = nullptr) {
+__device__ __forceinline__ float attn_head(const mi_attn_desc & a, int h, int t, float * sm, float * shm) {
     constexpr int LPK = D / 8;          // lanes per key
     constexpr int GPW = 64 / LPK;       // key groups per wave
     constexpr int G = 8 * GPW;          // key groups per workgroup
@@ -104,12 +102,10 @@ __device__ __forceinline__ float attn_head(const mi_attn_desc & a, int h, int t,
                 if (j == 0) s[key] = w;
             }
         }
-        if (c0 == 0) MI_STAMP(st, 2);
     }
     mx = mi_wave_max(mx);
     if (lane == 0) shm[wave] = mx;
     __syncthreads();  // s[] and shm[] complete
-    MI_STAMP(st, 3);
     mx = shm[0];
 #pragma unroll
     for (int w = 1; w < 8; w++) mx = fmaxf(mx, shm[w]);
@@ -137,7 +133,6 @@ __device__ __forceinline__ float attn_head(const mi_attn_desc & a, int h, int t,
 #pragma unroll
         for (int e = 0; e < 8; e++) o[e] += __shfl_xor(o[e], off, 64);
     }
-    MI_STAMP(st, 4);
     l = group_sum<LPK>(l);  // only lane j == 0 of each group accumulated l
     float * red = sm + n_kv;  // [8 waves][D + 8]: o slices, then l at [D]
     if (lane < LPK) {
@@ -185,8 +180,6 @@ __global__ __launch_bounds__(512) void k_attn_proj(mi_attn_desc a, mi_attn_proj_
     constexpr int RPW = 512 / LPR;       // rows per workgroup
     extern __shared__ __attribute__((aligned(16))) float sm[];  // s[n_kv] | red[8][D + 8] | (16 B aligned) oh[D] f16
     __shared__ float shm[8];
-    MI_STAMP(p.stamps, 0);
-    MI_STAMP_CLK(p.stamps, 6);
     const int rb = blockIdx.x, h = blockIdx.y;
     const int c = threadIdx.x % LPR;
     const int64_t row = (int64_t) rb * RPW + threadIdx.x / LPR;
@@ -197,9 +190,8 @@ __global__ __launch_bounds__(512) void k_attn_proj(mi_attn_desc a, mi_attn_proj_
     uint4 w = make_uint4(0u, 0u, 0u, 0u);
     if constexpr (!XF) w = *(const uint4 *) wp;
     const float e_bias = p.bias[rc], e_res = p.resid[rc];  // requested before the attention too
-    const float r = attn_head<D, KPG>(a, h, 0, sm, shm, p.stamps);
+    const float r = attn_head<D, KPG>(a, h, 0, sm, shm);
     if constexpr (XF) w = *(const uint4 *) wp;
-    MI_STAMP(p.stamps, 1);  // the head's attention done
     uint16_t * oh = (uint16_t *) (sm + ((a.n_kv + 3) & ~3) + 8 * (D + 8));  // 16-byte aligned
     if (threadIdx.x < D) oh[threadIdx.x] = mi_f2h(r);
     __syncthreads();
@@ -212,8 +204,6 @@ __global__ __launch_bounds__(512) void k_attn_proj(mi_attn_desc a, mi_attn_proj_
     acc = group_sum<LPR>(acc);
     // head 0: (x + bias) + resid, the order of the unfused epilogue
     if (c == 0 && row < p.N) p.parts[(size_t) h * p.N + row] = h == 0 ? (acc + e_bias) + e_res : acc;
-    MI_STAMP_CLK(p.stamps, 5);
-    MI_STAMP(p.stamps, 7);
 }
 
 // out[i] = sum_h parts[h][i], in head order
@@ -254,14 +244,12 @@ void mi_attn_proj(const mi_attn_desc & a, const mi_attn_proj_desc & p, hipStream
     constexpr int RPW = 512 / (64 / 8);
     const dim3 grid((unsigned) ((p.N + RPW - 1) / RPW), (unsigned) a.H);
     const size_t lds = (size_t) (a.n_kv + 3 + 8 * (a.D + 8) + a.D) * sizeof(float);
-    mi_attn_proj_desc ps = p;
-    ps.stamps = mi_stamp_take("k_attn_proj", grid.x * grid.y);
     if (g_mi_tuning.xfirst == 1) {  // (off by default, as the F16 GEMVs)
-        if (a.n_kv <= 256) hipLaunchKernelGGL((k_attn_proj<64, 4, true>), grid, dim3(512), lds, s, a, ps);
-        else hipLaunchKernelGGL((k_attn_proj<64, 8, true>), grid, dim3(512), lds, s, a, ps);
+        if (a.n_kv <= 256) hipLaunchKernelGGL((k_attn_proj<64, 4, true>), grid, dim3(512), lds, s, a, p);
+        else hipLaunchKernelGGL((k_attn_proj<64, 8, true>), grid, dim3(512), lds, s, a, p);
     } else {
-        if (a.n_kv <= 256) hipLaunchKernelGGL((k_attn_proj<64, 4, false>), grid, dim3(512), lds, s, a, ps);
-        else hipLaunchKernelGGL((k_attn_proj<64, 8, false>), grid, dim3(512), lds, s, a, ps);
+        if (a.n_kv <= 256) hipLaunchKernelGGL((k_attn_proj<64, 4, false>), grid, dim3(512), lds, s, a, p);
+        else hipLaunchKernelGGL((k_attn_proj<64, 8, false>), grid, dim3(512), lds, s, a, p);
     }
 }
 

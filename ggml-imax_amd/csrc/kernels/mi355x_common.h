@@ -1,41 +1,10 @@
 // mi355x_common.h -- device helpers shared by the gfx950 kernels (wave64, CDNA4).
 #pragma once
 
-// diagnostic builds (make DIAG=1): timing-ablation and stamp kernels, whose results are invalid,
-// become reachable through ggml_backend_mi355x_set_tuning; release builds compile them out
-#ifndef MI_DIAG
-#define MI_DIAG 0
-#endif
-
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #define MI_WAVE 64
-
-// Phase stamp of a diagnostic build: s_memrealtime (the chip-wide 100 MHz counter) of lane 0 of
-// the workgroup's first wave, written with a plain vector store into slot `slot` of the workgroup's
-// 8-slot record in `buf` (a buffer of its own, never an output). Compiled out of release builds.
-#if MI_DIAG
-#define MI_STAMP(buf, slot)                                                                                                \
-    do {                                                                                                                   \
-        if ((buf) && threadIdx.x == 0)                                                                                     \
-            (buf)[((size_t) blockIdx.y * gridDim.x + blockIdx.x) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime();        \
-    } while (0)
-// the shader clock (s_memtime) at the same point: slot 6 at entry, 5 at exit give the clock the
-// workgroup ran at (delta memtime / delta realtime x 100 MHz)
-#define MI_STAMP_CLK(buf, slot)                                                                                            \
-    do {                                                                                                                   \
-        if ((buf) && threadIdx.x == 0)                                                                                     \
-            (buf)[((size_t) blockIdx.y * gridDim.x + blockIdx.x) * 8 + (slot)] = __builtin_amdgcn_s_memtime();             \
-    } while (0)
-#else
-#define MI_STAMP(buf, slot) \
-    do {                    \
-    } while (0)
-#define MI_STAMP_CLK(buf, slot) \
-    do {                        \
-    } while (0)
-#endif
 
 // Quantized weight blocks exactly as stored by ggml (src/ggml-common.h:144-300). Kernels read
 // them with aligned 16-byte loads where the block size allows (Q4_K 144 B, Q5_K 176 B).

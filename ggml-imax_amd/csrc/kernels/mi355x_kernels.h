@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -99,7 +100,6 @@ struct mi_mmv_group {
     size_t nb01;            // weight row stride (bytes)
     size_t xcol;            // src1 column stride (bytes)
     size_t ycol;            // dst column stride (bytes)
-    int abl = 0;            // timing ablation of the reference-order chain (mmv_order 2: no chain; results invalid)
     int ord_rows = 0;       // reference order: rows per chain pass (0: one pass per 64-item chunk of a row)
     int ord_cs = 0;         // reference order: scratch words per (row, column)
     int ord_s = 0;          // reference order: Q4_0/Q8_0 lane-row stride in the scratch
@@ -125,7 +125,6 @@ struct mi_mmv_group {
         int mode = 0;  // 0 none, 1 norm, 2 rms_norm
     } pro;
     int pro_off = 0;   // set by the launcher: LDS byte offset of the normalized columns
-    uint64_t * stamps = nullptr;  // diagnostic builds: per-workgroup phase stamps (g_mi_stamp_dev)
     int q0r = 0;       // Q4_0 / Q8_0: every member's W is its 16-byte-aligned repacked copy (mi_planes_get type 2 / 8), nb01 = K / 32 * 18 / 34
     int pro_q = 0;     // set by the launcher (g_mi_tuning.mmv_pro4): one Q8_K column's norm prologue quantizes from registers
     mi_mmv_member m[kMiMaxMembers];
@@ -136,54 +135,68 @@ struct mi_mmv_group {
     size_t ids_nb02 = 0;
     int ids_n_as = 0;
 };
-// Diagnostic builds (make DIAG=1): when non-null, the decode kernels write s_memrealtime phase
-// stamps of wave 0 of every workgroup here (kMiStampSlots per workgroup); release builds never do
-extern uint64_t * g_mi_stamp_dev;
-constexpr int kMiStampSlots = 8;
-bool mi_stamps_enable(size_t slots);  // 0: off; false in release builds
-void mi_stamps_reset();
-bool mi_diag_build();  // this library's kernels were built with MI_DIAG (make diaglib)
-// the next launch's stamp range (nullptr when off or full); logs "name nblocks offset"
-uint64_t * mi_stamp_take(const char * name, unsigned nblocks);
-// copies up to n stamp words and the log; returns the words written so far
-size_t mi_stamps_read(uint64_t * host, size_t n, char * log, size_t log_size);
 bool mi_mmv_fused_supported(int type, int64_t K, int64_t ncols);
 constexpr int64_t kMiMmvProMaxK = 768;  // norm prologue: the column is held in one wave's registers
 
-// launch-shape knobs of the streaming kernels (defaults tuned on MI355X; settable for A/B runs)
+// launch-shape knobs of the kernels (defaults tuned on MI355X; settable for A/B runs). Every field is
+// a row of the knob table in mmv_fused.hip: set_tuning("<field>", v) and GGML_MI355X_<FIELD>=v pass
+// the same range check.
 struct mi_tuning {
-    int mmv_blocks;   // target resident workgroups for the fused GEMV (all members)
-    int mmv_variant;  // 10*prefetch_depth + {0: activations in VGPRs, 1: from LDS, 2: LDS + waves/EU cap}
-    int f16_variant;  // decode F16 GEMV: 0 = 16 lanes per row (k_mmv_f16_w16), 1 = quad per row (k_mmv_f16_x)
-    int f16_threads;  // k_mmv_f16_w16 workgroup size override (0 = automatic)
-    int mmq_variant;  // prefill GEMM: 0 = k_mmq3 (activations in registers), 1 = k_mmq2 (activations via LDS)
-    int attn_variant; // attention block: 0 = k_attn_fast where it fits, 1 = k_attn_ordered
-    int attn_abl;     // timing ablations of k_attn_fast (0 = none; results invalid otherwise)
-    int mmv_order;    // decode GEMVs (quantized and F16) and attention: 1 = the reference CPU's summation order (bit-identical,
-                      // slower), 0 = tree sums, -1 (default) = per graph: 1 where a quantized MUL_MAT consumes a value the
-                      // graph computes (its activation re-quantization would carry order differences forward), else 0
-    int f16_waves;    // fast F16 decode GEMV: target waves on the chip (0 = automatic)
-    int f16_rgs;      // fast F16 decode GEMV: row groups (4 rows) per workgroup (0 = automatic)
-    int f16_ps_waves; // k_gemv_f16_ps (GEMV over summed partials): waves per workgroup, 2 / 4 / 8 (0 = automatic)
-    int mmq_long;     // Q4_K / Q5_K prefill past 128 columns: 0 = automatic (Q4_K k_mmqt, Q5_K k_mmqw), 1 = k_mmqw, 2 = k_mmqt; 16-23 k_mmqt stamps (diagnostic builds)
-    int xfirst;       // lone decode GEMVs: activation loads issued and landed before the weight loads: 1 always, 0 / -1 never (-1: the default)
-    int f16_norm_waves; // F16 GEMV, several columns with the norm prologue: waves per workgroup (0 = automatic)
-    int planes;       // long Q4_K prompts on repacked MFMA planes (mmq_planes.hip k_mmqr): 1 on, 0 off (default: slower than k_mmqt with HBM-streamed weights)
-    int f16_nc;       // F16 decode GEMVs: columns per workgroup at most (ones digit: plain, tens: norm prologue; 0: up to 8)
-    int mmv_dma;      // grouped tree-order Q4_K GEMVs on the LDS-DMA weight stream (k_mmv_dma): 0 off, 1-3 shapes, +10 default load policy
-    int f16_bn;       // F16 decode GEMVs, 2..8 columns with the norm prologue (K <= 1024) on k_gemv_f16_bn: 0 off, 1-5 shapes (default 5), +10 one column too
-    int f16_bp;       // F16 decode GEMVs, 2..8 plain columns (K <= 3072) on k_gemv_f16_bn's staging form: 0 off, 1 on
-    int q40r;         // tree-order Q4_0 decode GEMVs on the 16-byte-aligned repacked copy (mmq_planes.hip k_q40_repack, FmtQ0R): 1 on (default), 0 off
-    int q80r;         // tree-order Q8_0 decode GEMVs on the 16-byte-aligned repacked copy (k_q80_repack, FmtQ8R): 1 on (default), 0 off
-    int mmv_pro4;     // decode GEMVs with the norm prologue, one Q8_K column: normalize and quantize in registers (norm_quant_prologue1): 1 (default), 0 through LDS
-    int f16_mt;       // tall F16 GEMVs (lm_head) of 2..8 columns, K <= 768, on the matrix cores (k_gemv_f16_mt): 1 on (default), 0 k_gemv_f16_tall
-    int f16_m8;       // plain F16 GEMVs of 2..8 columns (K <= 4096, K % 32 == 0) on the matrix cores (k_gemv_f16_m8): 0 off (default), 1 on (diagnostic builds: measured slower)
-    int mmqt_short;   // Q4_K prompts of 33..128 columns on k_mmqt (128 x 64 tiles) when a launch has at least this many of its workgroups (default 192; 0: never)
-    int mmid_group;   // MUL_MAT_ID of quantized experts: 1 = prompts from the measured crossover on (reference order: 8 tokens; tree order: never) run
-                      // over the pairs grouped by expert on the device (mi_mmid_group; up to 4 gathered columns per workgroup), 0 = pair by pair;
-                      // 4 / 8: grouped from 2 tokens on in either order with chunks of that many pairs (A/B timing)
-    int mmid_stream;  // MUL_MAT_ID of quantized experts: up to this many tokens run on the streaming decode kernel, a member per pair (0: never)
-    int fuse_router;  // a mixture-of-experts router chain (soft_max, argsort DESC, top-k view, get_rows, sum_rows, div; at most 64 experts) as one launch: 1 on (default), 0 off
+    int mmv_blocks = 0;    // target resident workgroups for the fused GEMV (all members); 0: from the kernel's residency (hipOccupancy...) per instance
+    int mmv_variant = 0;   // 10*prefetch_depth + {0: activations in VGPRs, 1: from LDS, 2: LDS + waves/EU cap}; 0: the per-type default
+    int f16_variant = 0;   // decode F16 GEMV: 0 = 16 lanes per row (k_mmv_f16_w16), 1 = quad per row (k_mmv_f16_x)
+    int f16_threads = 0;   // k_mmv_f16_w16 workgroup size override (0 = automatic)
+    int mmq_variant = 0;   // prefill GEMMs: A/B selection bits (mi_mmq_variant_bits below); 0 = the defaults
+    int attn_variant = 0;  // attention block: 0 = k_attn_fast where it fits, 1 = k_attn_ordered
+    int mmv_order = -1;    // decode GEMVs (quantized and F16) and attention: 1 = the reference CPU's summation order (bit-identical,
+                           // slower), 0 = tree sums, -1 (default) = per graph: 1 where a quantized MUL_MAT consumes a value the
+                           // graph computes (its activation re-quantization would carry order differences forward), else 0
+    int f16_waves = 0;     // fast F16 decode GEMV: target waves on the chip (0 = automatic)
+    int f16_rgs = 0;       // fast F16 decode GEMV: row groups (4 rows) per workgroup (0 = automatic)
+    int f16_ps_waves = 0;  // k_gemv_f16_ps (GEMV over summed partials): waves per workgroup, 2 / 4 / 8 (0 = automatic)
+    int xfirst = -1;       // lone decode GEMVs: activation loads issued and landed before the weight loads: 1 always, 0 / -1 never (-1: the default)
+    int f16_norm_waves = 0;  // F16 GEMV, several columns with the norm prologue: waves per workgroup (0 = automatic)
+    int planes = 0;        // long Q4_K prompts on repacked MFMA planes (mmq_planes.hip k_mmqr): 1 on, 0 off (default: slower than k_mmqt with HBM-streamed weights)
+    int f16_nc = 10;       // F16 decode GEMVs: columns per workgroup at most (ones digit: plain, tens: norm prologue; 0: up to 8)
+    int f16_bn = 5;        // F16 decode GEMVs, 2..8 columns with the norm prologue (K <= 1024) on k_gemv_f16_bn: 0 off, 1-5 shapes (default 5), +10 one column too
+    int q40r = 1;          // tree-order Q4_0 decode GEMVs on the 16-byte-aligned repacked copy (mmq_planes.hip k_q40_repack, FmtQ0R): 1 on (default), 0 off
+    int q80r = 1;          // tree-order Q8_0 decode GEMVs on the 16-byte-aligned repacked copy (k_q80_repack, FmtQ8R): 1 on (default), 0 off
+    int mmv_pro4 = 1;      // decode GEMVs with the norm prologue, one Q8_K column: normalize and quantize in registers (norm_quant_prologue1): 1 (default), 0 through LDS
+    int f16_mt = 1;        // tall F16 GEMVs (lm_head) of 2..8 columns, K <= 768, on the matrix cores (k_gemv_f16_mt): 1 on (default), 0 k_gemv_f16_tall
+    int mmqt_short = 192;  // Q4_K prompts of 33..128 columns on k_mmqt (128 x 64 tiles) when a launch has at least this many of its workgroups (default 192; 0: never)
+    int mmid_group = 1;    // MUL_MAT_ID of quantized experts: 1 = prompts from the measured crossover on (reference order: 8 tokens; tree order: never) run
+                           // over the pairs grouped by expert on the device (mi_mmid_group; up to 4 gathered columns per workgroup), 0 = pair by pair;
+                           // 4 / 8: grouped from 2 tokens on in either order with chunks of that many pairs (A/B timing)
+    int mmid_stream = 8;   // MUL_MAT_ID of quantized experts: up to this many tokens run on the streaming decode kernel, a member per pair (0: never)
+    int fuse_router = 1;   // a mixture-of-experts router chain (soft_max, argsort DESC, top-k view, get_rows, sum_rows, div; at most 64 experts) as one launch: 1 on (default), 0 off
+    int ord_prefill_cols = INT_MAX;  // reference-order graphs: quantized prompt mul_mats of up to this many columns run as 8-column chunks of the
+                           // reference-order streaming GEMV (ord_prefill_chunked in the backend); longer prompts take the MFMA GEMMs; 0: off
+    int tree_prefill_cols = 0;  // tree-order graphs: the same chunks for prompts of up to this many columns (0: off)
+};
+// looks `name` up in the knob table; false: unknown name or a value outside the knob's range
+bool mi_tuning_set(const char * name, int value);
+// mmq_variant bits. Within a weight-format family every kernel keeps the family's canonical combine,
+// so any choice gives the same bits; a bit only picks the kernel.
+enum mi_mmq_variant_bits : int {
+    kMmqActLds = 1,              // f16 GEMM (mmq.hip): k_mmq2, row-major activations via LDS (k_mmq3 / k_mmf16p read the K-blocked layout)
+    kMmqXcdOrder = 2,            // f16 GEMM: k_mmq3 with XCD-contiguous tile order
+    kMmqShortKernels = 16,       // exact GEMMs: the short-prompt kernels (k_mmqp / k_mmq0p) at any column count
+    kMmqxLead1 = 64,             // Q4_K / Q5_K long prompts: k_mmqx with a weight ring of 1
+    kMmqLongKernels = 128,       // exact GEMMs: the long-prompt kernels of the canonical blocks at any column count (k_mmq0x: 8 waves, 64 x 128)
+    kMmqd1 = 2048,               // Q4_K / Q5_K short prompts, K <= 4096: k_mmqd1 (a wave per superblock)
+    kMmqNoD16 = 4096,            // Q4_K / Q5_K short prompts: k_mmqp even where bits 2^21 / 2^22 ask for k_mmqd16
+    kMmqNoShortT = 8192,         // Q4_K prompts of 33..128 columns: never k_mmqt (as mmqt_short 0)
+    kMmqHalfWidth = 1 << 16,     // k_mmqx / k_mmq0x: half-width workgroups (64 x 64 tiles, 4 waves)
+    kMmqFullWidth = 1 << 17,     // Q4_K: no automatic half-width k_mmqx below 256 full tiles
+    kMmqNoF16p = 1 << 18,        // F16 weights, 9..128 columns: k_mmq3 instead of k_mmf16p
+    kMmqF16p8 = 1 << 20,         // k_mmf16p: 8 waves per tile (K % 512 == 0, fewer than 512 tiles)
+    kMmqd16 = 1 << 21,           // Q4_K / Q5_K, K <= 4096: k_mmqd16 (16 x 16 tiles) up to 16 columns
+    kMmqd16Wide = 1 << 22,       // the same up to 128 columns
+    kMmq0xRows2 = 1 << 24,       // with kMmqLongKernels, Q4_0 / Q8_0: k_mmq0x NR = 2 (4 waves, 64 x 128)
+    kMmq0xRows2W8 = 1 << 25,     // with kMmqLongKernels, Q4_0 / Q8_0: k_mmq0x NR = 2 with 8 waves (64 x 256)
+    kMmqp8 = 1 << 27,            // k_mmqp: 8 waves per tile (one workgroup per CU)
+    kMmqxOnly = 1 << 28,         // Q4_K / Q5_K long prompts: k_mmqx instead of k_mmqt / k_mmqw
+    kMmqF16Gemm = 1 << 30,       // quantized prompts on the f16 GEMM (mi_mul_mat_mmq) instead of the exact-integer kernels
 };
 extern mi_tuning g_mi_tuning;
 // the order of the graph being launched when mmv_order is -1 (set by the backend per graph)
@@ -198,15 +211,10 @@ void mi_mul_mat_q_fused(mi_mmv_group & g, hipStream_t s);
 // dst columns of ycol bytes. Requires K % 256 == 0.
 bool mi_mmq_supported(int type, int64_t K, size_t nb01, size_t ycol);
 // F16 weights, 9..128 columns (mmq.hip k_mmf16p): xh = f16 activations in the K-blocked layout
-// [K/16][ncols][16]; K % 256 == 0, 16-byte aligned rows (mmq_variant bits 1 / 2^18 turn it off)
+// [K/16][ncols][16]; K % 256 == 0, 16-byte aligned rows (mmq_variant bits kMmqActLds / kMmqNoF16p turn it off)
 bool mi_mmf16p_supported(int64_t K, int64_t N, size_t nb01, int64_t ncols, size_t ycol);
 void mi_mul_mat_f16p(const void * W, size_t nb01, int64_t K, int64_t N, const uint16_t * xh, int64_t ncols, float * dst, size_t ycol,
                      hipStream_t s);
-// the same reading the f32 src1 columns (xnb1 bytes apart) and rounding them to f16 in the kernel
-// (one launch, no conversion pass); 16-byte aligned columns
-bool mi_mmf16p_f32_supported(int64_t K, int64_t N, size_t nb01, int64_t ncols, size_t ycol, const void * x, size_t xnb1);
-void mi_mul_mat_f16p_f32(const void * W, size_t nb01, int64_t K, int64_t N, const float * x, size_t xnb1, int64_t ncols, float * dst,
-                         size_t ycol, hipStream_t s);
 // scratch for the f16 expansion of quantized activations when xh == nullptr (0 for F16 weights)
 size_t mi_mmq_scratch_bytes(int type, int64_t K, int64_t ncols);
 void mi_mul_mat_mmq(int type, const void * W, size_t nb01, int64_t K, int64_t N, const mi_act_q8 & act, const uint16_t * xh,
@@ -281,8 +289,6 @@ void mi_mul_mat_mmqx(int type, const void * W, size_t nb01, int64_t K, int64_t N
 // capturing), or null (disabled: GGML_MI355X_PLANES=0, unsupported shape, capture). Any write to
 // weight memory must be followed by mi_planes_refresh over the written bytes (a repack launch on
 // s for every overlapping entry; capturable); freeing the memory by mi_planes_drop.
-// mmq_variant bits of opt-in kernel forms measured slower than the defaults: diagnostic builds only
-constexpr int kMiMmqDiagBits = (1 << 19) | (1 << 26);  // (bit 2^17 doubles as k_mmqx's full-width bit)
 constexpr int64_t kMiPlanesMinCols = 129;  // prompts of more columns take the planes kernel
 // Types 2 / 8 (Q4_0 / Q8_0, g_mi_tuning.q40r / q80r): the tree-order decode GEMV's 16-byte-aligned
 // copy instead (k_q40_repack / k_q80_repack: per row the quants of every block, then their f16
@@ -366,7 +372,6 @@ struct mi_f16_epilogue {
         char * ptr = nullptr;
         size_t col_stride = 0;
     } copy[2];
-    uint64_t * stamps = nullptr;  // diagnostic builds: phase stamps (g_mi_stamp_dev)
     int xfirst = 0;               // set by the launcher (g_mi_tuning.xfirst): activations landed before the weight loads
 };
 // optional prologue: src1 = add(mul(norm|rms_norm(x, eps), g), b) computed in the kernel from x
@@ -427,7 +432,6 @@ struct mi_attn_proj_desc {
     const float * bias;   // [N]
     const float * resid;  // [N]
     float * parts;        // [H][N]
-    uint64_t * stamps = nullptr;  // diagnostic builds: phase stamps (g_mi_stamp_dev)
 };
 bool mi_attn_proj_supported(const mi_attn_desc & a, int64_t K, int64_t N, size_t nb01, const void * W);
 void mi_attn_proj(const mi_attn_desc & a, const mi_attn_proj_desc & p, hipStream_t s);

@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256 * SK) void k_mmq2(const uint8_t * __restrict__ 
 // 16 KB and re-read it per stage and group, which left the LDS array, not the MFMAs, as the
 // busiest unit). Only the dequantized 64 x 64 weight slab of a stage goes through LDS, written
 // once per group and read by its four waves (two A fragments per K step each).
-template <int TYPE, int SK, int NST, bool XCD, int ABL = 0>
+template <int TYPE, int SK, int NST, bool XCD>
 __global__ __launch_bounds__(256 * SK) void k_mmq3(const uint8_t * __restrict__ W, size_t nb01, int64_t K, int64_t N,
                                               const uint16_t * __restrict__ xh, int64_t ncols, float * __restrict__ dst,
                                               size_t ycol) {
@@ -343,7 +343,6 @@ __global__ __launch_bounds__(256 * SK) void k_mmq3(const uint8_t * __restrict__ 
     Raw raw[kPF];
     half8 xb[kPF][BK / 16];
     auto load_stage = [&](Raw & rw, half8 (&xv)[BK / 16], int64_t k0) {
-        if constexpr (ABL == 2) k0 = 0;  // ablation (timing only): every stage reads the first slab
         rw.load(wrow, k0 + ak);
 #pragma unroll
         for (int i = 0; i < BK / 16; i++) xv[i] = *(const half8 *) (xcol + (k0 / 16 + i) * kstep);
@@ -392,13 +391,8 @@ __global__ __launch_bounds__(256 * SK) void k_mmq3(const uint8_t * __restrict__ 
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int kk = 0; kk < BK / 16; kk++) {
-                if constexpr (ABL == 1) {  // ablation (timing only): no MFMAs
-                    acc0[kk] += (float) a0[kk][0] * (float) xb[u][kk][0];
-                    acc1[kk] += (float) a1[kk][1] * (float) xb[u][kk][1];
-                } else {
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[kk], xb[u][kk], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[kk], xb[u][kk], acc1, 0, 0, 0);
-                }
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[kk], xb[u][kk], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[kk], xb[u][kk], acc1, 0, 0, 0);
             }
             const int un = (u + 1) % kPF;
             store_stage(cur ^ 1, raw[un], kg + (st + 1 < nst ? st + 1 : st) * BK);  // last: harmless rewrite
@@ -465,14 +459,10 @@ __global__ __launch_bounds__(256 * SK) void k_mmq3(const uint8_t * __restrict__ 
 // profiles/r03z_f16_pmc.txt.) The four partial tiles meet in LDS and are added in wave order.
 // Products of fp16 values are exact in f32; only the summation order differs from the reference's
 // ggml_vec_dot_f16 (~1e-7 relative).
-// F32X: the activations are the f32 src1 itself (columns of K contiguous floats, xcs floats apart),
-// rounded to f16 in the kernel as ggml_fp32_to_fp16_row does (RNE; ggml.c:605-616) right before
-// their MFMA -- no separate conversion launch (each column tile's activations are converted by every
-// row tile that reads them: VALU the memory-bound kernel has to spare)
-template <int PF, int NW, bool F32X = false>
+template <int PF, int NW>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mmf16p(const uint8_t * __restrict__ W, size_t nb01, int64_t K, int64_t N,
                                                    const uint16_t * __restrict__ xh, int64_t ncols, float * __restrict__ dst,
-                                                   size_t ycol, const float * __restrict__ xf = nullptr, int64_t xcs = 0) {
+                                                   size_t ycol) {
     constexpr int kRow = 72;  // halves per LDS row (64 + 8 pad)
     __shared__ __attribute__((aligned(16))) _Float16 lw[NW][32 * kRow];
     __shared__ __attribute__((aligned(16))) float red[NW][16][64];
@@ -488,43 +478,19 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mmf16p(const uint8
 #pragma unroll
     for (int q = 0; q < 4; q++) wq[q] = W + std::min<int64_t>(n0 + lr + 8 * q, N - 1) * nb01 + (size_t) (w * kw) * 2 + 16 * lp;
     const int64_t col = std::min<int64_t>(c0 + r, ncols - 1);
-    const uint16_t * xc = F32X ? nullptr : xh + ((size_t) (w * kw / 16) * ncols + col) * 16 + 8 * h;
-    const float * xfc = F32X ? xf + col * xcs + w * kw + 8 * h : nullptr;
+    const uint16_t * xc = xh + ((size_t) (w * kw / 16) * ncols + col) * 16 + 8 * h;
     const size_t xstep = (size_t) ncols * 16;  // halves per 16-deep K step
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // (a HIP uint4 array is not promoted to registers)
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     struct Chunk {
         u32x4 wv[4];
-        u32x4 xv[F32X ? 0 : 4];
-        f32x4 xw[F32X ? 8 : 0];  // F32X: the 8 floats of each 16-deep step's lane half
+        u32x4 xv[4];
     };
     auto load = [&](Chunk & c, int i) {
         i = i < nch ? i : nch - 1;  // past the end: a harmless re-read of the last chunk
 #pragma unroll
         for (int q = 0; q < 4; q++) c.wv[q] = *(const u32x4 *) (wq[q] + (size_t) i * 128);
-        if constexpr (F32X) {
 #pragma unroll
-            for (int st = 0; st < 4; st++) {
-                c.xw[2 * st] = *(const f32x4 *) (xfc + (size_t) i * 64 + 16 * st);
-                c.xw[2 * st + 1] = *(const f32x4 *) (xfc + (size_t) i * 64 + 16 * st + 4);
-            }
-        } else {
-#pragma unroll
-            for (int st = 0; st < 4; st++) c.xv[st] = *(const u32x4 *) (xc + ((size_t) i * 4 + st) * xstep);
-        }
-    };
-    auto xop = [&](const Chunk & c, int st) -> half8 {
-        if constexpr (F32X) {
-            half8 v;
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                v[e] = (_Float16) c.xw[2 * st][e];
-                v[4 + e] = (_Float16) c.xw[2 * st + 1][e];
-            }
-            return v;
-        } else {
-            return __builtin_bit_cast(half8, c.xv[st]);
-        }
+        for (int st = 0; st < 4; st++) c.xv[st] = *(const u32x4 *) (xc + ((size_t) i * 4 + st) * xstep);
     };
     _Float16 * tile = lw[w];
     Chunk ring[PF];
@@ -538,7 +504,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mmf16p(const uint8
 #pragma unroll
         for (int st = 0; st < 4; st++) {
             const half8 a = *(const half8 *) (tile + r * kRow + 16 * st + 8 * h);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, xop(c, st), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, __builtin_bit_cast(half8, c.xv[st]), acc, 0, 0, 0);
         }
         load(c, i + PF);
     };
@@ -577,41 +543,21 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mmf16p(const uint8
 } // namespace
 
 bool mi_mmf16p_supported(int64_t K, int64_t N, size_t nb01, int64_t ncols, size_t ycol) {
-    return mi_mmq_wants_blocked() && (g_mi_tuning.mmq_variant & (1 << 18)) == 0 && ncols > 8 && ncols <= 128 && K % 256 == 0 && N >= 1 &&
+    return mi_mmq_wants_blocked() && (g_mi_tuning.mmq_variant & kMmqNoF16p) == 0 && ncols > 8 && ncols <= 128 && K % 256 == 0 && N >= 1 &&
            nb01 % 16 == 0 && ycol % 16 == 0;
 }
 
 void mi_mul_mat_f16p(const void * W, size_t nb01, int64_t K, int64_t N, const uint16_t * xh, int64_t ncols, float * dst, size_t ycol,
                      hipStream_t s) {
     const int64_t tiles = ((N + 31) / 32) * ((ncols + 31) / 32);
-    // variant bit 2^20: 8 waves per tile (K in eighths: twice the loads in flight per CU when the
+    // variant bit kMmqF16p8: 8 waves per tile (K in eighths: twice the loads in flight per CU when the
     // tiles do not fill the chip twice over); K % 512 == 0
-    const bool w8 = K % 512 == 0 && tiles < 512 && (g_mi_tuning.mmq_variant & (1 << 20)) != 0;
+    const bool w8 = K % 512 == 0 && tiles < 512 && (g_mi_tuning.mmq_variant & kMmqF16p8) != 0;
     if (w8) hipLaunchKernelGGL((k_mmf16p<3, 8>), dim3((unsigned) tiles), dim3(512), 0, s, (const uint8_t *) W, nb01, K, N, xh, ncols, dst, ycol);
     else hipLaunchKernelGGL((k_mmf16p<3, 4>), dim3((unsigned) tiles), dim3(256), 0, s, (const uint8_t *) W, nb01, K, N, xh, ncols, dst, ycol);
 }
 
-bool mi_mmf16p_f32_supported(int64_t K, int64_t N, size_t nb01, int64_t ncols, size_t ycol, const void * x, size_t xnb1) {
-    // opt-in (variant bit 2^17): measured SLOWER than the separate conversion launch + k_mmf16p
-    // (profiles/r04c_pf_f16.txt, 16 rotated weights: B=64 23.3 vs 17.3 us, B=32 22.9 vs 17.2 us) --
-    // every row tile re-reads and re-converts its columns' f32 (twice the bytes of f16, 128 row tiles)
-    // (diagnostic builds only)
-    return MI_DIAG && mi_mmf16p_supported(K, N, nb01, ncols, ycol) && ((uintptr_t) x % 16) == 0 && xnb1 % 16 == 0 &&
-           (g_mi_tuning.mmq_variant & (1 << 17)) != 0;
-}
-
-void mi_mul_mat_f16p_f32(const void * W, size_t nb01, int64_t K, int64_t N, const float * x, size_t xnb1, int64_t ncols, float * dst,
-                         size_t ycol, hipStream_t s) {
-#if MI_DIAG
-    const int64_t tiles = ((N + 31) / 32) * ((ncols + 31) / 32);
-    hipLaunchKernelGGL((k_mmf16p<2, 4, true>), dim3((unsigned) tiles), dim3(256), 0, s, (const uint8_t *) W, nb01, K, N, nullptr, ncols,
-                       dst, ycol, x, (int64_t) (xnb1 / sizeof(float)));
-#else
-    (void) W; (void) nb01; (void) K; (void) N; (void) x; (void) xnb1; (void) ncols; (void) dst; (void) ycol; (void) s;
-#endif
-}
-
-bool mi_mmq_wants_blocked() { return (g_mi_tuning.mmq_variant & 1) == 0; }
+bool mi_mmq_wants_blocked() { return (g_mi_tuning.mmq_variant & kMmqActLds) == 0; }
 
 bool mi_mmq_supported(int type, int64_t K, size_t nb01, size_t ycol) {
     if (type != 12 && type != 13 && type != 2 && type != 8 && type != 1) return false;
@@ -639,20 +585,17 @@ void mi_mul_mat_mmq(int type, const void * W, size_t nb01, int64_t K, int64_t N,
     // split K over two 4-wave groups when each group keeps a whole number of ring turns: with
     // one 64x128 tile per CU (grid <= 256) a single 4-wave group leaves one wave per SIMD
     const bool sk2 = K % (2 * BK * kPF) == 0;
-    // variant bits: 1 = k_mmq2 (activations via LDS), 2 = XCD-contiguous tile order, 8/16 = timing
-    // ablations; k_mmq3 is fully unrolled over the K stages for the common K (the loop back-edge
+    // variant bits: kMmqActLds = k_mmq2 (activations via LDS), kMmqXcdOrder = XCD-contiguous tile
+    // order; k_mmq3 is fully unrolled over the K stages for the common K (the loop back-edge
     // of the runtime-K loop makes the compiler drain the load ring: measured 47 -> 43 us at 4096)
     const int var = g_mi_tuning.mmq_variant;
-    const bool v3 = (var & 1) == 0;
-    const bool xcd = (var & 2) != 0;
-    const int abl = MI_DIAG ? (var >> 3) & 3 : 0;  // timing ablations (results invalid): make DIAG=1 only
+    const bool v3 = (var & kMmqActLds) == 0;
+    const bool xcd = (var & kMmqXcdOrder) != 0;
     const int nst2 = sk2 ? (int) (K / BK / 2) : 0;
     const dim3 grid1((unsigned) (((grid.x * grid.y) + 7) / 8 * 8));
 #define MI_MMQ3(T, NST) hipLaunchKernelGGL((k_mmq3<T, 2, NST, false>), grid, dim3(512), 0, s, w, nb01, K, N, xh, ncols, dst, ycol)
 #define MI_MMQ_LAUNCH(T)                                                                                             \
-    if (v3 && abl == 1 && nst2 == 32) hipLaunchKernelGGL((k_mmq3<T, 2, 32, false, 1>), grid, dim3(512), 0, s, w, nb01, K, N, xh, ncols, dst, ycol); \
-    else if (v3 && abl == 2 && nst2 == 32) hipLaunchKernelGGL((k_mmq3<T, 2, 32, false, 2>), grid, dim3(512), 0, s, w, nb01, K, N, xh, ncols, dst, ycol); \
-    else if (v3 && sk2 && xcd) hipLaunchKernelGGL((k_mmq3<T, 2, 0, true>), grid1, dim3(512), 0, s, w, nb01, K, N, xh, ncols, dst, ycol); \
+    if (v3 && sk2 && xcd) hipLaunchKernelGGL((k_mmq3<T, 2, 0, true>), grid1, dim3(512), 0, s, w, nb01, K, N, xh, ncols, dst, ycol); \
     else if (v3 && nst2 == 32) MI_MMQ3(T, 32);                                                                       \
     else if (v3 && nst2 == 24) MI_MMQ3(T, 24);                                                                       \
     else if (v3 && nst2 == 16) MI_MMQ3(T, 16);                                                                       \

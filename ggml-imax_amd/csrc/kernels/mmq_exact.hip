@@ -201,7 +201,7 @@ namespace {
 // Canonical combine (shared by every kernel of this file): mmqx_pre per superblock, cfold's order.
 // NWV = 4: half-width workgroups (64 rows x 64 columns, 4 waves, each thread stages two rows), two
 // per CU, so one workgroup's barrier wait overlaps the other's MFMA steps.
-template <int TYPE, bool XCD, int ABL = 0, int LEAD = 4, int SCT = 0, int NWV = 8>
+template <int TYPE, int LEAD = 4, int NWV = 8>
 __global__ __launch_bounds__(64 * NWV) void k_mmqx(mi_mmx_group g) {
     MI_MMX_MEMBER(g);
     using F = XFmt<TYPE>;
@@ -219,39 +219,9 @@ __global__ __launch_bounds__(64 * NWV) void k_mmqx(mi_mmx_group g) {
     const int wave = tid >> 6, lane = tid & 63;
     const int rw = wave & 1, cw = wave >> 1;
     const int64_t ncols = act.ncols;
-    int64_t n0, b0;
-    {
-        const int64_t nrt = (N + XBM - 1) / XBM, nct = (ncols + XBN_ - 1) / XBN_;
-        int64_t t = mmx_tile;
-        if constexpr (XCD) {
-            // workgroup i runs on XCD i % 8: give each XCD a contiguous run of tiles, row tiles
-            // fastest, so an XCD's L2 holds few activation column tiles (one-member launches)
-            const int64_t T = nrt * nct, per = (T + 7) / 8;
-            t = (int64_t) (blockIdx.x % 8) * per + blockIdx.x / 8;
-            if (t >= T) return;
-        }
-        n0 = (t % nrt) * XBM;
-        b0 = (t / nrt) * XBN_;
-    }
+    const int64_t nrt = (N + XBM - 1) / XBM;
+    const int64_t n0 = (mmx_tile % nrt) * XBM, b0 = (mmx_tile / nrt) * XBN_;
     const int S = (int) (K / 256);
-    // timing diagnostics (ABL & 8; results invalid): s_memtime of wave 0 of workgroups 0 and 97 into
-    // dst as uint64 [2][80]: 0 start, 1 after the prologue, 2 + 4 sb + {0 stage start, 1 after the
-    // MFMA steps, 2 after the combine, 3 after the barrier}
-    auto stamp = [&](int slot) {
-        if constexpr ((ABL & 8) != 0) {
-            const int wsel = blockIdx.x == 0 ? 0 : blockIdx.x == 97 ? 1 : -1;
-            if (wsel >= 0 && (threadIdx.x >> 6) == 0 && (threadIdx.x & 63) == 0 && slot < 80)
-                ((uint64_t *) dst)[wsel * 80 + slot] = __builtin_amdgcn_s_memtime();
-        }
-    };
-    // and every workgroup's start / end on the constant 100 MHz clock: uint64 [gridDim][2] at 160
-    auto rstamp = [&](int e) {
-        if constexpr ((ABL & 8) != 0) {
-            if (threadIdx.x == 0) ((uint64_t *) dst)[160 + 2 * blockIdx.x + e] = __builtin_amdgcn_s_memrealtime();
-        }
-    };
-    rstamp(0);
-    stamp(0);
 
     // All global loads go through buffer descriptors with 32-bit per-lane offsets (the host
     // checks the sizes): one address register per load instead of a 64-bit pointer.
@@ -338,7 +308,6 @@ __global__ __launch_bounds__(64 * NWV) void k_mmqx(mi_mmx_group g) {
         }
     };
     auto dq_piece = [&](int buf, const Dq & dq, int k, int pr) {
-        if constexpr ((ABL & 1) != 0) return;  // timing ablation: no dequantization
         char * pl0 = lds + buf * kBuf + (ar + pr * RSTEP) * XR + 32 * j0 + 16 * hf;
         const int p = k >> 1;
         if ((k & 1) == 0) {
@@ -350,7 +319,6 @@ __global__ __launch_bounds__(64 * NWV) void k_mmqx(mi_mmx_group g) {
         }
     };
     auto dq_rows = [&](int buf, const Raw & raw, int pr) {
-        if constexpr ((ABL & 1) != 0) return;
         const int ar = (tid >> 3) + pr * RSTEP;
         // row operands: U halves [m_c, 64 m_c] at slot c; d_w (c = 0), dmin_w (c = 1)
         char * ro = lds + buf * kBuf + NP * kPlane;
@@ -395,10 +363,8 @@ __global__ __launch_bounds__(64 * NWV) void k_mmqx(mi_mmx_group g) {
         }
     };
     auto park = [&](const f32x16 & v) {
-        if constexpr ((ABL & 8) == 0) {
-            f32x16 t = v;
-            y_io(t, true);
-        }
+        f32x16 t = v;
+        y_io(t, true);
     };
     const int gs = cfold_gs(S);
     // The raw weights of superblock sb + 1 are dequantized into LDS at the end of stage sb; they
@@ -419,14 +385,10 @@ __global__ __launch_bounds__(64 * NWV) void k_mmqx(mi_mmx_group g) {
 #pragma unroll
         for (int pr = 0; pr < ROWP; pr++) load_raw(raw[u][pr], 1 + u, pr);
     mi_lds_barrier();
-    stamp(1);
 
     // one stage = superblock sb; LDS buffer sb & 1. Unrolled by LEAD so every ring slot index is
-    // static (slot u = sb % LEAD holds superblock sb + 1); fully unrolled when S is a template
-    // constant (SCT), so no loop back-edge makes the compiler drain the ring.
-    const int S_ = SCT > 0 ? SCT : S;
+    // static (slot u = sb % LEAD holds superblock sb + 1).
     auto stage = [&](const int sb, Raw (&rslot)[ROWP]) {
-        stamp(2 + 4 * sb);
         const int cur = sb & 1;
         const char * base = lds + cur * kBuf;
         const char * arow_p = base + (32 * rw + r) * XR + 16 * h;
@@ -455,13 +417,8 @@ __global__ __launch_bounds__(64 * NWV) void k_mmqx(mi_mmx_group g) {
                 for (int p = 0; p < NP; p++) an[kk & 1][p] = *(const i32x4 *) (arow_p + p * kPlane + 32 * (kk + 2));
             }
 #pragma unroll
-            for (int p = 0; p < NP; p++) {
-                if constexpr ((ABL & 4) != 0) {  // timing ablation: no MFMAs
-                    acc[p][kk] = (kk == 0 ? 0 : acc[p][kk]) + a[p][0] * xs.q[kk][0];
-                } else {
-                    acc[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[p], xs.q[kk], kk == 0 ? i32x16{} : acc[p], 0, 0, 0);
-                }
-            }
+            for (int p = 0; p < NP; p++)
+                acc[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[p], xs.q[kk], kk == 0 ? i32x16{} : acc[p], 0, 0, 0);
             // step kk of the next superblock into the register just consumed
             xs.q[kk] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(xres, xcol + (kbn + kk) * xstep, 0, 0));
 #pragma unroll
@@ -475,71 +432,43 @@ __global__ __launch_bounds__(64 * NWV) void k_mmqx(mi_mmx_group g) {
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        stamp(3 + 4 * sb);
         // U on the f16 MFMA, then the canonical combine
-        if constexpr ((ABL & 2) != 0) {  // timing ablation: no combine
-#pragma unroll
-            for (int i = 0; i < 16; i++) {
-                float gg = gsum[i], yy = y[i], ll = -0.0f;  // (timing ablation: results invalid)
-                cfold(gg, yy, ll, (float) acc[0][i], 1.0f, sb, gs, S);
-                gsum[i] = gg;
-                y[i] = yy;
-            }
-        } else {
-            const char * ro = base + NP * kPlane;
-            const float * dwv = (const float *) (ro + XBM * 32);
-            const half8 au = *(const half8 *) (ro + (32 * rw + r) * 32 + 16 * h);
-            const f32x16 Uv = __builtin_amdgcn_mfma_f32_32x32x16_f16(au, xs.bu, f32x16{}, 0, 0, 0);
-            const float da = xs.da;
-            {
-                const uint32_t sc = (uint32_t) nx * (uint32_t) ncols + bcol;
-                xs.bu = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(ures, sc * 32 + 16 * h, 0, 0));
-                xs.da = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dres, sc * 4, 0, 0));
-            }
-            f32x16 tv;
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const float4 dw4 = *(const float4 *) (dwv + 32 * rw + 8 * g + 4 * h);
-                const float4 dm4 = *(const float4 *) (dwv + XBM + 32 * rw + 8 * g + 4 * h);
-                const float dw[4] = {dw4.x, dw4.y, dw4.z, dw4.w};
-                const float dm[4] = {dm4.x, dm4.y, dm4.z, dm4.w};
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const int i = 4 * g + e;
-                    int T = acc[NP - 1][i];
-#pragma unroll
-                    for (int p = NP - 2; p >= 0; p--) T = (T << F::SHIFT) + acc[p][i];
-                    tv[i] = mmqx_pre(T, Uv[i], dw[e], dm[e]);
-                }
-            }
-            cfold_vec_park(gsum, y, tv, f32x16(da), sb, gs, S, park);
+        const char * ro = base + NP * kPlane;
+        const float * dwv = (const float *) (ro + XBM * 32);
+        const half8 au = *(const half8 *) (ro + (32 * rw + r) * 32 + 16 * h);
+        const f32x16 Uv = __builtin_amdgcn_mfma_f32_32x32x16_f16(au, xs.bu, f32x16{}, 0, 0, 0);
+        const float da = xs.da;
+        {
+            const uint32_t sc = (uint32_t) nx * (uint32_t) ncols + bcol;
+            xs.bu = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(ures, sc * 32 + 16 * h, 0, 0));
+            xs.da = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dres, sc * 4, 0, 0));
         }
-        stamp(4 + 4 * sb);
-        mi_lds_barrier();
-        stamp(5 + 4 * sb);
-    };
-    if constexpr (SCT > 0) {
+        f32x16 tv;
 #pragma unroll
-        for (int sb = 0; sb < SCT; sb++) stage(sb, raw[sb % LEAD]);
-    } else {
-        for (int sb0 = 0; sb0 < S_; sb0 += LEAD) {
+        for (int g = 0; g < 4; g++) {
+            const float4 dw4 = *(const float4 *) (dwv + 32 * rw + 8 * g + 4 * h);
+            const float4 dm4 = *(const float4 *) (dwv + XBM + 32 * rw + 8 * g + 4 * h);
+            const float dw[4] = {dw4.x, dw4.y, dw4.z, dw4.w};
+            const float dm[4] = {dm4.x, dm4.y, dm4.z, dm4.w};
 #pragma unroll
-            for (int u = 0; u < LEAD; u++) {
-                if (sb0 + u < S_) stage(sb0 + u, raw[u]);
+            for (int e = 0; e < 4; e++) {
+                const int i = 4 * g + e;
+                int T = acc[NP - 1][i];
+#pragma unroll
+                for (int p = NP - 2; p >= 0; p--) T = (T << F::SHIFT) + acc[p][i];
+                tv[i] = mmqx_pre(T, Uv[i], dw[e], dm[e]);
             }
+        }
+        cfold_vec_park(gsum, y, tv, f32x16(da), sb, gs, S, park);
+        mi_lds_barrier();
+    };
+    for (int sb0 = 0; sb0 < S; sb0 += LEAD) {
+#pragma unroll
+        for (int u = 0; u < LEAD; u++) {
+            if (sb0 + u < S) stage(sb0 + u, raw[u]);
         }
     }
 
-    rstamp(1);
-    if constexpr ((ABL & 8) != 0) {
-        // dst holds the stamps; keep the results alive (an unlikely-value store) so nothing is
-        // eliminated
-        float t = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; i++) t += y[i];
-        if (t == 1.2345e-30f) dst[4096 + threadIdx.x] = t;
-        return;
-    }
     if (cfold_split(S) < S) {  // cfold_end: the parked low half + the high half
         f32x16 lo = {};
         y_io(lo, false);
@@ -557,8 +486,7 @@ __global__ __launch_bounds__(64 * NWV) void k_mmqx(mi_mmx_group g) {
 // MFMA steps, its share of the dequantization and the combine, and the barrier then waits for the
 // slowest; here the MFMA waves' stage is only MFMAs + combine. Same operands, same canonical combine
 // (mmqx_pre, cfold_vec): bit-identical to k_mmqx.
-// ABL 8: timing stamps of MFMA wave 0 (workgroups 0 and 97) into dst, as k_mmqx (results invalid)
-template <int TYPE, int LEAD, int ABL = 0>
+template <int TYPE, int LEAD>
 __global__ __launch_bounds__(768, 1) void k_mmqw(mi_mmx_group g) {
     MI_MMX_MEMBER(g);
     using F = XFmt<TYPE>;
@@ -703,19 +631,6 @@ __global__ __launch_bounds__(768, 1) void k_mmqw(mi_mmx_group g) {
         return;
     }
 
-    auto stamp = [&](int slot) {
-        if constexpr ((ABL & 8) != 0) {
-            const int wsel = blockIdx.x == 0 ? 0 : blockIdx.x == 97 ? 1 : -1;
-            if (wsel >= 0 && wave == 0 && lane == 0 && slot < 80) ((uint64_t *) dst)[wsel * 80 + slot] = __builtin_amdgcn_s_memtime();
-        }
-    };
-    auto rstamp = [&](int e) {
-        if constexpr ((ABL & 8) != 0) {
-            if (threadIdx.x == 0) ((uint64_t *) dst)[160 + 2 * blockIdx.x + e] = __builtin_amdgcn_s_memrealtime();
-        }
-    };
-    rstamp(0);
-    stamp(0);
     f32x16 y = f32x16(-0.0f), gsum = {};
     // the thread's output elements D[n][b]: column b = lane & 31 of this wave's 32, rows n = (reg & 3)
     // + 8 (reg >> 2) + 4 (lane >> 5); also where the low half's sum is parked (no register to spare)
@@ -745,17 +660,13 @@ __global__ __launch_bounds__(768, 1) void k_mmqw(mi_mmx_group g) {
         }
     };
     auto park = [&](const f32x16 & v) {
-        if constexpr ((ABL & 8) == 0) {
-            f32x16 t = v;
-            y_io(t, true);
-        }
+        f32x16 t = v;
+        y_io(t, true);
     };
     Xs xs;
     load_x(xs, 0);
     mi_lds_barrier();
-    stamp(1);
     for (int sb = 0; sb < S; sb++) {
-        stamp(2 + 4 * sb);
         const char * base = lds + (sb & 1) * kBuf;
         const char * arow_p = base + (32 * rw + r) * XR + 16 * h;
         const int nx = sb + 1 < S ? sb + 1 : S - 1;
@@ -783,7 +694,6 @@ __global__ __launch_bounds__(768, 1) void k_mmqw(mi_mmx_group g) {
             xs.q[kk] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(xres, xcol, so, 0));
             __builtin_amdgcn_sched_barrier(0);
         }
-        stamp(3 + 4 * sb);
         const char * ro = base + NP * kPlane;
         const float * dwv = (const float *) (ro + XBM * 32);
         const half8 au = *(const half8 *) (ro + (32 * rw + r) * 32 + 16 * h);
@@ -811,17 +721,7 @@ __global__ __launch_bounds__(768, 1) void k_mmqw(mi_mmx_group g) {
             }
         }
         cfold_vec_park(gsum, y, tv, f32x16(da), sb, gs, S, park);
-        stamp(4 + 4 * sb);
         mi_lds_barrier();
-        stamp(5 + 4 * sb);
-    }
-    rstamp(1);
-    if constexpr ((ABL & 8) != 0) {
-        float t = 0.0f;
-#pragma unroll
-        for (int i2 = 0; i2 < 16; i2++) t += y[i2];
-        if (t == 1.2345e-30f) dst[4096 + threadIdx.x] = t;
-        return;
     }
     if (cfold_split(S) < S) {  // cfold_end: the parked low half + the high half
         f32x16 lo = {};
@@ -832,13 +732,12 @@ __global__ __launch_bounds__(768, 1) void k_mmqw(mi_mmx_group g) {
 }
 
 // ---- short prompts, pipelined: 8 waves per tile, one superblock group each -----------------------
-// A workgroup computes one tile of 32 weight rows x 32 NC prompt columns; wave w computes the terms
+// A workgroup computes one tile of 32 weight rows x 32 prompt columns; wave w computes the terms
 // of superblock group w of the canonical order (cfold: kCfoldGroups = 8 contiguous groups) one
 // superblock after the other and left-folds them in registers. The weights of the next superblock
 // are requested before the current one's MFMAs (register double buffer); each 32-deep activation
 // fragment of the next superblock is requested into the register its step has just consumed. The
-// 8 group sums meet in LDS and are folded by the whole workgroup. With NC = 2 a wave's dequantized
-// weight planes feed two column tiles (half the dequantization VALU per MFMA).
+// 8 group sums meet in LDS and are folded by the whole workgroup.
 // VALU economy: the plane factors of all 8 sub-blocks come from 2 SWAR extractions of the header's
 // scale bytes (one bit-field extract per factor), loads advance by a wave-uniform SGPR offset (no
 // per-load address VALU), and the activation scales travel as one float per lane through a
@@ -847,19 +746,19 @@ __global__ __launch_bounds__(768, 1) void k_mmqw(mi_mmx_group g) {
 // dequantized weight planes (accumulator column = the lane's own weight row r).
 // NW = 4: two workgroups per CU (<= 256 VGPRs at two waves per SIMD), each wave computing groups
 // w and w + 4 one after the other (each group's sum goes to LDS when it ends).
-// RING: weight register buffers; superblock k + RING - 1's weights are requested when step k starts.
-// r03v counters (RING 2, B = 32, 16 members): waves wait ~45 % of their cycles (SQ_WAIT_INST_ANY),
-// MFMA 9 % busy, 18 VALU per MFMA. RING 4 measured slower (r03w): the activation fragments of step
-// k + 1 are requested after those weights, and vmcnt retires in order.
-template <int TYPE, int NC, int NW, int ABL = 0, int RING = 4>
+// Two weight register buffers: superblock k + 1's weights are requested when step k starts.
+// r03v counters (B = 32, 16 members): waves wait ~45 % of their cycles (SQ_WAIT_INST_ANY),
+// MFMA 9 % busy, 18 VALU per MFMA. A ring of 4 measured slower (r03w): the activation fragments of
+// step k + 1 are requested after those weights, and vmcnt retires in order.
+template <int TYPE, int NW>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mmqp(mi_mmx_group grp) {
     MI_MMX_MEMBER(grp);
     using F = XFmt<TYPE>;
     constexpr int NP = F::NP;
-    constexpr int NE = 16 * NC;  // accumulator elements per lane
+    constexpr int NE = 16;  // accumulator elements per lane
     constexpr int NG = kCfoldGroups / NW;  // groups per wave
     __shared__ __attribute__((aligned(16))) float red[kCfoldGroups * NE * 64];  // [group][el][lane] group sums
-    __shared__ __attribute__((aligned(16))) float dal[NW][32 * NC];              // per-wave da row
+    __shared__ __attribute__((aligned(16))) float dal[NW][32];             // per-wave da row
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);
     const int r = lane & 31, h = lane >> 5;
@@ -882,7 +781,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mmqp(mi_mmx_group 
         return S - 1;
     };
     const int64_t nrt = (N + 31) / 32;
-    const int64_t n0 = (mmx_tile % nrt) * 32, c0 = (mmx_tile / nrt) * (32 * NC);
+    const int64_t n0 = (mmx_tile % nrt) * 32, c0 = (mmx_tile / nrt) * 32;
 
     const int nrows = (int) std::min<int64_t>(32, N - n0);
     const __amdgpu_buffer_rsrc_t wres = __builtin_amdgcn_make_buffer_rsrc((void *) (W + n0 * nb01), (short) 0, (int) (nrows * nb01), 0x00020000);
@@ -892,9 +791,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mmqp(mi_mmx_group 
     constexpr uint32_t kQs = F::Q5 ? 48 : 16;
     // lane-constant parts of every offset; the superblock / step advance is an SGPR
     const uint32_t wv = (uint32_t) (min(r, nrows - 1) * nb01);
-    uint32_t acol[NC];
-#pragma unroll
-    for (int t = 0; t < NC; t++) acol[t] = (uint32_t) std::min<int64_t>(c0 + 32 * t + r, ncols - 1);
+    const uint32_t acol = (uint32_t) std::min<int64_t>(c0 + r, ncols - 1);
     const uint32_t xstep = (uint32_t) ncols * 32;
 
     auto ld = [](__amdgpu_buffer_rsrc_t res, uint32_t voff, uint32_t soff) -> uint4 {
@@ -910,51 +807,43 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mmqp(mi_mmx_group 
         for (int p = 0; p < 4; p++) o.q4[p] = ld(wres, wv + kQs + 32 * p + 16 * h, so);
         if constexpr (F::Q5) o.qh = ld(wres, wv + 16 + 16 * h, so);
     };
-    auto ld_x = [&](int sb, int kk, int t) -> i32x4 {
+    auto ld_x = [&](int sb, int kk) -> i32x4 {
         const uint32_t so = (uint32_t) __builtin_amdgcn_readfirstlane((sb * 8 + kk) * (int) xstep);
-        return __builtin_bit_cast(i32x4, ld(xres, acol[t] * 32 + 16 * h, so));
+        return __builtin_bit_cast(i32x4, ld(xres, acol * 32 + 16 * h, so));
     };
-    auto ld_u = [&](int sb, int t) -> half8 {
+    auto ld_u = [&](int sb) -> half8 {
         const uint32_t so = (uint32_t) __builtin_amdgcn_readfirstlane(sb * (int) ncols * 32);
-        return __builtin_bit_cast(half8, ld(ures, acol[t] * 32 + 16 * h, so));
+        return __builtin_bit_cast(half8, ld(ures, acol * 32 + 16 * h, so));
     };
-    auto ld_d = [&](int sb, int t) -> float {
+    auto ld_d = [&](int sb) -> float {
         const uint32_t so = (uint32_t) __builtin_amdgcn_readfirstlane(sb * (int) ncols * 4);
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dres, acol[t] * 4, so, 0));
+        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dres, acol * 4, so, 0));
     };
 
-    f32x16 gsum[NC];
-#pragma unroll
-    for (int t = 0; t < NC; t++) gsum[t] = f32x16{};
+    f32x16 gsum = {};
     if (nsb > 0) {
-        Wt wt[RING];
-        i32x4 xa[NC][8];
-        half8 xu[NC];
-        float da[NC];
+        Wt wt[2];
+        i32x4 xa[8];
         const int sbf = sb_at(0);
+        load_w(wt[0], sbf);
 #pragma unroll
-        for (int u = 0; u < RING - 1; u++) load_w(wt[u], sb_at(u));
-#pragma unroll
-        for (int t = 0; t < NC; t++) {
-#pragma unroll
-            for (int kk = 0; kk < 8; kk++) xa[t][kk] = ld_x(sbf, kk, t);
-            xu[t] = ld_u(sbf, t);
-            da[t] = ld_d(sbf, t);
-        }
-        // the wave's k-th superblock: `cur` holds its weights; superblock k + RING - 1's weights go
-        // into `nxt` (the buffer the previous step consumed), the next superblock's activations are
+        for (int kk = 0; kk < 8; kk++) xa[kk] = ld_x(sbf, kk);
+        half8 xu = ld_u(sbf);
+        float da = ld_d(sbf);
+        // the wave's k-th superblock: `cur` holds its weights; superblock k + 1's weights go into
+        // `nxt` (the buffer the previous step consumed), the next superblock's activations are
         // requested step by step as their registers free up
         auto step = [&](const Wt & cur, Wt & nxt, const int k) {
             const int sb = sb_at(k);
             const int sn = sb_at(k + 1);  // clamped: a past-the-end prefetch re-reads the last one
             const bool first = sb % gs == 0, last = sb % gs == gs - 1 || sb == S - 1;
-            load_w(nxt, sb_at(k + RING - 1));
+            load_w(nxt, sn);
             const uint32_t w0 = cur.hdr.y, w1 = cur.hdr.z, w2 = cur.hdr.w;
             // the 6-bit scales of sub-blocks 0..3 / 4..7 as bytes (get_scale_min_k4)
             const uint32_t sca = w0 & 0x3F3F3F3Fu;
             const uint32_t scb = (w2 & 0x0F0F0F0Fu) | ((w0 >> 2) & 0x30303030u);
             const float dw = mi_h2f((uint16_t) (cur.hdr.x & 0xFFFF)), dm = mi_h2f((uint16_t) (cur.hdr.x >> 16));
-            i32x16 acc[NC][NP];
+            i32x16 acc[NP];
             uint32_t lo[4], hi[4];
 #pragma unroll
             for (int kk = 0; kk < 8; kk++) {
@@ -982,14 +871,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mmqp(mi_mmx_group 
                     // plane factor: Q4_K sc = 8 hi3 + lo3; Q5_K sc = 16 f2 + 4 f1 + f0
                     const uint32_t f = __builtin_amdgcn_ubfe(scw, 8 * (kk & 3) + (F::Q5 ? 2 * p : 3 * p), F::Q5 ? 2 : 3);
                     const i32x4 b = {(int) mulb(v[0], f), (int) mulb(v[1], f), (int) mulb(v[2], f), (int) mulb(v[3], f)};
-#pragma unroll
-                    for (int t = 0; t < NC; t++) {
-                        if constexpr ((ABL & 4) != 0) acc[t][p][kk] = (kk == 0 ? 0 : acc[t][p][kk]) + xa[t][kk][0] * b[0];
-                        else acc[t][p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[t][kk], b, kk == 0 ? i32x16{} : acc[t][p], 0, 0, 0);
-                    }
+                    acc[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[kk], b, kk == 0 ? i32x16{} : acc[p], 0, 0, 0);
                 }
-#pragma unroll
-                for (int t = 0; t < NC; t++) xa[t][kk] = ld_x(sn, kk, t);
+                xa[kk] = ld_x(sn, kk);
             }
             // U on the f16 MFMA: A = [S & 63, S >> 6] of the lane's column, B = [m, 64 m] of its row
             const uint32_t ma = w1 & 0x3F3F3F3Fu;
@@ -1003,66 +887,56 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mmqp(mi_mmx_group 
                 mu[2 * q + 1] = (_Float16) (float) (64 * m);
             }
             // the activation scales of the tile's columns, redistributed through this wave's LDS row
-            if (h == 0) {
-#pragma unroll
-                for (int t = 0; t < NC; t++) dal[w][32 * t + r] = da[t];
-            }
+            if (h == 0) dal[w][r] = da;
             __builtin_amdgcn_wave_barrier();
             __atomic_signal_fence(__ATOMIC_SEQ_CST);
             if (first) {  // uniform: a group starts at -0 (-0 + t == t), kept a branch (no selects)
                 asm volatile("" ::: "memory");
-#pragma unroll
-                for (int t = 0; t < NC; t++) gsum[t] = f32x16(-0.0f);
+                gsum = f32x16(-0.0f);
             }
+            const f32x16 Uv = __builtin_amdgcn_mfma_f32_32x32x16_f16(xu, mu, f32x16{}, 0, 0, 0);
+            xu = ld_u(sn);
+            da = ld_d(sn);
 #pragma unroll
-            for (int t = 0; t < NC; t++) {
-                const f32x16 Uv = __builtin_amdgcn_mfma_f32_32x32x16_f16(xu[t], mu, f32x16{}, 0, 0, 0);
-                xu[t] = ld_u(sn, t);
-                da[t] = ld_d(sn, t);
+            for (int g = 0; g < 4; g++) {
+                const float4 d4 = *(const float4 *) &dal[w][8 * g + 4 * h];
+                const float dav[4] = {d4.x, d4.y, d4.z, d4.w};
 #pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const float4 d4 = *(const float4 *) &dal[w][32 * t + 8 * g + 4 * h];
-                    const float dav[4] = {d4.x, d4.y, d4.z, d4.w};
+                for (int e = 0; e < 4; e++) {
+                    const int el = 4 * g + e;
+                    int T = acc[NP - 1][el];
 #pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const int el = 4 * g + e;
-                        int T = acc[t][NP - 1][el];
-#pragma unroll
-                        for (int p = NP - 2; p >= 0; p--) T = (T << F::SHIFT) + acc[t][p][el];
-                        gsum[t][el] = __builtin_fmaf(dav[e], mmqx_pre(T, Uv[el], dw, dm), gsum[t][el]);
-                    }
+                    for (int p = NP - 2; p >= 0; p--) T = (T << F::SHIFT) + acc[p][el];
+                    gsum[el] = __builtin_fmaf(dav[e], mmqx_pre(T, Uv[el], dw, dm), gsum[el]);
                 }
             }
             if (last) {  // the group's sum -> LDS slot of group sb / gs
                 const int grp_i = sb / gs;
 #pragma unroll
-                for (int t = 0; t < NC; t++)
-#pragma unroll
-                    for (int el = 0; el < 16; el++) red[(grp_i * NE + 16 * t + el) * 64 + lane] = gsum[t][el];
+                for (int el = 0; el < 16; el++) red[(grp_i * NE + el) * 64 + lane] = gsum[el];
             }
             __builtin_amdgcn_wave_barrier();  // the LDS row is rewritten by the next superblock
             __atomic_signal_fence(__ATOMIC_SEQ_CST);
         };
-        for (int k = 0; k < nsb; k += RING) {
+        for (int k = 0; k < nsb; k += 2) {
 #pragma unroll
-            for (int u = 0; u < RING; u++) {
+            for (int u = 0; u < 2; u++) {
                 if (k + u >= nsb) break;
-                step(wt[u], wt[(u + RING - 1) % RING], k + u);
+                step(wt[u], wt[u ^ 1], k + u);
             }
         }
     }
     mi_lds_barrier();
     // the group sums folded (canonical order) by the whole workgroup: output o = el 64 + l
-    // (el: accumulator element of tile el / 16, l: lane) -- lanes 0..31 store 32 consecutive rows
+    // (el: accumulator element, l: lane) -- lanes 0..31 store 32 consecutive rows
     const int ngroups = (S + gs - 1) / gs;
 #pragma unroll
     for (int i = 0; i < NE / NW; i++) {
         const int o = (int) threadIdx.x + 64 * NW * i;
         const int el = o >> 6, l = o & 63;
         const float y = cfold_groups(ngroups, [&](int v) { return red[(v * NE + el) * 64 + l]; });
-        const int e = el & 15, t = el >> 4;
         const int64_t n = n0 + (l & 31);
-        const int64_t c = c0 + 32 * t + (e & 3) + 8 * (e >> 2) + 4 * (l >> 5);
+        const int64_t c = c0 + (el & 3) + 8 * (el >> 2) + 4 * (l >> 5);
         if (n < N && c < ncols) *(float *) ((char *) dst + c * ycol + n * sizeof(float)) = y;
     }
 }
@@ -1089,25 +963,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mmqp(mi_mmx_group 
 // Per superblock and wave: 34 MFMAs (2 tiles x (2 planes x 8 steps + 1 U)) for one dequantization.
 // (LDS-DMA helpers mi_glds16 / mi_glds4 / mi_lds_addr: mmq_exact_common.h)
 
-// ABL (diagnostic builds only, results invalid): 8 s_memtime stamps of waves 0 and 4 of workgroups 0
-// and 97 into dst as uint64 [2][2][80] (0 start, 1 after the prologue, 2 + 4 u + {0 step start, 1
-// after the MFMA steps, 2 after the combine, 3 after the DMA wait}); 1 no weight DMAs after the
-// prologue, 2 no combine, 4 no DMAs at all after the prologue (profiles/r04l_mmqt_stamps.txt).
-// HS (round 6): the two K halves synchronize separately. Each half's 36 pieces are issued by its own
-// four waves (9 each, as before) and the stage barrier is a per-half LDS counter (arrive after the
-// wave's DMAs and LDS reads have completed, spin until the half's four waves have arrived) instead of
-// the workgroup's s_barrier, so waves w and w + 4 -- the two waves of one SIMD, one of each half --
-// are no longer held in lock step: one half's combine (VALU) can run under the other half's MFMAs.
-// The halves have equal stage counts and meet at a full barrier before the final lo + hi.
-// ST (round 6, diagnostic builds: measured 3-9 % slower than the lock-step form at B = 64..512,
-// profiles/r06s2h_mmqt_stagger_ab.txt): a stagger of the two waves of a SIMD (MI355X_MICROARCH.md, "Two waves per SIMD",
-// item 9): the high half (waves 4-7) defers each stage's combine into the next stage, ahead of that
-// stage's MFMAs -- so while waves 0-3 issue their MFMAs their partner wave runs the previous
-// combine, and the other way round. The deferred combine's LDS operands (the weight header, the U
-// fragments, d_a) are copied to registers before the stage barrier (the next DMAs overwrite that
-// buffer); the accumulators stay live until the combine. Same operations in the same order per
-// element: bit-identical.
-template <int TYPE, int ABL = 0, bool HS = false, bool ST = false>
+template <int TYPE>
 __global__ __launch_bounds__(512, 1) void k_mmqt(mi_mmx_group grp) {
     MI_MMX_MEMBER(grp);
     using F = XFmt<TYPE>;
@@ -1125,10 +981,6 @@ __global__ __launch_bounds__(512, 1) void k_mmqt(mi_mmx_group grp) {
     constexpr int NI = 2 * NPIECE / 8;        // pieces per wave and stage (9)
     constexpr int SINK = 2 * SB;              // d_a DMAs of waves 2-7 land here
     __shared__ __attribute__((aligned(16))) char lds[SINK + DB];
-    __shared__ uint32_t hbar[2];              // HS: per-half arrival counters
-    constexpr int kDefB = UB + DB + BM * 16;  // ST: the high half's deferred combine operands, per area
-    static_assert(!ST || UB + DB == 2304, "deferred-area offsets");
-    __shared__ __attribute__((aligned(16))) char ldef[ST ? 2 * kDefB : 16];
 
     const int tid = (int) threadIdx.x;
     const int lane = tid & 63;
@@ -1151,7 +1003,7 @@ __global__ __launch_bounds__(512, 1) void k_mmqt(mi_mmx_group grp) {
 #pragma unroll
     for (int i = 0; i < NI; i++) {
         const int q = w + 8 * i;
-        const int hf = HS ? kh : q / NPIECE, t = HS ? (w & 3) + 4 * i : q % NPIECE;
+        const int hf = q / NPIECE, t = q % NPIECE;
         pdst[i] = (uint32_t) (hf * HB + 1024 * t);
         if (t < 16) {  // activation quants: step kk, 32-column group cg
             const int kk = t >> 1, cg = t & 1, col = 32 * cg + (lane >> 1);
@@ -1176,19 +1028,12 @@ __global__ __launch_bounds__(512, 1) void k_mmqt(mi_mmx_group grp) {
     // Piece i < NI; i == NI: d_a (wave 0 the low half's, wave 1 the high half's, the others into the
     // sink).
     auto stage_piece = [&](int u, int i) {
-        if constexpr ((ABL & 4) != 0) if (u > 0) return;
-        if constexpr ((ABL & 1) != 0) if (u > 0 && i < NI && (w + 8 * i) % NPIECE >= 18) return;
         char * sbuf = lds + (u & 1) * SB;
         if (i < NI) {
-            const int hf = HS ? kh : (w + 8 * i) / NPIECE;
+            const int hf = (w + 8 * i) / NPIECE;
             const int sb = std::min(hf ? SK + u : u, S - 1);
             const char * src = pbase[i] + (size_t) sb * pstride[i] + poff[i];
             mi_glds16(src, mi_lds_addr(sbuf + pdst[i]));
-        } else if constexpr (HS) {  // wave 0 of each half its d_a, the others into the sink
-            const int sb = std::min(kh ? SK + u : u, S - 1);
-            const char * src = (const char *) act.xd + (size_t) sb * ncols * 4 + doff;
-            char * dd = (w & 3) ? lds + SINK : sbuf + kh * HB + XB + UB + WB;
-            mi_glds4(src, mi_lds_addr(dd));
         } else {
             const int sb = std::min(w == 1 ? SK + u : u, S - 1);
             const char * src = (const char *) act.xd + (size_t) sb * ncols * 4 + doff;
@@ -1200,34 +1045,10 @@ __global__ __launch_bounds__(512, 1) void k_mmqt(mi_mmx_group grp) {
 #pragma unroll
         for (int i = 0; i <= NI; i++) stage_piece(u, i);
     };
-    auto stamp = [&](int slot) {
-        if constexpr ((ABL & 8) != 0) {
-            const int wsel = blockIdx.x == 0 ? 0 : blockIdx.x == 97 ? 1 : -1;
-            if (wsel >= 0 && (w & 3) == 0 && lane == 0 && slot < 80)
-                ((uint64_t *) dst)[(wsel * 2 + (w >> 2)) * 80 + slot] = __builtin_amdgcn_s_memtime();
-        }
-    };
-    int stamp_slot = 0;
     auto stage_wait = [&] {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        stamp(stamp_slot);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     };
-    // HS: the half's barrier for the stage-u wait (u >= 1: the 4 u-th arrival of the half's waves)
-    auto half_wait = [&](int u) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        stamp(stamp_slot);
-        if (lane == 0) __hip_atomic_fetch_add(&hbar[kh], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        const uint32_t target = 4u * (uint32_t) u;
-        // (bounded: every wave arrives once per stage, so the bound is never reached; it only keeps
-        // a fault from hanging the device)
-        for (int spin = 0; spin < (1 << 24) && __hip_atomic_load(&hbar[kh], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < target; spin++)
-            __builtin_amdgcn_s_sleep(0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    };
-    if constexpr (HS) {
-        if (tid < 2) hbar[tid] = 0;  // (ordered before any arrival by the prologue's full barrier)
-    }
 
     // ---- compute: rows n0 + 32 rw + r of half kh; tiles ct = columns 32 ct ..
     const uint32_t xoff0 = (uint32_t) (r * 32 + 16 * (h ^ ((r >> 4) & 1)));  // tile 0; tile 1 at + 1024
@@ -1279,10 +1100,6 @@ __global__ __launch_bounds__(512, 1) void k_mmqt(mi_mmx_group grp) {
     // column from xup, B = [m, 64 m] of its row from the header at hdrp), then mmqx_pre per element
     // (d_a from dal), folded into this half's sum
     auto combine = [&](const char * hdrp, const char * xup, const float * dal, int sb) {
-        if constexpr ((ABL & 2) != 0) {  // timing ablation: no combine (keep the accumulators alive)
-            if (acc[0][0][0] == 0x7fffffff && acc[1][1][5] == 0x7fffffff) y[0][0] += 1.0f;
-            return;
-        }
         const uint4 hdr = *(const uint4 *) hdrp;
         const float dw = mi_h2f((uint16_t) (hdr.x & 0xFFFF)), dm = mi_h2f((uint16_t) (hdr.x >> 16));
         const uint32_t ma = hdr.z & 0x3F3F3F3Fu;
@@ -1335,51 +1152,9 @@ __global__ __launch_bounds__(512, 1) void k_mmqt(mi_mmx_group grp) {
         combine(lds + buf * SB + woff, hb + XB + xoff0, (const float *) (hb + XB + UB + WB), sb);
     };
     const int sb0 = kh ? SK : 0;
-    stamp(0);
     stage_dma(0);
-    stamp_slot = 1;
     stage_wait();
-    if constexpr (ST) {
-        // the deferred combine's operands of stage u, copied by waves 4-7 into area u & 1 behind their
-        // MFMAs: [U halves 2 KB | d_a 256 B | the 128 rows' headers 2 KB] (the stage buffer itself is
-        // refilled by the next stage's DMAs)
-        auto def_area = [&](int u) { return ldef + (u & 1) * kDefB; };
-        for (int u = 0; u < SK; u++) {
-            auto dma_hook = [&](int kk) {
-                if (kk < 7) {
-                    stage_piece(u + 1, kk);
-                } else {
-#pragma unroll
-                    for (int i = 7; i <= NI; i++) stage_piece(u + 1, i);
-                }
-            };
-            if (kh && u > 0) {  // the previous stage's combine, under waves 0-3's MFMAs
-                const char * d = def_area(u - 1);
-                combine(d + 2304 + (32 * rw + r) * 16, d + xoff0, (const float *) (d + 2048), sb0 + u - 1);
-            }
-            mfma(u & 1, dma_hook);
-            if (kh) {
-                const char * hb = lds + (u & 1) * SB + HB;  // (the high half's stage image)
-                char * d = def_area(u);
-                if (lane < 32) {
-                    *(uint4 *) (d + 2304 + (32 * rw + lane) * 16) = *(const uint4 *) (hb + XB + UB + (32 * rw + lane) * F::BS);
-                    if (lane < 4) *(uint4 *) (d + 2048 + 64 * rw + 16 * lane) = *(const uint4 *) (hb + XB + UB + WB + 64 * rw + 16 * lane);
-                } else {
-                    *(uint4 *) (d + 512 * rw + 16 * (lane - 32)) = *(const uint4 *) (hb + XB + 512 * rw + 16 * (lane - 32));
-                }
-            } else {
-                combine_stage(u & 1, sb0 + u);
-            }
-            stage_wait();
-        }
-        if (kh && SK > 0) {
-            const char * d = def_area(SK - 1);
-            combine(d + 2304 + (32 * rw + r) * 16, d + xoff0, (const float *) (d + 2048), sb0 + SK - 1);
-        }
-    } else
     for (int u = 0; u < SK; u++) {
-        stamp(2 + 4 * u);
-        stamp_slot = 5 + 4 * u;
         // the next stage's DMAs (past the end: clamped re-reads into the idle buffer), one piece
         // behind each 32-deep step's MFMAs, the rest after the last
         auto dma_hook = [&](int kk) {
@@ -1391,24 +1166,13 @@ __global__ __launch_bounds__(512, 1) void k_mmqt(mi_mmx_group grp) {
             }
         };
         mfma(u & 1, dma_hook);
-        stamp(3 + 4 * u);
         combine_stage(u & 1, sb0 + u);
-        stamp(4 + 4 * u);
-        if constexpr (HS) half_wait(u + 1);
-        else stage_wait();
-    }
-    if constexpr ((ABL & 8) != 0) {  // dst holds the stamps; keep the results alive
-        float t = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; i++) t += y[0][i] + y[1][i];
-        if (t == 1.2345e-30f) dst[8192 + threadIdx.x] = t;
-        return;
+        stage_wait();
     }
 
     // the halves meet: waves 4-7 leave their sums in LDS (the stage buffers are idle: every DMA
     // has landed and every wave has passed the last barrier), waves 0-3 add and store
     f32x16 * ex = (f32x16 *) lds;
-    if constexpr (HS) mi_lds_barrier();  // the halves drift: both done with the stage buffers
     if (kh) {
         ex[(rw * 2 + 0) * 64 + lane] = y[0];
         ex[(rw * 2 + 1) * 64 + lane] = y[1];
@@ -1420,253 +1184,6 @@ __global__ __launch_bounds__(512, 1) void k_mmqt(mi_mmx_group grp) {
 #pragma unroll
     for (int ct = 0; ct < 2; ct++) {
         const f32x16 yv = y[ct] + ex[(rw * 2 + ct) * 64 + lane];  // cfold_end: lo + hi
-        // element el: prompt column c0 + 32 ct + (el & 3) + 8 (el >> 2) + 4 h
-#pragma unroll
-        for (int el = 0; el < 16; el++) {
-            const int64_t c = c0 + 32 * ct + (el & 3) + 8 * (el >> 2) + 4 * h;
-            if (c < ncols) *(float *) ((char *) dst + c * ycol + n * sizeof(float)) = yv[el];
-        }
-    }
-}
-
-// ---- long prompts, one wave per SIMD, software-pipelined: k_mmqv (round 6) --------------------------
-// k_mmqt's phases run in lock step per stage: every wave issues its MFMAs, then its combine (VALU),
-// and the two waves of a SIMD do so together (stamps: MFMA steps ~2500-3200 cycles, combine ~1800,
-// barrier ~1200 per stage, profiles/r04l_mmqt_stamps.txt; synchronizing the halves separately did not
-// separate them, profiles/r06d_mmqt_stamps.txt). Here one wave per SIMD (4 waves, 128 rows x 64
-// columns, each wave 32 rows x 64 columns over the WHOLE K) overlaps the two inside itself: the
-// combine of superblock s - 1 (T = (P1 << 3) + P0, t = fma(-dmin_w, U, d_w T): 4 VALU per element, no
-// branches) is issued between the MFMAs of superblock s, so the MFMA pipe hides the VALU latency
-// chains; only the group fold (cfold_vec: g = fma(d_a, t, g), group ends) runs on its own. Stage =
-// one superblock: activation quants [8][64][32] (swizzled halves), U halves, the 128 rows' raw
-// blocks, d_a (k_mmqt's half-stage image, 36.4 KB) by LDS-DMA, 4 buffers, issued two stages ahead (9
-// one-KB pieces + one d_a DMA per wave and stage: s_waitcnt vmcnt(10) leaves the next stage in
-// flight). Same operands, same canonical combine: bit-identical to every kernel of the family.
-template <int TYPE>
-__global__ __launch_bounds__(256, 1) void k_mmqv(mi_mmx_group grp) {
-    MI_MMX_MEMBER(grp);
-    using F = XFmt<TYPE>;
-    static_assert(!F::Q5, "Q4_K only");
-    constexpr int NP = F::NP;
-    constexpr int BM = 128, BN = 64;
-    constexpr int XB = 8 * BN * 32;           // activation quants of one superblock
-    constexpr int UB = BN * 32;               // U halves
-    constexpr int WB = BM * F::BS;            // raw weight blocks
-    constexpr int DB = BN * 4;                // d_a
-    constexpr int HB = XB + UB + WB + DB;     // a stage: [X | U | W | d_a]
-    constexpr int NBUF = 4;
-    constexpr int NPIECE = (XB + UB + WB) / 1024;  // 36
-    constexpr int NI = NPIECE / 4;            // 9 per wave
-    static_assert(NPIECE % 4 == 0, "pieces evenly dealt");
-    constexpr int SINK = NBUF * HB;
-    __shared__ __attribute__((aligned(16))) char lds[SINK + DB];
-
-    const int tid = (int) threadIdx.x;
-    const int lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    const int64_t ncols = act.ncols;
-    const int S = (int) (K / 256);
-    const int gs = cfold_gs(S);
-    const int64_t nrt = (N + BM - 1) / BM;
-    const int64_t n0 = (mmx_tile % nrt) * BM, c0 = (mmx_tile / nrt) * BN;
-    const int nrows = (int) std::min<int64_t>(BM, N - n0);
-    auto col_of = [&](int c) { return (uint32_t) std::min<int64_t>(c0 + c, ncols - 1); };
-
-    const char * pbase[NI];
-    uint32_t pstride[NI], poff[NI], pdst[NI];
-#pragma unroll
-    for (int i = 0; i < NI; i++) {
-        const int t = w + 4 * i;
-        pdst[i] = (uint32_t) (1024 * t);
-        if (t < 16) {  // activation quants: step kk, 32-column group cg
-            const int kk = t >> 1, cg = t & 1, col = 32 * cg + (lane >> 1);
-            pbase[i] = (const char *) act.xq + (size_t) kk * ncols * 32;
-            pstride[i] = 8 * (uint32_t) ncols * 32;
-            poff[i] = col_of(col) * 32 + 16 * ((lane & 1) ^ ((lane >> 5) & 1));
-        } else if (t < 18) {  // U halves
-            const int col = 32 * (t - 16) + (lane >> 1);
-            pbase[i] = (const char *) act.xu;
-            pstride[i] = (uint32_t) ncols * 32;
-            poff[i] = col_of(col) * 32 + 16 * ((lane & 1) ^ ((lane >> 5) & 1));
-        } else {  // raw weight blocks: 1 KB of the [128 rows][BS] image
-            const int o = 1024 * (t - 18) + 16 * lane, row = o / F::BS;
-            pbase[i] = (const char *) W + (size_t) n0 * nb01;
-            pstride[i] = F::BS;
-            poff[i] = (uint32_t) (std::min(row, nrows - 1) * nb01 + o % F::BS);
-        }
-    }
-    const uint32_t doff = col_of(lane) * 4;
-    // stage u (clamped: past the end re-reads the last superblock into an idle buffer) into buffer u % 4
-    auto stage_piece = [&](int u, int i) {
-        char * sbuf = lds + (u % NBUF) * HB;
-        const int sb = std::min(u, S - 1);
-        if (i < NI) {
-            mi_glds16(pbase[i] + (size_t) sb * pstride[i] + poff[i], mi_lds_addr(sbuf + pdst[i]));
-        } else {
-            const char * src = (const char *) act.xd + (size_t) sb * ncols * 4 + doff;
-            mi_glds4(src, mi_lds_addr(w ? lds + SINK : sbuf + XB + UB + WB));
-        }
-    };
-
-    const uint32_t xoff0 = (uint32_t) (r * 32 + 16 * (h ^ ((r >> 4) & 1)));  // tile 0; tile 1 at + 1024
-    const uint32_t woff = (uint32_t) (XB + UB + (32 * w + r) * F::BS);
-    f32x16 g[2] = {}, y[2] = {f32x16(-0.0f), f32x16(-0.0f)}, lo[2] = {f32x16(-0.0f), f32x16(-0.0f)};
-    i32x16 accA[2][NP], accB[2][NP];
-
-    // U of superblock sb (its stage buffer) on the f16 MFMA (A = [S & 63, S >> 6] of the lane's
-    // column, B = [m, 64 m] of its row); returns d_w, dmin_w of the row
-    auto u_of = [&](int sb, f32x16 (&Uo)[2]) {
-        const char * base = lds + (sb % NBUF) * HB;
-        const uint4 hdr = *(const uint4 *) (base + woff);
-        const uint32_t ma = hdr.z & 0x3F3F3F3Fu;
-        const uint32_t mb = ((hdr.w >> 4) & 0x0F0F0F0Fu) | ((hdr.z >> 2) & 0x30303030u);
-        const uint32_t mw = h ? mb : ma;
-        half8 mu;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint32_t m = (mw >> (8 * q)) & 0xFF;
-            mu[2 * q] = (_Float16) (float) m;
-            mu[2 * q + 1] = (_Float16) (float) (64 * m);
-        }
-#pragma unroll
-        for (int ct = 0; ct < 2; ct++) {
-            const half8 xu = *(const half8 *) (base + XB + xoff0 + 1024 * ct);
-            Uo[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xu, mu, f32x16{}, 0, 0, 0);
-        }
-        return std::make_pair(mi_h2f((uint16_t) (hdr.x & 0xFFFF)), mi_h2f((uint16_t) (hdr.x >> 16)));
-    };
-
-    // superblock u: its MFMAs into acc; the previous superblock's t values (accp; when `pre`)
-    // computed between the MFMA steps into tv; the stage two ahead's DMAs behind the steps
-    auto body = [&](auto pre_c, int u, i32x16 (&acc)[2][NP], const i32x16 (&accp)[2][NP], f32x16 (&tv)[2]) {
-        constexpr bool pre = decltype(pre_c)::value;
-        const char * base = lds + (u % NBUF) * HB;
-        const char * wr = base + woff;
-        f32x16 Up[2];
-        float dwp = 0.0f, dmp = 0.0f;
-        if constexpr (pre) {
-            const auto dd = u_of(u - 1, Up);
-            dwp = dd.first;
-            dmp = dd.second;
-        }
-        const uint4 hdr = *(const uint4 *) wr;
-        uint4 q4[4];
-#pragma unroll
-        for (int p = 0; p < 4; p++) q4[p] = *(const uint4 *) (wr + 16 + 32 * p + 16 * h);
-        const uint32_t w0 = hdr.y, w2 = hdr.w;
-        const uint32_t sca = w0 & 0x3F3F3F3Fu;
-        const uint32_t scb = (w2 & 0x0F0F0F0Fu) | ((w0 >> 2) & 0x30303030u);
-        uint32_t lq[4], hq[4];
-#pragma unroll
-        for (int kk = 0; kk < 8; kk++) {
-            const i32x4 xa0 = *(const i32x4 *) (base + kk * (BN * 32) + xoff0);
-            const i32x4 xa1 = *(const i32x4 *) (base + kk * (BN * 32) + 1024 + xoff0);
-            if ((kk & 1) == 0) {
-                const uint4 q = q4[kk >> 1];
-                const uint32_t qv[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    lq[e] = qv[e] & 0x0F0F0F0Fu;
-                    hq[e] = (qv[e] >> 4) & 0x0F0F0F0Fu;
-                }
-            }
-            const uint32_t scw = kk < 4 ? sca : scb;
-#pragma unroll
-            for (int p = 0; p < NP; p++) {
-                const uint32_t f = __builtin_amdgcn_ubfe(scw, 8 * (kk & 3) + 3 * p, 3);
-                const uint32_t * v = (kk & 1) ? hq : lq;
-                const i32x4 b = {(int) mulb(v[0], f), (int) mulb(v[1], f), (int) mulb(v[2], f), (int) mulb(v[3], f)};
-                acc[0][p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa0, b, kk == 0 ? i32x16{} : acc[0][p], 0, 0, 0);
-                acc[1][p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa1, b, kk == 0 ? i32x16{} : acc[1][p], 0, 0, 0);
-            }
-            // the previous superblock's values of elements 2 kk, 2 kk + 1 (both tiles)
-            if constexpr (pre) {
-#pragma unroll
-                for (int ct = 0; ct < 2; ct++) {
-#pragma unroll
-                    for (int e = 0; e < 2; e++) {
-                        const int el = 2 * kk + e;
-                        const int T = (accp[ct][1][el] << F::SHIFT) + accp[ct][0][el];
-                        tv[ct][el] = mmqx_pre(T, Up[ct][el], dwp, dmp);
-                    }
-                }
-            }
-            // the stage two ahead: one piece behind each step (steps 0..NI-1), the d_a DMA after the last
-            if (kk < NI) stage_piece(u + 2, kk);
-        }
-#pragma unroll
-        for (int i = 8; i <= NI; i++) stage_piece(u + 2, i);
-    };
-    // the last superblock's values (after its MFMAs, no next superblock to hide them under)
-    auto last_pre = [&](int sb, const i32x16 (&accp)[2][NP], f32x16 (&tv)[2]) {
-        f32x16 Up[2];
-        const auto dd = u_of(sb, Up);
-#pragma unroll
-        for (int ct = 0; ct < 2; ct++)
-#pragma unroll
-            for (int el = 0; el < 16; el++) {
-                const int T = (accp[ct][1][el] << F::SHIFT) + accp[ct][0][el];
-                tv[ct][el] = mmqx_pre(T, Up[ct][el], dd.first, dd.second);
-            }
-    };
-    // the fold of superblock sb's values tv (d_a from its stage buffer)
-    auto fold = [&](int sb, const f32x16 (&tv)[2]) {
-        const float * dal = (const float *) (lds + (sb % NBUF) * HB + XB + UB + WB);
-#pragma unroll
-        for (int ct = 0; ct < 2; ct++) {
-            f32x16 dv;
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const float2 d2 = *(const float2 *) &dal[32 * ct + 8 * (j >> 1) + 4 * h + 2 * (j & 1)];
-                dv[2 * j] = d2.x;
-                dv[2 * j + 1] = d2.y;
-            }
-            cfold_vec(g[ct], y[ct], lo[ct], tv[ct], dv, sb, gs, S);
-        }
-    };
-    auto stage_wait = [&] {
-        asm volatile("s_waitcnt vmcnt(10)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    };
-
-    // prologue: stages 0 and 1 in flight
-#pragma unroll
-    for (int i = 0; i <= NI; i++) stage_piece(0, i);
-#pragma unroll
-    for (int i = 0; i <= NI; i++) stage_piece(1, i);
-    f32x16 tv[2];
-    using no_pre = std::integral_constant<bool, false>;
-    using with_pre = std::integral_constant<bool, true>;
-    stage_wait();
-    body(no_pre{}, 0, accA, accB, tv);
-    if (S == 1) {
-        last_pre(0, accA, tv);
-        fold(0, tv);
-    }
-    for (int u = 1; u < S; u += 2) {
-        stage_wait();
-        body(with_pre{}, u, accB, accA, tv);
-        fold(u - 1, tv);
-        if (u + 1 >= S) {  // the last superblock from accB
-            last_pre(u, accB, tv);
-            fold(u, tv);
-            break;
-        }
-        stage_wait();
-        body(with_pre{}, u + 1, accA, accB, tv);
-        fold(u, tv);
-        if (u + 2 >= S) {  // the last superblock from accA
-            last_pre(u + 1, accA, tv);
-            fold(u + 1, tv);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the clamped DMAs past the end have landed)
-
-    const int64_t n = n0 + 32 * w + r;
-    if (n >= N) return;
-#pragma unroll
-    for (int ct = 0; ct < 2; ct++) {
-        const f32x16 yv = cfold_end_vec(lo[ct], y[ct]);
         // element el: prompt column c0 + 32 ct + (el & 3) + 8 (el >> 2) + 4 h
 #pragma unroll
         for (int el = 0; el < 16; el++) {
@@ -2104,10 +1621,7 @@ __global__ __launch_bounds__(64 * NWV, NR == 2 ? 2 : 1) void k_mmq0x(mi_mmx_grou
 // per SIMD at S = 16: <= 128 VGPRs, so the 16 da of a lane's accumulator elements go through a
 // wave-private LDS row instead of registers. Same operands, same exact T / U and the same
 // canonical fold (terms left-folded in superblock order) as k_mmqd / k_mmqx: bit-identical.
-// ABL (timing ablations, results invalid): 1 no MFMAs, 2 one activation load reused, 4 no fold,
-// 8 weight header only, 16 weight loads addressed as a wave-contiguous repacked layout ([chunk][row]
-// 16-byte chunks per 32-row x superblock tile: every load instruction one contiguous 1 KB)
-template <int TYPE, int ABL = 0>
+template <int TYPE>
 __global__ __launch_bounds__(1024) void k_mmqd1(mi_mmx_group g) {
     MI_MMX_MEMBER(g);
     using F = XFmt<TYPE>;
@@ -2134,21 +1648,14 @@ __global__ __launch_bounds__(1024) void k_mmqd1(mi_mmx_group g) {
 
     // every load of the wave, weights first (HBM), then the activation fragments (L2)
     auto ld_w = [&](uint32_t off) -> uint4 { return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(wres, wrow + off, 0, 0)); };
-    // ABL 16: the same loads at the offsets of a [chunk][row] repacked tile (chunk 0 = header,
-    // 1 + 2 p + h = quant chunk p, half h)
-    const uint32_t wtile = (uint32_t) sb * 32 * F::BS;
-    auto ld_wc = [&](int chunk) -> uint4 {
-        return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(wres, wtile + (uint32_t) (chunk * 32 + r) * 16, 0, 0));
-    };
-    const uint4 hdr = (ABL & 16) ? ld_wc(0) : ld_w(0);
+    const uint4 hdr = ld_w(0);
     uint4 q4[4];
 #pragma unroll
-    for (int p = 0; p < 4; p++) q4[p] = (ABL & 8) ? hdr : (ABL & 16) ? ld_wc(1 + 2 * p + h) : ld_w(kQs + 32 * p + 16 * h);
+    for (int p = 0; p < 4; p++) q4[p] = ld_w(kQs + 32 * p + 16 * h);
     const uint4 qh = F::Q5 ? ld_w(16 + 16 * h) : uint4{};
     i32x4 xa[8];
 #pragma unroll
-    for (int kk = 0; kk < 8; kk++)
-        xa[kk] = ((ABL & 2) && kk) ? xa[0] : __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(xres, xcol + kk * xstep, 0, 0));
+    for (int kk = 0; kk < 8; kk++) xa[kk] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(xres, xcol + kk * xstep, 0, 0));
     const half8 xu = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(ures, ((uint32_t) sb * (uint32_t) ncols + acol) * 32 + 16 * h, 0, 0));
     // da of prompt column c0 + r (lanes >= 32 duplicate), parked in this wave's LDS row: columns
     // past ncols read a clamped column's value (never stored)
@@ -2178,8 +1685,7 @@ __global__ __launch_bounds__(1024) void k_mmqd1(mi_mmx_group g) {
             uint32_t f = F::factor((int) sc, p);
             f |= f << 16;
             const i32x4 b = {(int) mulb(v[0], f), (int) mulb(v[1], f), (int) mulb(v[2], f), (int) mulb(v[3], f)};
-            if constexpr ((ABL & 1) != 0) acc[p][kk] = (kk == 0 ? 0 : acc[p][kk]) + xa[kk][0] * b[0];
-            else acc[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[kk], b, kk == 0 ? i32x16{} : acc[p], 0, 0, 0);
+            acc[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[kk], b, kk == 0 ? i32x16{} : acc[p], 0, 0, 0);
         }
     }
     half8 mu;
@@ -2221,9 +1727,8 @@ __global__ __launch_bounds__(1024) void k_mmqd1(mi_mmx_group g) {
         // d_a of superblock v for this output's column (the waves' da rows after the terms)
         const float * dsrc = red + (size_t) S * 64 * 16 + ((el & 3) + 8 * (el >> 2) + 4 * (lo >> 5));
         float y = -0.0f, ylo = -0.0f, gsum = 0.0f;
-        for (int v = 0; v < ((ABL & 4) ? 1 : S); v++) cfold(gsum, y, ylo, src[(size_t) v * 64 * 16], dsrc[v * 32], v, gs, S);
+        for (int v = 0; v < S; v++) cfold(gsum, y, ylo, src[(size_t) v * 64 * 16], dsrc[v * 32], v, gs, S);
         y = cfold_end(ylo, y);
-        if (ABL & 4) y = gsum;
         // element el of lane lo = prompt column c0 + (el & 3) + 8 (el >> 2) + 4 (lo >> 5), row n0 + lo % 32
         const int64_t n = n0 + (lo & 31);
         const int64_t c = c0 + (el & 3) + 8 * (el >> 2) + 4 * (lo >> 5);
@@ -2384,272 +1889,164 @@ static int64_t mmx_deal(mi_mmx_group & g, int64_t tr, int64_t tc) {
     return t;
 }
 
-void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
-    if (g.n <= 0) return;
-    const int type = g.type;
-    const int64_t K = g.K;
-    const int64_t ncols = g.m[0].act.ncols;  // every member has the same column count
-    if (type == 2 || type == 8) {  // Q4_0 / Q8_0: q8_0 activations (mi_act_mmx0_*), every column count
-        // By workgroup count: 64 x 128 tiles of 4 waves, each 64 rows x 32 columns (k_mmq0x NR = 2)
-        // when there are >= 256 of them; else 64 x 64 tiles of 4 waves (k_mmq0x half width) when
-        // >= 256 (Q8_0: 128); else 32 x 32 tiles of 4 waves on one tile (k_mmq0p). Variant bits force one: 16 k_mmq0p, 128 k_mmq0x (8 waves, 64 x 128), 128 |
-        // 65536 half width, 128 | 2^24 NR = 2, 128 | 2^25 NR = 2 with 8 waves (64 x 256). Every one
-        // keeps the family's canonical combine: the same bits.
-        const int var = g_mi_tuning.mmq_variant;
-        int pick;
-        if (var & 16) pick = 0;
-        else if (var & 128) pick = (var & (1 << 25)) ? 4 : (var & (1 << 24)) ? 3 : (var & 65536) ? 2 : 1;
-        else {
-            int64_t t2 = 0, th = 0;
-            for (int i = 0; i < g.n; i++) {
-                const int64_t rt = (g.m[i].N + XBM - 1) / XBM, nc = g.m[i].act.ncols;
-                t2 += rt * ((nc + 127) / 128);
-                th += rt * ((nc + 63) / 64);
-            }
-            // (k_mmq0p's Q8_0 operands -- five dword loads per block and lane -- make it the
-            // slower one for Q8_0 from 128 half-width tiles on)
-            pick = t2 >= 256 && ncols > 64 ? 3 : th >= (type == 8 ? 128 : 256) ? 2 : 0;
-        }
-        const bool q8 = type == 8;
-        switch (pick) {
-            case 0: {  // (a deeper weight ring, RING 3, spills: 36-dword units)
-                const dim3 grid((unsigned) mmx_deal(g, 32, 32));
-                if (!q8) hipLaunchKernelGGL((k_mmq0p<false>), grid, dim3(256), 0, s, g);
-                else hipLaunchKernelGGL((k_mmq0p<true>), grid, dim3(256), 0, s, g);
-                return;
-            }
-            case 1: {
-                const dim3 grid((unsigned) mmx_deal(g, XBM, XBN));
-                if (!q8) hipLaunchKernelGGL((k_mmq0x<false, 8, 4>), grid, dim3(512), 0, s, g);
-                else hipLaunchKernelGGL((k_mmq0x<true, 8, 4>), grid, dim3(512), 0, s, g);
-                return;
-            }
-            case 2: {
-                const dim3 grid((unsigned) mmx_deal(g, XBM, 64));
-                if (!q8) hipLaunchKernelGGL((k_mmq0x<false, 4, 2>), grid, dim3(256), 0, s, g);
-                else hipLaunchKernelGGL((k_mmq0x<true, 4, 2>), grid, dim3(256), 0, s, g);
-                return;
-            }
-            case 3: {
-                const dim3 grid((unsigned) mmx_deal(g, XBM, 128));
-                if (!q8) hipLaunchKernelGGL((k_mmq0x<false, 4, 2, 2>), grid, dim3(256), 0, s, g);
-                else hipLaunchKernelGGL((k_mmq0x<true, 4, 2, 2>), grid, dim3(256), 0, s, g);
-                return;
-            }
-            default: {
-                const dim3 grid((unsigned) mmx_deal(g, XBM, 256));
-                if (!q8) hipLaunchKernelGGL((k_mmq0x<false, 8, 2, 2>), grid, dim3(512), 0, s, g);
-                else hipLaunchKernelGGL((k_mmq0x<true, 8, 2, 2>), grid, dim3(512), 0, s, g);
-                return;
-            }
-        }
-    }
-    // short prompts (<= 128 columns): pipelined 32 x 32 tiles of 4 waves (k_mmqp; variant bit
-    // 2048: k_mmqd1, a wave per superblock) or, <= 16 columns, 16 x 16 tiles of a wave per
-    // superblock (k_mmqd16); long ones: 64 x 128 tiles with the weights dequantized once per
-    // workgroup into LDS (k_mmqx). All follow the same canonical combine order (cfold), so a
-    // prompt's column shards give the whole prompt's bits whichever kernel runs them (variant bit
-    // 128 forces k_mmqx, 16 the short-prompt kernels).
+// Q4_0 / Q8_0 (q8_0 activations, mi_act_mmx0_*), every column count. By workgroup count: 64 x 128
+// tiles of 4 waves, each 64 rows x 32 columns (k_mmq0x NR = 2) when there are >= 256 of them; else
+// 64 x 64 tiles of 4 waves (k_mmq0x half width) when >= 256 (Q8_0: 128); else 32 x 32 tiles of 4 waves
+// on one tile (k_mmq0p). Variant bits force one: kMmqShortKernels k_mmq0p, kMmqLongKernels k_mmq0x
+// (8 waves, 64 x 128), with kMmqHalfWidth half width, with kMmq0xRows2 NR = 2, with kMmq0xRows2W8
+// NR = 2 with 8 waves (64 x 256). Every one keeps the family's canonical combine: the same bits.
+static void mmq0_group(mi_mmx_group & g, hipStream_t s) {
     const int var = g_mi_tuning.mmq_variant;
-    // k_mmqx / k_mmqw park the low half of the canonical fold in their own output locations until
-    // the end: only plain device memory of this device may be used that way. An output in pinned
-    // host memory (host-staged logits) or on a peer device takes the pipelined 32 x 32 tiles, which
-    // store each element once (the same bits: the family's canonical combine).
-    bool dst_local = true;
-    for (int i = 0; i < g.n && dst_local; i++) {
+    const bool q8 = g.type == 8;
+    int pick;
+    if (var & kMmqShortKernels) pick = 0;
+    else if (var & kMmqLongKernels) pick = (var & kMmq0xRows2W8) ? 4 : (var & kMmq0xRows2) ? 3 : (var & kMmqHalfWidth) ? 2 : 1;
+    else {
+        int64_t t2 = 0, th = 0;
+        for (int i = 0; i < g.n; i++) {
+            const int64_t rt = (g.m[i].N + XBM - 1) / XBM, nc = g.m[i].act.ncols;
+            t2 += rt * ((nc + 127) / 128);
+            th += rt * ((nc + 63) / 64);
+        }
+        // (k_mmq0p's Q8_0 operands -- five dword loads per block and lane -- make it the
+        // slower one for Q8_0 from 128 half-width tiles on)
+        pick = t2 >= 256 && g.m[0].act.ncols > 64 ? 3 : th >= (q8 ? 128 : 256) ? 2 : 0;
+    }
+    // tiles of TR rows x TC columns, NT threads each
+#define MI_MMQ0(KERN, TR, TC, NT, ...)                                                          \
+    do {                                                                                        \
+        const dim3 grid((unsigned) mmx_deal(g, TR, TC));                                        \
+        if (!q8) hipLaunchKernelGGL((KERN<false, ##__VA_ARGS__>), grid, dim3(NT), 0, s, g);     \
+        else hipLaunchKernelGGL((KERN<true, ##__VA_ARGS__>), grid, dim3(NT), 0, s, g);          \
+    } while (0)
+    switch (pick) {
+        case 0: MI_MMQ0(k_mmq0p, 32, 32, 256); break;  // (a deeper weight ring, RING 3, spills: 36-dword units)
+        case 1: MI_MMQ0(k_mmq0x, XBM, XBN, 512, 8, 4); break;
+        case 2: MI_MMQ0(k_mmq0x, XBM, 64, 256, 4, 2); break;
+        case 3: MI_MMQ0(k_mmq0x, XBM, 128, 256, 4, 2, 2); break;
+        default: MI_MMQ0(k_mmq0x, XBM, 256, 512, 8, 2, 2); break;
+    }
+#undef MI_MMQ0
+}
+
+// k_mmqx / k_mmqw park the low half of the canonical fold in their own output locations until the
+// end (k_mmqt's tiles are sized for the same prompts): only plain device memory of this device may
+// be used that way. An output in pinned host memory (host-staged logits) or on a peer device takes
+// the pipelined 32 x 32 tiles, which store each element once (the same bits: the family's canonical
+// combine).
+static bool mmx_dst_local(const mi_mmx_group & g) {
+    int dev = 0;
+    (void) hipGetDevice(&dev);
+    for (int i = 0; i < g.n; i++) {
         hipPointerAttribute_t pa;
-        int dev = 0;
-        (void) hipGetDevice(&dev);
         if (hipPointerGetAttributes(&pa, g.m[i].dst) != hipSuccess) {
             (void) hipGetLastError();
-            dst_local = false;  // unknown to HIP: plain host memory
-        } else {
-            dst_local = pa.type == hipMemoryTypeDevice && pa.device == dev;
+            return false;  // unknown to HIP: plain host memory
         }
+        if (pa.type != hipMemoryTypeDevice || pa.device != dev) return false;
     }
-    // long prompts on repacked planes (mmq_planes.hip) when every member carries them (each output
-    // stored once: any destination); variant bits forcing a canonical kernel (16, 128) keep it
-    if (ncols >= kMiPlanesMinCols && !(var & (16 | 128)) && mi_mul_mat_mmqr_group(g, s)) return;
-    // Q4_K prompts of 33..128 columns whose launch (nearly) fills the chip with k_mmqt's 128 x 64
-    // tiles (one workgroup per CU; mmqt_short, default 192 workgroups): k_mmqt instead of k_mmqp
+    return true;
+}
+
+// Q4_K / Q5_K (q8_K activations). Short prompts (<= 128 columns): pipelined 32 x 32 tiles (k_mmqp),
+// a wave per superblock (k_mmqd1, k_mmqd16) when asked, or k_mmqt where its tiles fill the chip; long
+// ones: the planes kernel, k_mmqt (Q4_K), k_mmqw (Q5_K) or k_mmqx. All follow the same canonical
+// combine order (cfold), so a prompt's column shards give the whole prompt's bits whichever kernel
+// runs them. One decision per kernel, top to bottom; the first that applies launches.
+void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
+    if (g.n <= 0) return;
+    if (g.type == 2 || g.type == 8) return mmq0_group(g, s);
+    const bool q4 = g.type == 12;
+    const int S = (int) (g.K / 256);
+    const int64_t ncols = g.m[0].act.ncols;  // every member has the same column count
+    const int var = g_mi_tuning.mmq_variant;
+    const bool dst_local = mmx_dst_local(g);
+    // tiles of tr x tc over all members
+    auto tiles = [&](int64_t tr, int64_t tc) {
+        int64_t t = 0;
+        for (int i = 0; i < g.n; i++) t += ((g.m[i].N + tr - 1) / tr) * ((g.m[i].act.ncols + tc - 1) / tc);
+        return t;
+    };
+    // KERN on tiles of TR rows x TC columns (dealt to the members first), NT threads, LDS dynamic bytes
+#define MI_MMQX(KERN, TR, TC, NT, LDS)                             \
+    do {                                                          \
+        const dim3 grid((unsigned) mmx_deal(g, TR, TC));          \
+        hipLaunchKernelGGL(KERN, grid, dim3(NT), LDS, s, g);      \
+    } while (0)
+#define MI_MMQX_T(KERN, TR, TC, NT, LDS, ...)                                      \
+    do {                                                                          \
+        if (q4) MI_MMQX((KERN<12, ##__VA_ARGS__>), TR, TC, NT, LDS);              \
+        else MI_MMQX((KERN<13, ##__VA_ARGS__>), TR, TC, NT, LDS);                 \
+    } while (0)
+
+    // k_mmqr: long prompts on repacked planes (mmq_planes.hip) when every member carries them (each
+    // output stored once: any destination); variant bits forcing a canonical kernel keep it off
+    if (ncols >= kMiPlanesMinCols && !(var & (kMmqShortKernels | kMmqLongKernels)) && mi_mul_mat_mmqr_group(g, s)) return;
+
+    // k_mmqt, short: Q4_K prompts of 33..128 columns whose launch (nearly) fills the chip with its
+    // 128 x 64 tiles (one workgroup per CU; mmqt_short, default 192 workgroups) instead of k_mmqp
     // (round 6, bit-identical). 32 rotated weights grouped 16 to a launch: B = 64 7.29 -> 5.36 us,
     // B = 128 13.39 -> 10.04 us per mul_mat (profiles/r06s2_pf_mmqt_short.txt); by group size
     // (r06s2b_mmqt_short_groups.txt, r06s2c_mmqt_short_threshold.txt) k_mmqt wins from 192 of its
     // workgroups (3 x B = 128: 13.99 -> 11.19 us; 6 x B = 64: 6.98 -> 5.72 us) and loses below (4 x
     // B = 64, 128 workgroups: 7.76 vs 7.86; a lone B = 64 member's 32: 12.4 vs 26.6 us); B = 32 stays
     // on k_mmqp (4.52 vs 4.85). Variant bits that ask for a particular kernel turn it off.
-    constexpr int kShortTBlock = 16 | 128 | 2048 | 4096 | 8192 | (1 << 19) | (1 << 21) | (1 << 22) | (1 << 26) | (1 << 27);
-    bool short_t = false;
-    if (type == 12 && ncols > 32 && ncols <= 128 && dst_local && g_mi_tuning.mmqt_short > 0 && !(var & kShortTBlock)) {
-        int64_t tt = 0;
-        for (int i = 0; i < g.n; i++) tt += ((g.m[i].N + 127) / 128) * ((g.m[i].act.ncols + 63) / 64);
-        short_t = tt >= g_mi_tuning.mmqt_short;
-    }
-    // k_mmqt plain, or (diagnostic builds, mmq_long 5) with the high half staggered (ST; measured
-    // 3-9 % slower, profiles/r06s2h_mmqt_stagger_ab.txt)
-    const bool st = MI_DIAG && g_mi_tuning.mmq_long == 5;
-    if (short_t) {
-        const dim3 gridt((unsigned) mmx_deal(g, 128, 64));
-#if MI_DIAG
-        if (st) hipLaunchKernelGGL((k_mmqt<12, 0, false, true>), gridt, dim3(512), 0, s, g);
-        else
-#endif
-        hipLaunchKernelGGL((k_mmqt<12>), gridt, dim3(512), 0, s, g);
+    constexpr int kAsksOther = kMmqShortKernels | kMmqLongKernels | kMmqd1 | kMmqNoD16 | kMmqNoShortT | kMmqd16 | kMmqd16Wide | kMmqp8;
+    if (q4 && ncols > 32 && ncols <= 128 && dst_local && g_mi_tuning.mmqt_short > 0 && !(var & kAsksOther) &&
+        tiles(128, 64) >= g_mi_tuning.mmqt_short) {
+        MI_MMQX((k_mmqt<12>), 128, 64, 512, 0);
         return;
     }
-    const bool direct = (var & 16) || (ncols <= 128 && !(var & 128)) || !dst_local;
-    if (direct) {
-        const int S = (int) (K / 256);
-        // 16 x 16 tiles (k_mmqd16) only when asked: variant bit 2^21 up to 16 columns, 2^22 up to 128.
+
+    if ((var & kMmqShortKernels) || (ncols <= 128 && !(var & kMmqLongKernels)) || !dst_local) {
+        // k_mmqd16: 16 x 16 tiles only when asked (kMmqd16 up to 16 columns, kMmqd16Wide up to 128).
         // Round 6 (profiles/r06a_short_prefill.txt, Q4_K / Q5_K 4096^2, 8 rotated weights): k_mmqp's
         // 32 x 32 tiles are faster at B = 9 and 16 both grouped (Q4_K 3.98 / 4.07 vs 5.56 / 5.63 us per
         // mul_mat) and alone in a graph (11.5 / 11.4 vs 12.0 / 12.0 us)
-        const int64_t lim16 = (var & (1 << 22)) ? 128 : (var & (1 << 21)) ? 16 : 0;
-        if (S <= 16 && ncols <= lim16 && !(var & (2048 | 4096))) {
-            const dim3 grid16((unsigned) mmx_deal(g, 16, 16));
-            const size_t lds16 = (size_t) S * 64 * 4 * sizeof(float) + (size_t) S * 16 * sizeof(float);
-            if (type == 12) hipLaunchKernelGGL((k_mmqd16<12>), grid16, dim3(64 * S), lds16, s, g);
-            else hipLaunchKernelGGL((k_mmqd16<13>), grid16, dim3(64 * S), lds16, s, g);
+        const int64_t lim16 = (var & kMmqd16Wide) ? 128 : (var & kMmqd16) ? 16 : 0;
+        if (S <= 16 && ncols <= lim16 && !(var & (kMmqd1 | kMmqNoD16))) {
+            MI_MMQX_T(k_mmqd16, 16, 16, 64 * S, (size_t) S * (64 * 4 + 16) * sizeof(float));
             return;
         }
-        const dim3 grid((unsigned) mmx_deal(g, 32, 32));
-        if (S <= 16 && (var & 2048)) {  // one round: a wave per superblock (variant bit 2048: k_mmqd1)
-            const size_t lds = (size_t) S * 64 * 16 * sizeof(float) + (size_t) S * 32 * sizeof(float);
-            // ABL bits 1..8 from variant bits 12..15, 16 from bit 23
-#if MI_DIAG  // timing ablations (results invalid): diagnostic builds only (make DIAG=1)
-            const int abl = ((var >> 12) & 15) | (((var >> 23) & 1) << 4);
-            if (abl && type == 12) {
-#define MI_MMQD1A(A) hipLaunchKernelGGL((k_mmqd1<12, A>), grid, dim3(64 * S), lds, s, g)
-                switch (abl) {
-                case 1: MI_MMQD1A(1); break;
-                case 2: MI_MMQD1A(2); break;
-                case 4: MI_MMQD1A(4); break;
-                case 8: MI_MMQD1A(8); break;
-                case 10: MI_MMQD1A(10); break;
-                case 16: MI_MMQD1A(16); break;
-                default: MI_MMQD1A(15); break;
-                }
-#undef MI_MMQD1A
-                return;
-            }
-#endif
-            if (type == 12) hipLaunchKernelGGL((k_mmqd1<12>), grid, dim3(64 * S), lds, s, g);
-            else hipLaunchKernelGGL((k_mmqd1<13>), grid, dim3(64 * S), lds, s, g);
+        // k_mmqd1: one round, a wave per superblock, when asked
+        if (S <= 16 && (var & kMmqd1)) {
+            MI_MMQX_T(k_mmqd1, 32, 32, 64 * S, (size_t) S * (64 * 16 + 32) * sizeof(float));
             return;
         }
-        // pipelined 32 x 32 tiles, 8 waves each (k_mmqp; variant bit 2^26: 32 x 64 tiles)
-        const int64_t t64 = mmx_deal(g, 32, 64);
-        const int nc = (MI_DIAG && (var & (1 << 26))) ? 2 : 1;  // 64-column tiles spill: diagnostic builds only
-        const dim3 gridp((unsigned) (nc == 2 ? t64 : mmx_deal(g, 32, 32)));
-        // 4 waves per tile (two workgroups per CU) unless variant bit 2^27 (8 waves, one per CU);
-        // weight ring of 2 (variant bit 2^19: 4 -- slower, profiles/r03w_mmqp_ring.txt: vmcnt retires
-        // in issue order, so a step waiting for its activations also waits for every weight request
-        // issued before them; a deeper weight lead alone only adds outstanding loads)
-        const bool w8 = (var & (1 << 27)) != 0;
-        const bool r2 = !MI_DIAG || (var & (1 << 19)) == 0;  // (ring 4: diagnostic builds only)
-#define MI_MMQP(TY, NCC, NWW, RG) hipLaunchKernelGGL((k_mmqp<TY, NCC, NWW, 0, RG>), gridp, dim3(64 * NWW), 0, s, g)
-#if MI_DIAG
-#define MI_MMQP1(TY, NWW) do { if (r2) MI_MMQP(TY, 1, NWW, 2); else MI_MMQP(TY, 1, NWW, 4); } while (0)
-        if (type == 12) {
-            if (nc == 2) { if (w8) MI_MMQP(12, 2, 8, 2); else MI_MMQP(12, 2, 4, 2); }
-            else { if (w8) MI_MMQP1(12, 8); else MI_MMQP1(12, 4); }
-        } else {
-            if (nc == 2) { if (w8) MI_MMQP(13, 2, 8, 2); else MI_MMQP(13, 2, 4, 2); }
-            else { if (w8) MI_MMQP1(13, 8); else MI_MMQP1(13, 4); }
-        }
-#undef MI_MMQP1
-#else
-        (void) nc;
-        (void) r2;
-        if (type == 12) { if (w8) MI_MMQP(12, 1, 8, 2); else MI_MMQP(12, 1, 4, 2); }
-        else { if (w8) MI_MMQP(13, 1, 8, 2); else MI_MMQP(13, 1, 4, 2); }
-#endif
-#undef MI_MMQP
+        // k_mmqp: pipelined 32 x 32 tiles, 4 waves per tile (two workgroups per CU) unless kMmqp8 (8
+        // waves, one per CU)
+        if (var & kMmqp8) MI_MMQX_T(k_mmqp, 32, 32, 512, 0, 8);
+        else MI_MMQX_T(k_mmqp, 32, 32, 256, 0, 4);
         return;
     }
-    // half-width workgroups (two per CU) when full-width tiles would leave CUs idle: Q4_K B=256
-    // 27.8 -> 26.4 us (B=512 41.7 vs 34.7 us: the per-workgroup dequantization then doubles)
-    int64_t full_tiles = 0;
-    for (int i = 0; i < g.n; i++) full_tiles += ((g.m[i].N + XBM - 1) / XBM) * ((g.m[i].act.ncols + XBN - 1) / XBN);
-    const bool half = (var & 65536) || (type == 12 && full_tiles < 256 && !(var & 131072));
-    if (half) {
-        const dim3 grid4((unsigned) mmx_deal(g, XBM, 64));
-        if (type == 12) hipLaunchKernelGGL((k_mmqx<12, false, 0, 2, 0, 4>), grid4, dim3(256), 0, s, g);
-        else hipLaunchKernelGGL((k_mmqx<13, false, 0, 2, 0, 4>), grid4, dim3(256), 0, s, g);
+
+    // k_mmqx, half-width workgroups (two per CU) when full-width tiles would leave CUs idle: Q4_K
+    // B=256 27.8 -> 26.4 us (B=512 41.7 vs 34.7 us: the per-workgroup dequantization then doubles)
+    if ((var & kMmqHalfWidth) || (q4 && tiles(XBM, XBN) < 256 && !(var & kMmqFullWidth))) {
+        MI_MMQX_T(k_mmqx, XBM, 64, 256, 0, 2, 4);
         return;
     }
-    // Q4_K: K split over wave pairs, 128 x 64 tiles (k_mmqt, the default; B=512 33.4 vs 36.6 us for
-    // k_mmqw, B=256 18.5 vs 19.7, profiles/r04i_pf_long_mmqt.txt; its DMAs all at the step start
-    // instead of one behind each MFMA step: 37.1 us; the high half folding one step late from a
-    // 3-slot LDS ring, so the two waves of a SIMD alternate MFMA and VALU phases: 38.7 us,
-    // profiles/r04k_mmqt_skew_ab.txt, r04m_mmqt_skew_stamps.txt; DMAs through buffer descriptors:
-    // no change, r04p_mmqt_buf_ab.txt; the two column tiles in two passes over held planes with
-    // tile 0's combine under tile 1's MFMAs: 36.4 vs 35.5 us, r04r_mmqt_split_ab.txt, and tile 1's
-    // combine deferred into the next step too: 36.9 vs 35.4 us, r04t_mmqt_split2_ab.txt -- all
-    // removed)
-    const int lng = g_mi_tuning.mmq_long;
-    if ((!MI_DIAG || lng == 0 || lng == 2 || lng == 3 || lng == 4 || lng == 5) && type == 12 && !(var & ((1 << 28) | 64 | 1024))) {
-        const dim3 gridt((unsigned) mmx_deal(g, 128, 64));
-#if MI_DIAG  // measured slower (round 6, profiles/r06e_mmqv_prefill.txt): diagnostic builds only
-        if (lng == 3) hipLaunchKernelGGL((k_mmqt<12, 0, true>), gridt, dim3(512), 0, s, g);  // per-half stage sync
-        else if (lng == 4) hipLaunchKernelGGL((k_mmqv<12>), gridt, dim3(256), 0, s, g);  // one wave per SIMD, pipelined
-        else
-#endif
-#if MI_DIAG
-        if (st) hipLaunchKernelGGL((k_mmqt<12, 0, false, true>), gridt, dim3(512), 0, s, g);
-        else
-#endif
-        hipLaunchKernelGGL((k_mmqt<12>), gridt, dim3(512), 0, s, g);
-        (void) st;
+
+    // k_mmqt: Q4_K, K split over wave pairs, 128 x 64 tiles (the default; B=512 33.4 vs 36.6 us for
+    // k_mmqw, B=256 18.5 vs 19.7, profiles/r04i_pf_long_mmqt.txt)
+    const bool mmqx_asked = (var & (kMmqxOnly | kMmqxLead1)) != 0;
+    if (q4 && !mmqx_asked) {
+        MI_MMQX((k_mmqt<12>), 128, 64, 512, 0);
         return;
     }
-#if MI_DIAG
-    if (lng >= 16 && lng < 24 && type == 12) {  // k_mmqt stamps (+ ablation bits lng - 16; results invalid)
-        const dim3 gridt((unsigned) mmx_deal(g, 128, 64));
-        switch (lng - 16) {
-            case 1: hipLaunchKernelGGL((k_mmqt<12, 9>), gridt, dim3(512), 0, s, g); break;
-            case 2: hipLaunchKernelGGL((k_mmqt<12, 10>), gridt, dim3(512), 0, s, g); break;
-            case 4: hipLaunchKernelGGL((k_mmqt<12, 12>), gridt, dim3(512), 0, s, g); break;
-            case 6: hipLaunchKernelGGL((k_mmqt<12, 14>), gridt, dim3(512), 0, s, g); break;
-            case 7: hipLaunchKernelGGL((k_mmqt<12, 8, true>), gridt, dim3(512), 0, s, g); break;  // per-half sync, stamps
-            default: hipLaunchKernelGGL((k_mmqt<12, 8>), gridt, dim3(512), 0, s, g); break;
-        }
+
+    // k_mmqw: Q5_K, warp-specialized (4 loader + 8 MFMA waves; Q5_K B=512 46.2 -> 43.8 us grouped,
+    // profiles/r03r_prefill_mmqw.txt); its loader loop needs S % 4 == 0
+    if (!q4 && !mmqx_asked && S % 4 == 0) {
+        MI_MMQX((k_mmqw<13, 4>), XBM, XBN, 768, 0);
         return;
     }
-#endif
-    const dim3 grid((unsigned) mmx_deal(g, XBM, XBN));
-    // warp-specialized k_mmqw (4 loader + 8 MFMA waves; Q4_K B=512 32.1 -> 31.2 us, Q5_K 46.2 ->
-    // 43.8 us grouped, profiles/r03r_prefill_mmqw.txt) unless variant bit 2^28 asks for k_mmqx
-#if MI_DIAG
-    if ((var & 1024) && (var & (1 << 29)) && type == 12) {  // k_mmqw timing stamps (results invalid)
-        hipLaunchKernelGGL((k_mmqw<12, 4, 8>), grid, dim3(768), 0, s, g);
-        return;
-    }
-#endif
-    if (!(var & ((1 << 28) | 64 | 1024)) && (K / 256) % 4 == 0) {
-#if MI_DIAG  // (Q4_K on k_mmqw: mmq_long 1, diagnostic builds only)
-        if (type == 12) hipLaunchKernelGGL((k_mmqw<12, 4>), grid, dim3(768), 0, s, g);
-        else
-#endif
-        hipLaunchKernelGGL((k_mmqw<13, 4>), grid, dim3(768), 0, s, g);
-        return;
-    }
-    // weight ring depth LEAD (variant bits: 64 -> 1, default 4). (Fully unrolling the stage loop
-    // for K = 4096, SCT = 16, spills: the compiler hoists loads across stages.)
-#define MI_MMQX_T(TY, LD) hipLaunchKernelGGL((k_mmqx<TY, false, 0, LD, 0>), grid, dim3(512), 0, s, g)
-    const int lead = (var & 64) ? 1 : 4;
-#if MI_DIAG
-    if (var & 1024) {  // timing stamps (results invalid)
-        if (type == 12) hipLaunchKernelGGL((k_mmqx<12, false, 8, 4, 0>), grid, dim3(512), 0, s, g);
-        return;
-    }
-#endif
-    if (type == 12) {
-        if (lead == 1) MI_MMQX_T(12, 1); else MI_MMQX_T(12, 4);
-    } else {
-        if (lead == 1) MI_MMQX_T(13, 1); else MI_MMQX_T(13, 4);
-    }
+
+    // k_mmqx: weight ring depth 4 (kMmqxLead1: 1)
+    if (var & kMmqxLead1) MI_MMQX_T(k_mmqx, XBM, XBN, 512, 0, 1);
+    else MI_MMQX_T(k_mmqx, XBM, XBN, 512, 0, 4);
 #undef MI_MMQX_T
+#undef MI_MMQX
 }
 
 void mi_mul_mat_mmqx(int type, const void * W, size_t nb01, int64_t K, int64_t N, const mi_act_mmx & act, float * dst,

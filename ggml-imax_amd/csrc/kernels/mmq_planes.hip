@@ -113,11 +113,8 @@ __global__ __launch_bounds__(64) void k_planes_repack(const uint8_t * __restrict
     }
 }
 
-// STAMP (diagnostic builds, mmq_long 24): wave 0 of every workgroup records s_memrealtime at entry
-// (slot 0), after the prologue (1) and per superblock sb at 2 + 4 sb + {0 step start, 1 MFMAs
-// issued, 2 combine done, 3 past the end-of-step wait and barrier}; ns slots per workgroup
-template <int TYPE, bool STAMP = false>
-__global__ __launch_bounds__(512, 1) void k_mmqr(mi_mmx_group grp, uint64_t * st = nullptr, int ns = 0) {
+template <int TYPE>
+__global__ __launch_bounds__(512, 1) void k_mmqr(mi_mmx_group grp) {
     MI_MMX_MEMBER(grp);
     using P = PFmt<TYPE>;
     using F = XFmt<TYPE>;
@@ -138,12 +135,6 @@ __global__ __launch_bounds__(512, 1) void k_mmqr(mi_mmx_group grp, uint64_t * st
     __shared__ __attribute__((aligned(16))) char lds[2 * SB];
 
     const char * __restrict__ planes = grp.m[mmx_i_].planes;
-    auto stamp = [&](int slot) {
-        if constexpr (STAMP) {
-            if (threadIdx.x == 0) st[(size_t) blockIdx.x * ns + slot] = __builtin_amdgcn_s_memrealtime();
-        }
-    };
-    stamp(0);
     const int tid = (int) threadIdx.x;
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -220,7 +211,6 @@ __global__ __launch_bounds__(512, 1) void k_mmqr(mi_mmx_group grp, uint64_t * st
 
     auto step = [&](int sb) {
         const char * base = lds + (sb & 1) * SB;
-        stamp(2 + 4 * sb);
 #pragma unroll
         for (int kk = 0; kk < 8; kk++) {
             const i32x4 xa = *(const i32x4 *) (base + kk * (BN * 32) + xoff);
@@ -233,7 +223,6 @@ __global__ __launch_bounds__(512, 1) void k_mmqr(mi_mmx_group grp, uint64_t * st
         }
 #pragma unroll
         for (int i = 8; i <= NI; i++) stage_piece(sb + 1, i);
-        stamp(3 + 4 * sb);
         // combine: U on the f16 MFMA, mmqx_pre per element, canonical fold
         const half8 mu = *(const half8 *) (base + woff + P::PB);
         const float2 dd = *(const float2 *) (base + OM + rw * 256 + r * 8);
@@ -256,19 +245,16 @@ __global__ __launch_bounds__(512, 1) void k_mmqr(mi_mmx_group grp, uint64_t * st
             }
         }
         cfold_vec(gsum, y, lo, tv, dv, sb, gs, S);
-        stamp(4 + 4 * sb);
     };
 
 #pragma unroll
     for (int i = 0; i <= NI; i++) stage_piece(0, i);
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    stamp(1);
     for (int sb = 0; sb < S; sb++) {
         step(sb);
         // the next stage has landed (every global load of this kernel is a DMA), every wave is done
         // with this stage's buffer
         asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        stamp(5 + 4 * sb);
     }
 
     const int64_t n = n0 + 32 * rw + r;
@@ -465,18 +451,6 @@ bool mi_mul_mat_mmqr_group(mi_mmx_group & g, hipStream_t s) {
         g.m[i].tile_begin = tiles;
         tiles += ((g.m[i].N + 63) / 64) * ((g.m[i].act.ncols + 127) / 128);
     }
-    const int var = g_mi_tuning.mmq_variant;
-#if MI_DIAG
-    if (g_mi_tuning.mmq_long == 24) {  // per-step stamps (tools/mmqr_stamps.py)
-        const int ns = ((4 * (int) (g.K / 256) + 2 + 7) / 8) * 8;
-        uint64_t * st = mi_stamp_take("k_mmqr", (unsigned) (tiles * ns / 8));
-        if (st) {
-            hipLaunchKernelGGL((k_mmqr<12, true>), dim3((unsigned) tiles), dim3(512), 0, s, g, st, ns);
-            return true;
-        }
-    }
-#endif
-    (void) var;
     hipLaunchKernelGGL((k_mmqr<12>), dim3((unsigned) tiles), dim3(512), 0, s, g);
     return true;
 }

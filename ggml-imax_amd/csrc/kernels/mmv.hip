@@ -766,7 +766,7 @@ void mi_mul_mat_q(const mi_mm_desc & m, const mi_act_q8 & act, hipStream_t s) {
     const int nc = m.ne11 >= 5 ? 8 : (int) m.ne11;
     const mi_act_q8 act_or_x = act;
     const bool q32 = m.type == 2 || m.type == 8 || m.type == 3 || m.type == 6 || m.type == 7;
-    if (mi_mmv_order() == 1 && q32) {  // reference CPU order: 8 rows per wave (mode 2 is a timing ablation of the fused kernel only)
+    if (mi_mmv_order() == 1 && q32) {  // reference CPU order: 8 rows per wave
 #define MI_MMV_ORD_LAUNCH(NC)                                                                               \
         do {                                                                                                 \
             const mmv_geom g = make_geom(m, NC);                                                             \

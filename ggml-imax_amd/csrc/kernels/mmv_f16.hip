@@ -267,8 +267,6 @@ __global__ __launch_bounds__(512) void k_gemv_f16(const uint8_t * __restrict__ W
                                                   float * __restrict__ dst, size_t ycol, mi_f16_epilogue e, mi_norm_prologue pro,
                                                   int64_t kp, int rgs) {
     extern __shared__ __attribute__((aligned(16))) uint16_t xs[];  // [NC][kp] f16 (zero beyond K), then [waves][4][NC] f32
-    MI_STAMP(e.stamps, 0);
-    MI_STAMP_CLK(e.stamps, 6);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x >> 6) / rgs;
     const int grp = wid / nw, wave = wid % nw;  // row group, K slice
     const int m = lane & (kLpr - 1), rg = lane >> 4;
@@ -361,7 +359,6 @@ __global__ __launch_bounds__(512) void k_gemv_f16(const uint8_t * __restrict__ W
             stage_cols<JX>(x, c0, nc, K, kp, xs);
         }
     }
-    MI_STAMP(e.stamps, 1);  // activations staged (normalized) by wave 0
     if (!priv) mi_lds_barrier();
 
     float acc[NC];
@@ -394,7 +391,6 @@ __global__ __launch_bounds__(512) void k_gemv_f16(const uint8_t * __restrict__ W
         }
     }
 
-    MI_STAMP(e.stamps, 3);  // wave 0's dots done (its weights landed)
     // this wave's row totals in every lane of the row; lane m < nc holds column m
     float mine = 0.0f;
 #pragma unroll
@@ -426,8 +422,6 @@ __global__ __launch_bounds__(512) void k_gemv_f16(const uint8_t * __restrict__ W
                 *(float *) (e.copy[k].ptr + col * e.copy[k].col_stride + (row - e.copy[k].row0) * sizeof(float)) = v;
         }
     }
-    MI_STAMP_CLK(e.stamps, 5);
-    MI_STAMP(e.stamps, 7);
 }
 
 // Tall matrices (lm_head, N = 50257): 1..8 columns (NC, padded), rows in one register pass (K <= 128 U).
@@ -442,8 +436,6 @@ __global__ __launch_bounds__(256) void k_gemv_f16_tall(const uint8_t * __restric
                                                        mi_src_cols x, int ncols, float * __restrict__ dst, size_t ycol,
                                                        mi_f16_epilogue e, mi_norm_prologue pro, int64_t kp) {
     extern __shared__ __attribute__((aligned(16))) uint16_t xs[];  // [NC][kp] f16
-    MI_STAMP(e.stamps, 0);
-    MI_STAMP_CLK(e.stamps, 6);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int m = lane & (kLpr - 1), rg = lane >> 4;
     const int64_t ngroups = (N + 3) / 4, stride = (int64_t) gridDim.x * 4;
@@ -501,7 +493,6 @@ __global__ __launch_bounds__(256) void k_gemv_f16_tall(const uint8_t * __restric
         stage_cols<4>(x, 0, nc, K, kp, xs);
     }
     mi_lds_barrier();
-    MI_STAMP(e.stamps, 2);
 
     for (; grp < ngroups; grp += stride) {
         uint4 nxt[U];
@@ -540,8 +531,6 @@ __global__ __launch_bounds__(256) void k_gemv_f16_tall(const uint8_t * __restric
         for (int u = 0; u < U; u++) cur[u] = nxt[u];
         eb = ebn;
     }
-    MI_STAMP_CLK(e.stamps, 5);
-    MI_STAMP(e.stamps, 7);
 }
 
 // Tall matrices (lm_head) with 2..8 columns on the matrix cores (round 6): k_gemv_f16_tall's dot8
@@ -560,7 +549,6 @@ __global__ __launch_bounds__(256) void k_gemv_f16_mt(const uint8_t * __restrict_
                                                      mi_src_cols x, int ncols, float * __restrict__ dst, size_t ycol,
                                                      mi_f16_epilogue e, mi_norm_prologue pro, int64_t kp) {
     extern __shared__ __attribute__((aligned(16))) uint16_t xs[];  // [8][kp] f16
-    MI_STAMP(e.stamps, 0);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int li = lane & 15, lk = lane >> 4;
     const int nc = ncols < 8 ? ncols : 8;
@@ -598,7 +586,6 @@ __global__ __launch_bounds__(256) void k_gemv_f16_mt(const uint8_t * __restrict_
         stage_cols<4>(x, 0, nc, K, kp, xs);
     }
     mi_lds_barrier();
-    MI_STAMP(e.stamps, 2);
     // the columns as B operands for the whole K (zero past nc)
     half8 b[NK];
 #pragma unroll
@@ -629,104 +616,7 @@ __global__ __launch_bounds__(256) void k_gemv_f16_mt(const uint8_t * __restrict_
             }
         }
     }
-    MI_STAMP(e.stamps, 7);
 }
-
-#if MI_DIAG
-// (diagnostic builds only: measured slower than k_gemv_f16 on batched decode, 0.515 -> 0.568 ms/step,
-// profiles/r06s2k_batched_f16_m8_ab.txt -- a 16-row tile per workgroup leaves 48 workgroups for the
-// 768-row projections, fewer than the streams the weight rows need)
-// Plain (no norm prologue) F16 GEMVs of 2..8 columns on the matrix cores (round 6, batched decode's
-// attention / MLP output projections): one workgroup of NW waves per 16-row tile, the K steps
-// (32 deep) dealt to the waves in contiguous runs of at most NKW; each lane loads its A operand (row
-// l % 16, K slice 8 (l / 16) of a step) straight from the weights and its B operand (column l % 16,
-// the same K slice) straight from the f32 columns, rounded to f16 in registers -- no LDS staging of
-// the columns, each workgroup reads only its K runs of them once. The waves' 16 x 16 partial tiles
-// are added in wave order by wave 0, which applies the epilogue (bias, residual, GELU, row copies).
-// Tree order (f32 sums in the matrix core's order): within 1e-5 of the reference's vec_dot_f16.
-template <int EPI, int NKW, int NW>
-__global__ __launch_bounds__(64 * NW) void k_gemv_f16_m8(const uint8_t * __restrict__ W, size_t nb01, int64_t K, int64_t N,
-                                                         mi_src_cols x, int ncols, float * __restrict__ dst, size_t ycol,
-                                                         mi_f16_epilogue e) {
-    __shared__ float red[NW][64][4];
-    MI_STAMP(e.stamps, 0);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int li = lane & 15, lk = lane >> 4;
-    const int nc = ncols < 8 ? ncols : 8;
-    const int nk = (int) (K / 32);
-    const int spw = (nk + NW - 1) / NW;                 // steps per wave (<= NKW, launcher)
-    const int t0 = wid * spw, t1 = t0 + spw < nk ? t0 + spw : nk;
-    const int64_t r0 = (int64_t) blockIdx.x * 16;
-    const int64_t r = r0 + li;
-    const uint8_t * wrow = W + (r < N ? r : N - 1) * nb01 + (size_t) lk * 16;
-    const char * xc = x.base + (size_t) (li < nc ? li : 0) * x.nb1 + (size_t) lk * 32;
-    half8 a[NKW];
-    float4 xv[NKW][2];
-#pragma unroll
-    for (int i = 0; i < NKW; i++) {
-        const int t = t0 + i < t1 ? t0 + i : (t1 > t0 ? t1 - 1 : 0);  // (clamped: unconditional loads)
-        a[i] = *(const half8 *) (wrow + (size_t) t * 64);
-    }
-    // (the epilogue operands ride behind the weights)
-    float e_bias[4], e_res[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int64_t rq = r0 + lk * 4 + q;
-        const int64_t rc = rq < N ? rq : N - 1;
-        e_bias[q] = EPI >= 1 ? e.bias[rc] : 0.0f;
-        e_res[q] = EPI == 2 ? *(const float *) (e.resid + (size_t) (li < nc ? li : 0) * e.resid_nb1 + rc * sizeof(float)) : 0.0f;
-    }
-#pragma unroll
-    for (int i = 0; i < NKW; i++) {
-        const int t = t0 + i < t1 ? t0 + i : (t1 > t0 ? t1 - 1 : 0);
-        xv[i][0] = *(const float4 *) (xc + (size_t) t * 128);
-        xv[i][1] = *(const float4 *) (xc + (size_t) t * 128 + 16);
-    }
-    typedef float f32x4v_t __attribute__((ext_vector_type(4)));
-    f32x4v_t acc = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int i = 0; i < NKW; i++) {
-        if (t0 + i < t1) {
-            half8 b;
-            b[0] = (_Float16) xv[i][0].x; b[1] = (_Float16) xv[i][0].y; b[2] = (_Float16) xv[i][0].z; b[3] = (_Float16) xv[i][0].w;
-            b[4] = (_Float16) xv[i][1].x; b[5] = (_Float16) xv[i][1].y; b[6] = (_Float16) xv[i][1].z; b[7] = (_Float16) xv[i][1].w;
-            if (li >= nc) b = half8{};
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i], b, acc, 0, 0, 0);
-        }
-    }
-    MI_STAMP(e.stamps, 3);
-    red[wid][lane][0] = acc.x;
-    red[wid][lane][1] = acc.y;
-    red[wid][lane][2] = acc.z;
-    red[wid][lane][3] = acc.w;
-    mi_lds_barrier();
-    if (wid != 0) return;
-    float v4[4] = {red[0][lane][0], red[0][lane][1], red[0][lane][2], red[0][lane][3]};
-#pragma unroll
-    for (int w = 1; w < NW; w++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) v4[q] += red[w][lane][q];
-    if (li < nc) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int64_t row = r0 + lk * 4 + q;
-            if (row < N) {
-                float v = v4[q];
-                if (EPI >= 1) v = v + e_bias[q];
-                if (EPI == 2) v = v + e_res[q];
-                if (EPI == 3) v = v <= -10.0f ? 0.0f : (v >= 10.0f ? v : mi_h2f(e.gelu_table[mi_f2h(v)]));
-                *(float *) ((char *) dst + (size_t) li * ycol + row * sizeof(float)) = v;
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    if (e.copy[k].ptr && row >= e.copy[k].row0 && row < e.copy[k].row1)
-                        *(float *) (e.copy[k].ptr + (size_t) li * e.copy[k].col_stride + (row - e.copy[k].row0) * sizeof(float)) = v;
-                }
-            }
-        }
-    }
-    MI_STAMP(e.stamps, 7);
-}
-#endif  // MI_DIAG
 
 // The F16 GEMV of one column whose input is a norm chain over a value still held as partial sums
 // (mi_attn_proj's per-head parts, mi_norm_prologue::parts): workgroup = RW waves x 4 rows (RW =
@@ -741,8 +631,6 @@ __global__ __launch_bounds__(512) void k_gemv_f16_ps(const uint8_t * __restrict_
                                                      float * __restrict__ dst, mi_f16_epilogue e, mi_norm_prologue pro, int64_t kp) {
     const int rw = blockDim.x >> 6;
     extern __shared__ __attribute__((aligned(16))) uint16_t xs[];  // [rw][kp] f16 per wave, then [kp] f32 (the sum)
-    MI_STAMP(e.stamps, 0);
-    MI_STAMP_CLK(e.stamps, 6);
     float * xf = (float *) (xs + (size_t) rw * kp);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int m = lane & (kLpr - 1), rg = lane >> 4;
@@ -800,9 +688,7 @@ __global__ __launch_bounds__(512) void k_gemv_f16_ps(const uint8_t * __restrict_
             if (blockIdx.x == 0) *(float4 *) (pro.store + q4) = sum;
         }
     }
-    MI_STAMP(e.stamps, 1);  // parts landed and summed (wave 0)
     __syncthreads();
-    MI_STAMP(e.stamps, 2);
     float4 v[JM];
 #pragma unroll
     for (int j = 0; j < JM; j++) {
@@ -811,7 +697,6 @@ __global__ __launch_bounds__(512) void k_gemv_f16_ps(const uint8_t * __restrict_
     }
     uint16_t * xw = xs + (size_t) wid * kp;
     norm_store<JM, true>(v, pg, pb, K, kp, pro, xw, lane);
-    MI_STAMP(e.stamps, 4);  // normalized
 
     float acc = 0.0f;
 #pragma unroll
@@ -830,8 +715,6 @@ __global__ __launch_bounds__(512) void k_gemv_f16_ps(const uint8_t * __restrict_
                 *(float *) (e.copy[k].ptr + (row - e.copy[k].row0) * sizeof(float)) = r;
         }
     }
-    MI_STAMP_CLK(e.stamps, 5);
-    MI_STAMP(e.stamps, 7);
 }
 
 // Several columns (2..8) with the norm prologue (round 6; batched decode's c_attn / c_fc, K <= 1024):
@@ -845,8 +728,7 @@ __global__ __launch_bounds__(512) void k_gemv_f16_ps(const uint8_t * __restrict_
 // dot8, row16_sum): tree order, within the F16 tolerance of the reference.
 // KS > 1: the KS waves of a 4-row group split the row's chunks (wave part p takes chunks i = p mod KS)
 // and their partial sums meet in LDS, added in part order.
-// JM == 0 (plain, no norm: batched decode's c_proj / mlp projection): every thread stages the f32
-// columns to f16 LDS (stage_cols) instead; NCHT = 16-byte chunks per lane and row (K <= 128 NCHT).
+// NCHT = 16-byte chunks per lane and row (K <= 128 NCHT).
 template <int EPI, int JM, int NW, int KS = 1, int NCHT = JM * 2>
 __global__ __launch_bounds__(64 * NW) void k_gemv_f16_bn(const uint8_t * __restrict__ W, size_t nb01, int64_t K, int64_t N,
                                                         mi_src_cols x, int64_t ncols, float * __restrict__ dst, size_t ycol,
@@ -854,8 +736,6 @@ __global__ __launch_bounds__(64 * NW) void k_gemv_f16_bn(const uint8_t * __restr
     extern __shared__ __attribute__((aligned(16))) uint16_t xs[];  // [8][kp] f16, then [NW][4][8] f32 partials
     constexpr int CPW = (8 + NW - 1) / NW;  // columns per wave
     constexpr int NCH = NCHT / KS;           // 16-byte chunks per lane and row of this wave
-    constexpr int JMV = JM > 0 ? JM : 1;
-    MI_STAMP(e.stamps, 0);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int m = lane & (kLpr - 1), rg = lane >> 4;
     const int grp = wid / KS, part = wid % KS;
@@ -865,18 +745,16 @@ __global__ __launch_bounds__(64 * NW) void k_gemv_f16_bn(const uint8_t * __restr
     const int64_t k8 = K / kChunk;
 
     // the wave's columns, g and b first (vmcnt retires in order), then the rows' weight chunks
-    float4 pv[CPW][JMV], pg[JMV], pb[JMV];
-    if constexpr (JM > 0) {
+    float4 pv[CPW][JM], pg[JM], pb[JM];
 #pragma unroll
-        for (int j = 0; j < CPW; j++) {
-            const int c = wid + NW * j;
-            const float * xc = (const float *) (x.base + (c < nc ? c : nc - 1) * x.nb1);
-            if (j == 0) {
-                norm_load<JM, true>(xc, K, lane, pro, pv[0], pg, pb);
-            } else {
-                float4 dg[1], db[1];
-                norm_load<JM, false>(xc, K, lane, pro, pv[j], dg, db);
-            }
+    for (int j = 0; j < CPW; j++) {
+        const int c = wid + NW * j;
+        const float * xc = (const float *) (x.base + (c < nc ? c : nc - 1) * x.nb1);
+        if (j == 0) {
+            norm_load<JM, true>(xc, K, lane, pro, pv[0], pg, pb);
+        } else {
+            float4 dg[1], db[1];
+            norm_load<JM, false>(xc, K, lane, pro, pv[j], dg, db);
         }
     }
     asm volatile("" ::: "memory");
@@ -894,17 +772,11 @@ __global__ __launch_bounds__(64 * NW) void k_gemv_f16_bn(const uint8_t * __restr
         if (EPI >= 1) e_bias = e.bias[rc];
         if (EPI == 2) e_res = *(const float *) (e.resid + cc * e.resid_nb1 + rc * sizeof(float));
     }
-    if constexpr (JM > 0) {
 #pragma unroll
-        for (int j = 0; j < CPW; j++) {
-            const int c = wid + NW * j;
-            if (c < nc) norm_store<JM, true>(pv[j], pg, pb, K, kp, pro, xs + (size_t) c * kp, lane);
-        }
-    } else {
-        (void) pv; (void) pg; (void) pb;
-        stage_cols<8>(x, 0, nc, K, kp, xs);
+    for (int j = 0; j < CPW; j++) {
+        const int c = wid + NW * j;
+        if (c < nc) norm_store<JM, true>(pv[j], pg, pb, K, kp, pro, xs + (size_t) c * kp, lane);
     }
-    MI_STAMP(e.stamps, 1);
     mi_lds_barrier();
 
     float acc[8];
@@ -920,7 +792,6 @@ __global__ __launch_bounds__(64 * NW) void k_gemv_f16_bn(const uint8_t * __restr
                 if (c < nc) acc[c] = dot8(w, *(const uint4 *) (xs + (size_t) c * kp + k), acc[c]);
         }
     }
-    MI_STAMP(e.stamps, 3);
     float mine = 0.0f;
 #pragma unroll
     for (int c = 0; c < 8; c++) {
@@ -949,7 +820,6 @@ __global__ __launch_bounds__(64 * NW) void k_gemv_f16_bn(const uint8_t * __restr
                 *(float *) (e.copy[k].ptr + col * e.copy[k].col_stride + (row - e.copy[k].row0) * sizeof(float)) = v;
         }
     }
-    MI_STAMP(e.stamps, 7);
 }
 
 template <int NC, int U, bool ONE, int JM>
@@ -962,7 +832,6 @@ void launch_nc(const void * W, size_t nb01, int64_t K, int64_t N, const mi_src_c
     const int epi = e.gelu_table ? 3 : (e.resid ? 2 : (e.bias ? 1 : 0));
     const uint8_t * w = (const uint8_t *) W;
     mi_f16_epilogue es = e;
-    es.stamps = mi_stamp_take(JM ? "k_gemv_f16_norm" : "k_gemv_f16", grid.x * grid.y);
     es.xfirst = g_mi_tuning.xfirst == 1;  // (off by default: GPT-2 decode 304 -> 316 us per token with it)
 #define MI_GEMV_F16X(EP, XHV) hipLaunchKernelGGL((k_gemv_f16<NC, EP, U, ONE, JM, XHV>), grid, dim3(64 * ks * rgs), lds, s, w, nb01, K, N, x, xh, ncols, dst, ycol, es, pro, kp, rgs)
 #define MI_GEMV_F16(EP) do { if constexpr (JM == 0) { if (xh) MI_GEMV_F16X(EP, true); else MI_GEMV_F16X(EP, false); } else MI_GEMV_F16X(EP, false); } while (0)
@@ -1058,7 +927,6 @@ void mi_mul_mat_f16_fast(const void * W, size_t nb01, int64_t K, int64_t N, cons
             // several columns on the matrix cores (k_gemv_f16_mt): 16-row tiles, grid-stride
             const dim3 gridm((unsigned) std::min<int64_t>(((N + 15) / 16 + 3) / 4, 512));
             const size_t ldsm = (size_t) 8 * kp * sizeof(uint16_t);
-            es.stamps = mi_stamp_take("k_gemv_f16_mt", gridm.x);
 #define MI_GEMV_MT(EP, JMV) hipLaunchKernelGGL((k_gemv_f16_mt<EP, JMV, 24>), gridm, dim3(256), ldsm, s, w, nb01, K, N, x, (int) ncols, dst, ycol, es, pro, kp)
             if (pro.mode) {
                 if (epi == 0) MI_GEMV_MT(0, 4); else if (epi == 1) MI_GEMV_MT(1, 4); else MI_GEMV_MT(3, 4);
@@ -1068,7 +936,6 @@ void mi_mul_mat_f16_fast(const void * W, size_t nb01, int64_t K, int64_t N, cons
 #undef MI_GEMV_MT
             return;
         }
-        es.stamps = mi_stamp_take("k_gemv_f16_tall", grid.x);
         es.xfirst = g_mi_tuning.xfirst == 1;  // (off by default: GPT-2 decode 304 -> 316 us per token with it)
 #define MI_GEMV_TALL_N(EP, JMV, NCV) hipLaunchKernelGGL((k_gemv_f16_tall<EP, 8, JMV, NCV>), grid, dim3(256), lds, s, w, nb01, K, N, x, (int) ncols, dst, ycol, es, pro, kp)
 #define MI_GEMV_TALL(EP, JMV) do { switch (nc) { case 1: MI_GEMV_TALL_N(EP, JMV, 1); break; case 2: MI_GEMV_TALL_N(EP, JMV, 2); break; \
@@ -1093,7 +960,6 @@ void mi_mul_mat_f16_fast(const void * W, size_t nb01, int64_t K, int64_t N, cons
         const int epi = e.gelu_table ? 3 : (e.resid ? 2 : (e.bias ? 1 : 0));
         const uint8_t * w = (const uint8_t *) W;
         mi_f16_epilogue es = e;
-        es.stamps = mi_stamp_take("k_gemv_f16_ps", grid.x);
         es.xfirst = g_mi_tuning.xfirst == 1;  // (off by default: GPT-2 decode 304 -> 316 us per token with it)
 #define MI_GEMV_PS(EP, NPM, QPT) hipLaunchKernelGGL((k_gemv_f16_ps<EP, 8, 4, NPM, QPT>), grid, dim3(64 * rw), lds, s, w, nb01, K, N, dst, es, pro, kp)
 #define MI_GEMV_PS_E(NPM, QPT)                     \
@@ -1120,48 +986,13 @@ void mi_mul_mat_f16_fast(const void * W, size_t nb01, int64_t K, int64_t N, cons
         const size_t lds = (size_t) 8 * kp * sizeof(uint16_t) + (size_t) NWv * 4 * 8 * sizeof(float);
         const int epi = e.gelu_table ? 3 : (e.resid ? 2 : (e.bias ? 1 : 0));
         const uint8_t * w = (const uint8_t *) W;
-        mi_f16_epilogue es = e;
-        es.stamps = mi_stamp_take("k_gemv_f16_bn", grid.x);
-#define MI_GEMV_BN(EP, NWV, KSV) hipLaunchKernelGGL((k_gemv_f16_bn<EP, 4, NWV, KSV>), grid, dim3(64 * NWV), lds, s, w, nb01, K, N, x, ncols, dst, ycol, es, pro, kp)
+#define MI_GEMV_BN(EP, NWV, KSV) hipLaunchKernelGGL((k_gemv_f16_bn<EP, 4, NWV, KSV>), grid, dim3(64 * NWV), lds, s, w, nb01, K, N, x, ncols, dst, ycol, e, pro, kp)
 #define MI_GEMV_BN_E(NWV, KSV) switch (epi) { case 0: MI_GEMV_BN(0, NWV, KSV); break; case 1: MI_GEMV_BN(1, NWV, KSV); break; \
                                                   case 2: MI_GEMV_BN(2, NWV, KSV); break; default: MI_GEMV_BN(3, NWV, KSV); break; }
         if (bn == 5) { MI_GEMV_BN_E(16, 4) } else if (bn == 4) { MI_GEMV_BN_E(8, 4) } else if (KSv == 2) { MI_GEMV_BN_E(8, 2) }
         else if (NWv == 8) { MI_GEMV_BN_E(8, 1) } else { MI_GEMV_BN_E(4, 1) }
 #undef MI_GEMV_BN_E
 #undef MI_GEMV_BN
-#if MI_DIAG
-    } else if (!pro.mode && ncols > 1 && K % 32 == 0 && K <= 4096 && !xh && g_mi_tuning.f16_m8 > 0 && (N + 3) / 4 < 4096) {
-        // several plain columns on the matrix cores (k_gemv_f16_m8): per 16-row tile 4 waves (K <= 1024,
-        // at most 8 steps of 32 each) or 8 (at most 16 steps each)
-        const int nk = (int) (K / 32);
-        const dim3 grid((unsigned) ((N + 15) / 16));
-        const int epi = e.gelu_table ? 3 : (e.resid ? 2 : (e.bias ? 1 : 0));
-        const uint8_t * w = (const uint8_t *) W;
-        mi_f16_epilogue es = e;
-        es.stamps = mi_stamp_take("k_gemv_f16_m8", grid.x);
-#define MI_GEMV_M8(EP, NKWV, NWV) hipLaunchKernelGGL((k_gemv_f16_m8<EP, NKWV, NWV>), grid, dim3(64 * NWV), 0, s, w, nb01, K, N, x, (int) ncols, dst, ycol, es)
-#define MI_GEMV_M8_E(NKWV, NWV) switch (epi) { case 0: MI_GEMV_M8(0, NKWV, NWV); break; case 1: MI_GEMV_M8(1, NKWV, NWV); break; \
-                                                   case 2: MI_GEMV_M8(2, NKWV, NWV); break; default: MI_GEMV_M8(3, NKWV, NWV); break; }
-        if (nk <= 32) { MI_GEMV_M8_E(8, 4) } else { MI_GEMV_M8_E(16, 8) }
-#undef MI_GEMV_M8_E
-#undef MI_GEMV_M8
-#endif
-    } else if (!pro.mode && ncols > 1 && K <= 3072 && !xh && g_mi_tuning.f16_bp > 0 && (N + 3) / 4 < 4096) {
-        // several plain columns: 16 waves, 4 row groups x K split over 4 (k_gemv_f16_bn, JM = 0). Measured
-        // slower than k_gemv_f16 on batched decode (profiles/r06r_batched_plain_gemv_ab.txt): opt-in,
-        // f16_bp 1 is accepted by diagnostic builds only
-        const dim3 grid((unsigned) ((N + 15) / 16));
-        const size_t lds = (size_t) 8 * kp * sizeof(uint16_t) + (size_t) 16 * 4 * 8 * sizeof(float);
-        const int epi = e.gelu_table ? 3 : (e.resid ? 2 : (e.bias ? 1 : 0));
-        const uint8_t * w = (const uint8_t *) W;
-        mi_f16_epilogue es = e;
-        es.stamps = mi_stamp_take("k_gemv_f16_bp", grid.x);
-#define MI_GEMV_BP(EP, NCHT) hipLaunchKernelGGL((k_gemv_f16_bn<EP, 0, 16, 4, NCHT>), grid, dim3(1024), lds, s, w, nb01, K, N, x, ncols, dst, ycol, es, pro, kp)
-#define MI_GEMV_BP_E(NCHT) switch (epi) { case 0: MI_GEMV_BP(0, NCHT); break; case 1: MI_GEMV_BP(1, NCHT); break; \
-                                              case 2: MI_GEMV_BP(2, NCHT); break; default: MI_GEMV_BP(3, NCHT); break; }
-        if (K <= 1024) { MI_GEMV_BP_E(8) } else { MI_GEMV_BP_E(24) }
-#undef MI_GEMV_BP_E
-#undef MI_GEMV_BP
     } else if (pro.mode) {  // supported() guarantees one pass (K <= 3072)
         if (K <= 1024) launch_one<4>(per, W, nb01, K, N, x, xh, ncols, dst, ycol, e, pro, s, nc, ks, rgs);
         else launch_one<12>(per, W, nb01, K, N, x, xh, ncols, dst, ycol, e, pro, s, nc, ks, rgs);

@@ -26,80 +26,78 @@
 #include "mi355x_kernels.h"
 
 
+#include <ctype.h>
+#include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <string>
 
-static int env_int(const char * name, int def) {
-    const char * v = getenv(name);
-    return v ? atoi(v) : def;
+// The one list of knobs: set_tuning(name, v) and GGML_MI355X_<NAME>=v (read once at start-up) both go
+// through mi_tuning_set, so both accept lo <= v <= hi (and ok(v) where a knob takes only some values).
+namespace {
+constexpr int kAny = INT_MAX;
+struct knob {
+    const char * name;
+    int mi_tuning::*field;
+    int lo, hi;
+    bool (*ok)(int);
+};
+const knob kKnobs[] = {
+    {"mmv_blocks", &mi_tuning::mmv_blocks, 0, kAny, nullptr},
+    {"mmv_variant", &mi_tuning::mmv_variant, INT_MIN, kAny, nullptr},
+    {"f16_variant", &mi_tuning::f16_variant, INT_MIN, kAny, nullptr},
+    {"f16_threads", &mi_tuning::f16_threads, 0, 256, [](int v) { return v == 0 || v == 64 || v == 128 || v == 256; }},
+    {"mmq_variant", &mi_tuning::mmq_variant, INT_MIN, kAny, nullptr},
+    {"attn_variant", &mi_tuning::attn_variant, INT_MIN, kAny, nullptr},
+    {"mmv_order", &mi_tuning::mmv_order, -1, 1, nullptr},
+    {"f16_waves", &mi_tuning::f16_waves, 0, kAny, nullptr},
+    {"f16_rgs", &mi_tuning::f16_rgs, 0, 8, nullptr},
+    {"f16_ps_waves", &mi_tuning::f16_ps_waves, 0, 8, [](int v) { return v == 0 || v == 2 || v == 4 || v == 8; }},
+    {"xfirst", &mi_tuning::xfirst, -1, 1, nullptr},
+    {"f16_norm_waves", &mi_tuning::f16_norm_waves, 0, 8, nullptr},
+    {"planes", &mi_tuning::planes, 0, 1, nullptr},
+    {"f16_nc", &mi_tuning::f16_nc, 0, 88, [](int v) { return v % 10 <= 8; }},
+    {"f16_bn", &mi_tuning::f16_bn, 0, 15, [](int v) { return v % 10 <= 5; }},
+    {"q40r", &mi_tuning::q40r, 0, 1, nullptr},
+    {"q80r", &mi_tuning::q80r, 0, 1, nullptr},
+    {"mmv_pro4", &mi_tuning::mmv_pro4, 0, 1, nullptr},
+    {"f16_mt", &mi_tuning::f16_mt, 0, 1, nullptr},
+    {"mmqt_short", &mi_tuning::mmqt_short, 0, kAny, nullptr},
+    {"mmid_group", &mi_tuning::mmid_group, 0, 8, [](int v) { return v == 0 || v == 1 || v == 4 || v == 8; }},
+    {"mmid_stream", &mi_tuning::mmid_stream, 0, 8, nullptr},
+    {"fuse_router", &mi_tuning::fuse_router, 0, 1, nullptr},
+    {"ord_prefill_cols", &mi_tuning::ord_prefill_cols, 0, kAny, nullptr},
+    {"tree_prefill_cols", &mi_tuning::tree_prefill_cols, 0, kAny, nullptr},
+};
+
+bool knob_set(mi_tuning & t, const char * name, int value) {
+    for (const knob & k : kKnobs) {
+        if (strcmp(name, k.name) != 0) continue;
+        if (value < k.lo || value > k.hi || (k.ok && !k.ok(value))) return false;
+        t.*k.field = value;
+        return true;
+    }
+    return false;
 }
 
-// mmv_blocks == 0: size the grid from the kernel's residency (hipOccupancy...) per instance
-mi_tuning g_mi_tuning = {env_int("GGML_MI355X_MMV_BLOCKS", 0), env_int("GGML_MI355X_MMV_VARIANT", 0), env_int("GGML_MI355X_F16_VARIANT", 0), 0, env_int("GGML_MI355X_MMQ_VARIANT", 0), env_int("GGML_MI355X_ATTN_VARIANT", 0), env_int("GGML_MI355X_ATTN_ABL", 0), env_int("GGML_MI355X_MMV_ORDER", -1), env_int("GGML_MI355X_F16_WAVES", 0), env_int("GGML_MI355X_F16_RGS", 0), env_int("GGML_MI355X_F16_PS_WAVES", 0), env_int("GGML_MI355X_MMQ_LONG", 0), env_int("GGML_MI355X_XFIRST", -1), env_int("GGML_MI355X_F16_NORM_WAVES", 0), env_int("GGML_MI355X_PLANES", 0), env_int("GGML_MI355X_F16_NC", 10), env_int("GGML_MI355X_MMV_DMA", 0), env_int("GGML_MI355X_F16_BN", 5), env_int("GGML_MI355X_F16_BP", 0), env_int("GGML_MI355X_Q40R", 1), env_int("GGML_MI355X_Q80R", 1), env_int("GGML_MI355X_MMV_PRO4", 1), env_int("GGML_MI355X_F16_MT", 1), env_int("GGML_MI355X_F16_M8", 0), env_int("GGML_MI355X_MMQT_SHORT", 192), env_int("GGML_MI355X_MMID_GROUP", 1), env_int("GGML_MI355X_MMID_STREAM", 8), env_int("GGML_MI355X_FUSE_ROUTER", 1)};
+mi_tuning tuning_from_env() {
+    mi_tuning t;
+    for (const knob & k : kKnobs) {
+        std::string env = "GGML_MI355X_";
+        for (const char * c = k.name; *c; c++) env += (char) toupper((unsigned char) *c);
+        const char * v = getenv(env.c_str());
+        if (v && !knob_set(t, k.name, atoi(v))) fprintf(stderr, "%s=%s: value not accepted, keeping the default %d\n", env.c_str(), v, t.*k.field);
+    }
+    return t;
+}
+}  // namespace
+
+mi_tuning g_mi_tuning = tuning_from_env();
 thread_local int tl_mi_graph_order = 0;
 
-// ---- diagnostic phase stamps (make DIAG=1 builds; MI_STAMP in mi355x_common.h) ----
-// A device buffer of kMiStampSlots words per workgroup and launch; each instrumented launch takes
-// the next range (mi_stamp_take) and the host log records (kernel, workgroups, offset) so a tool
-// can rebuild the device timeline: per-launch first-start / last-end and per-workgroup phases.
-uint64_t * g_mi_stamp_dev = nullptr;
-static size_t g_mi_stamp_cap = 0, g_mi_stamp_cur = 0;
-static std::string g_mi_stamp_log;
-
-bool mi_stamps_enable(size_t slots) {
-#if MI_DIAG
-    if (g_mi_stamp_dev) (void) hipFree(g_mi_stamp_dev);
-    g_mi_stamp_dev = nullptr;
-    g_mi_stamp_cap = g_mi_stamp_cur = 0;
-    g_mi_stamp_log.clear();
-    if (slots == 0) return true;
-    if (hipMalloc(&g_mi_stamp_dev, slots * sizeof(uint64_t)) != hipSuccess) {
-        g_mi_stamp_dev = nullptr;
-        return false;
-    }
-    (void) hipMemset(g_mi_stamp_dev, 0, slots * sizeof(uint64_t));
-    g_mi_stamp_cap = slots;
-    return true;
-#else
-    (void) slots;
-    return false;  // release build: the kernels carry no stamps
-#endif
-}
-
-bool mi_diag_build() { return MI_DIAG != 0; }
-
-void mi_stamps_reset() {
-    g_mi_stamp_cur = 0;
-    g_mi_stamp_log.clear();
-}
-
-uint64_t * mi_stamp_take(const char * name, unsigned nblocks) {
-    if (!g_mi_stamp_dev) return nullptr;
-    const size_t need = (size_t) nblocks * kMiStampSlots;
-    if (g_mi_stamp_cur + need > g_mi_stamp_cap) return nullptr;
-    uint64_t * p = g_mi_stamp_dev + g_mi_stamp_cur;
-    char line[160];
-    snprintf(line, sizeof line, "%s %u %zu\n", name, nblocks, g_mi_stamp_cur);
-    g_mi_stamp_log += line;
-    g_mi_stamp_cur += need;
-    return p;
-}
-
-size_t mi_stamps_read(uint64_t * host, size_t n, char * log, size_t log_size) {
-    if (!g_mi_stamp_dev) return 0;
-    const size_t m = n < g_mi_stamp_cur ? n : g_mi_stamp_cur;
-    if (host && m) (void) hipMemcpy(host, g_mi_stamp_dev, m * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    if (log && log_size) {
-        const size_t k = g_mi_stamp_log.size() < log_size - 1 ? g_mi_stamp_log.size() : log_size - 1;
-        memcpy(log, g_mi_stamp_log.data(), k);
-        log[k] = 0;
-    }
-    return g_mi_stamp_cur;
-}
-
+bool mi_tuning_set(const char * name, int value) { return knob_set(g_mi_tuning, name, value); }
 
 // per-format launchers (mmv_fused_q4k.hip, _q5k, _q6k, _q40, _q80, _q41, _q50, _q51: one translation unit each)
 void mi_mmv_launch_q4k(const mi_mmv_group & g, int variant, hipStream_t s);

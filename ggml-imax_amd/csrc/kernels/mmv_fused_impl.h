@@ -1083,17 +1083,14 @@ __device__ void norm_prologue(const mi_mmv_group & g, const char * X, int ncols,
         float scale;
         if (g.pro.mode == 2) {
             const float mean = wave_mean_cpu_order<true, kJ>(r.v, K);
-            if (c == 0) MI_STAMP(g.stamps, 6);  // (diagnostic: first column's x landed, mean certified)
             scale = 1.0f / sqrtf(add_rn(mean, g.pro.eps));
         } else {
             const float mean = wave_mean_cpu_order<false, kJ>(r.v, K);
-            if (c == 0) MI_STAMP(g.stamps, 6);
 #pragma unroll
             for (int j = 0; j < kJ; j++) r.v[j] = sub_rn(r.v[j], mean);
             const float variance = wave_mean_cpu_order<true, kJ>(r.v, K);
             scale = 1.0f / sqrtf(add_rn(variance, g.pro.eps));
         }
-        if (c == 0) MI_STAMP(g.stamps, 5);  // (diagnostic: first column's scale)
 #pragma unroll
         for (int j = 0; j < kJ; j++) {
             const int64_t k = (int64_t) j * 64 + lane;
@@ -1233,11 +1230,9 @@ __device__ void norm_quant_prologue1(const mi_mmv_group & g, norm_cols4 & r, con
     float scale;
     if (g.pro.mode == 2) {
         const float mean = wave_mean_cpu_order4<true, kJ>(r.v, K);
-        MI_STAMP(g.stamps, 6);
         scale = 1.0f / sqrtf(add_rn(mean, g.pro.eps));
     } else {
         const float mean = wave_mean_cpu_order4<false, kJ>(r.v, K);
-        MI_STAMP(g.stamps, 6);
 #pragma unroll
         for (int j = 0; j < kJ; j++) {
             r.v[j].x = sub_rn(r.v[j].x, mean);
@@ -1248,7 +1243,6 @@ __device__ void norm_quant_prologue1(const mi_mmv_group & g, norm_cols4 & r, con
         const float variance = wave_mean_cpu_order4<true, kJ>(r.v, K);
         scale = 1.0f / sqrtf(add_rn(variance, g.pro.eps));
     }
-    MI_STAMP(g.stamps, 5);
     float y[kJ][4];
 #pragma unroll
     for (int j = 0; j < kJ; j++) {
@@ -1334,8 +1328,6 @@ __device__ __forceinline__ void store_out(const mi_mmv_group & g, float * dst, i
 template <class F, int NC, int PD, int IPL, bool TAIL, bool ORD, bool PRO, bool XF, int MR = 1, bool IDS = false>
 __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    MI_STAMP(g.stamps, 0);
-    if (!(PRO && g.pro.mode)) MI_STAMP_CLK(g.stamps, 6);  // (norm prologue: slots 6, 5 time its phases)
     constexpr int NB = PD + 1;  // ring slots
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -1454,11 +1446,9 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
     if (PRO && g.pro.mode && p4) {
         // (the activations complete in LDS once wave 0 is through: the barrier below publishes them)
         if (wave == 0) norm_quant_prologue1(g, nc4, act);
-        MI_STAMP(g.stamps, 2);
     } else if (PRO && g.pro.mode) {
         float * xn = (float *) (lds + g.pro_off);
         if (wave == 0) norm_prologue(g, X, ncols, xn, nc0);
-        MI_STAMP(g.stamps, 2);  // (norm prologue: slot 2 = wave 0's norm done, instead of the barrier below)
         __syncthreads();
         Xq = (const char *) xn;
         xcolq = (size_t) K * sizeof(float);
@@ -1488,7 +1478,6 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
             }
         }
     }
-    MI_STAMP(g.stamps, 1);  // wave 0's activation slices loaded and quantized
     if constexpr (XF && PRO) {
 #pragma unroll
         for (int u = 0; u < PD; u++) {
@@ -1497,7 +1486,6 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
         }
     }
     __syncthreads();
-    if (!(PRO && g.pro.mode)) MI_STAMP(g.stamps, 2);  // every wave's
 
     if constexpr (MR > 1) {
         static_assert(NC == 1 && IPL == 1 && !TAIL, "multi-row steps: one column, one item per lane");
@@ -1521,14 +1509,12 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
                     if (it < nitems) F::template dot_ord<1>(ring[u][0], it, it, act, K, ncols, scr + (slot * MR + rr) * cs, cs, S);
                     if (slot == RS - 1 || k == nsteps - 1) {  // wave-uniform
                         sync();
-                        if (k == nsteps - 1) MI_STAMP(g.stamps, 3);
                         const int r = lane >> 3, ll = lane & 7;
                         const int jr = (k - slot) * MR + r;
                         const bool mine = r < (slot + 1) * MR && jr < nrows;
                         float A = 0.0f, M = 0.0f;
-                        if (mine && !g.abl) F::chain(scr + r * cs, ll, nitems, S, A, M);
+                        if (mine) F::chain(scr + r * cs, ll, nitems, S, A, M);
                         const float v = F::finish(A, M);
-                        if (k == nsteps - 1) MI_STAMP(g.stamps, 4);
                         if (ll == 0 && mine) store_out<PRO, 1>(g, dst, 0, row_begin + 4 * jr + wave, v, &epre);
                         sync();
                     }
@@ -1544,7 +1530,6 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
                     v += f(mi_dpp<MI_DPP_ROW_HALF_MIRROR>(0, i(v)));
                     v += f(mi_dpp<MI_DPP_ROW_MIRROR>(0, i(v)));
                     if (it == 0 && j < nrows) store_out<PRO, 1>(g, dst, 0, row_begin + 4 * j + wave, v, &epre);
-                    if (k == 0) MI_STAMP(g.stamps, 3);
                 }
             }
         }
@@ -1581,7 +1566,7 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
                     float A = 0.0f, M = 0.0f;
                     auto chunk_done = [&](int base) {
                         sync();
-                        if (cl < ncols && !g.abl) F::chain(scr + cl * cs, ll, min(64, nitems - base), S, A, M);
+                        if (cl < ncols) F::chain(scr + cl * cs, ll, min(64, nitems - base), S, A, M);
                         sync();
                     };
 #pragma unroll
@@ -1626,13 +1611,11 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
                 }
                 if (slot == R - 1 || k == nrows - 1) {  // wave-uniform
                     sync();
-                    if (k == nrows - 1) MI_STAMP(g.stamps, 3);  // (reference order) the last rows' lane sums in the scratch
                     const int r = lane / (8 * NC), cl = (lane >> 3) % NC, ll = lane & 7;
                     const bool mine = r <= slot && cl < ncols;
                     float A = 0.0f, M = 0.0f;
-                    if (mine && !g.abl) F::chain(scr + (r * NC + cl) * cs, ll, nitems, S, A, M);
+                    if (mine) F::chain(scr + (r * NC + cl) * cs, ll, nitems, S, A, M);
                     const float v = F::finish(A, M);
-                    if (k == nrows - 1) MI_STAMP(g.stamps, 4);  // (reference order) chains done
                     if (ll == 0 && mine) {
                         store_out<PRO, NC>(g, dst, cl, row_begin + 4 * (k - slot + r) + wave, v, &epre);
                     }
@@ -1667,164 +1650,10 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
                 const float v = mi_wave_sum_u(acc[c]);
                 if (lane == 0 && c < ncols) store_out<PRO, NC>(g, dst, c, row, v, &epre);
             }
-            if (k == 0) MI_STAMP(g.stamps, 3);  // first row reduced and stored
         }
     }
     }
-    if (!(PRO && g.pro.mode)) MI_STAMP_CLK(g.stamps, 5);
-    MI_STAMP(g.stamps, 7);
 }
-
-// ------------------------------------------------------------------ LDS-DMA weight stream (round 6)
-#if MI_DIAG
-// k_mmv_dma: the tree-order Q4_K GEMV of one column with the weights moved by LDS-DMA. Measured
-// (profiles/r06h_gemv_lds_dma_ab.txt, headline workload): 5.6-6.0 TB/s against k_mmv_stream's
-// 6.2-6.3 on the same box (nt 3-7 % faster than the default policy); diagnostic builds only.
-// Design:
-// (global_load_lds_dwordx4, 1 KB per wave-instruction, every weight byte fetched exactly once --
-// k_mmv_stream's lanes load each 16-byte superblock header four times) into wave-private rings,
-// optionally with the nontemporal policy (NT; the guide's nt-weights row: LDS-DMA streams reach
-// 6.5-6.8 TB/s chip-wide nt, 6.4 default, MI355X_MICROARCH.md "ldsdma-fill"). Wave w of a workgroup
-// owns a contiguous run of rows, i.e. a contiguous byte stream (rows of 144 K / 256 bytes, packed);
-// a ring slot is a group of 4 rows = 9 x 1 KB pieces for K = 4096 (GR = 4 rows x BS x K / 256 / 1024
-// pieces; K = 4096 only, as the waits' immediates assume), G slots, G - 1 groups in flight. The dot products read the
-// slot with ds_read_b128 and use FmtKQ's arithmetic (the same per-item sums and wave reduction as
-// k_mmv_stream: the same bits); the 4 rows' results leave as one 16-byte store by lane 0. The DMAs
-// are inline asm outside the compiler's vmcnt bookkeeping: per group a wave issues exactly GR DMAs
-// and one store, so "group g landed" is s_waitcnt vmcnt((G - 1) (GR + 1)).
-__device__ __forceinline__ uint32_t mi_lds_addr_u8(const uint8_t * p) {  // LDS byte address, wave-uniform
-    return (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) (uintptr_t) p);
-}
-__device__ __forceinline__ void mi_glds16_nt(const void * gsrc, uint32_t lds) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds));
-}
-__device__ __forceinline__ void mi_glds16_dflt(const void * gsrc, uint32_t lds) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds));
-}
-template <int G> struct dma_wait;
-template <> struct dma_wait<2> { __device__ static void run() { asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); } };
-template <> struct dma_wait<3> { __device__ static void run() { asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); } };
-template <> struct dma_wait<4> { __device__ static void run() { asm volatile("s_waitcnt vmcnt(30)" ::: "memory"); } };
-
-constexpr int kDmaRowsPerGroup = 4;
-
-template <int NW, int G, bool NT>
-__global__ __launch_bounds__(64 * NW) void k_mmv_dma(mi_mmv_group g) {
-    using F = FmtKQ<false>;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    constexpr int64_t K = 4096;
-    constexpr int nsl = K / 256;
-    constexpr int RB = nsl * F::BS;                   // row bytes (rows packed: nb01 == RB)
-    constexpr int GB = kDmaRowsPerGroup * RB;         // group bytes
-    constexpr int GR = GB / 1024;                     // DMA pieces per group
-    static_assert(GB % 1024 == 0 && GR == 9, "dma_wait assumes 9 pieces + 1 store per group");
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int member = blockIdx.x / g.blocks_per_member;
-    const int rb = blockIdx.x - member * g.blocks_per_member;
-    const uint8_t * W = (const uint8_t *) g.m[member].W;
-    const char * X = g.m[member].X;
-    float * dst = g.m[member].dst;
-    const lds_act act = lds_carve<256>(lds, 1, K);
-    uint8_t * ring = lds + ord_offset(lds_bytes<256>(1, K)) + (size_t) wave * G * GB;
-
-    // rows of this workgroup, then of this wave (contiguous, whole groups except the member's last)
-    const int Nr = (int) g.N;
-    const int row_begin = rb * (int) g.rows_per_block;
-    const int row_end = min(row_begin + (int) g.rows_per_block, Nr);
-    const int rpw = (int) g.rows_per_block / NW;  // a multiple of kDmaRowsPerGroup (launcher)
-    const int r0 = min(row_begin + wave * rpw, row_end), r1 = min(r0 + rpw, row_end);
-    const int ngroups = (r1 - r0 + kDmaRowsPerGroup - 1) / kDmaRowsPerGroup;
-    const uint8_t * wbase = W + (size_t) r0 * RB;
-    const uint8_t * wlast = W + (size_t) Nr * RB - 16;  // (clamp: pieces past the member's end re-read its last bytes)
-    auto issue = [&](int grp) {
-        const int gc = grp < ngroups ? grp : (ngroups > 0 ? ngroups - 1 : 0);  // (past the end: the last group again)
-        const uint8_t * src = wbase + (size_t) gc * GB + 16 * lane;
-        const uint32_t dsts = mi_lds_addr_u8(ring + (grp % G) * GB);
-#pragma unroll
-        for (int p = 0; p < GR; p++) {
-            const uint8_t * a = src + 1024 * p;
-            a = a < wlast ? a : wlast;
-            if constexpr (NT) mi_glds16_nt(a, dsts + 1024 * p);
-            else mi_glds16_dflt(a, dsts + 1024 * p);
-        }
-    };
-
-    // activations: the column's slices quantized into LDS by every wave (as k_mmv_stream), requested
-    // before the first groups' DMAs
-    auto load_round = [&](float4 (&v)[4], int p0) {
-        const int p = min(p0 + (lane >> 4), nsl - 1);
-        const float4 * src = (const float4 *) (X + ((size_t) p * 256 + (lane & 15) * 16) * sizeof(float));
-#pragma unroll
-        for (int u = 0; u < 4; u++) v[u] = src[u];
-    };
-    float4 xfirst[4];
-    load_round(xfirst, 4 * wave);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the compiler does not count the DMAs below)
-    for (int grp = 0; grp < G - 1; grp++) issue(grp);
-    for (int p0 = 4 * wave; p0 < nsl; p0 += 4 * NW) {
-        float4 v[4];
-        if (p0 == 4 * wave) {
-#pragma unroll
-            for (int u = 0; u < 4; u++) v[u] = xfirst[u];
-        } else {
-            load_round(v, p0);
-        }
-        const int p = min(p0 + (lane >> 4), nsl - 1);
-        quantize_row16(v, lane, act, K, 0, p, p0 + (lane >> 4) < nsl);
-    }
-    __syncthreads();
-    // this lane's item (superblock s, 64-group j) is the same in every row: its activation operands
-    // stay in registers
-    const int s = lane >> 2, j = lane & 3;
-    int alo[8], ahi[8];
-    {
-        const int4 * p = (const int4 *) (act.qs + (int64_t) s * 256 + 64 * j);
-        const int4 a0 = p[0], a1 = p[1], a2 = p[2], a3 = p[3];
-        const int l8[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-        const int h8[8] = {a2.x, a2.y, a2.z, a2.w, a3.x, a3.y, a3.z, a3.w};
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            alo[i] = l8[i];
-            ahi[i] = h8[i];
-        }
-    }
-    const int ss = *(const int *) (act.s32 + s * 8 + 2 * j);
-    const float ad = act.d[s];
-    const uint32_t ioff = (uint32_t) (s * F::BS);
-
-    // stream: group grp in slot grp % G; its refill (group grp + G - 1) issued first
-    for (int grp = 0; grp < ngroups; grp++) {
-        issue(grp + G - 1);
-        dma_wait<G>::run();
-        const uint8_t * slot = ring + (grp % G) * GB + ioff;
-        typename F::Regs rg[kDmaRowsPerGroup];
-#pragma unroll
-        for (int r = 0; r < kDmaRowsPerGroup; r++) {
-            rg[r].hdr = *(const uint4 *) (slot + r * RB);
-            rg[r].qa = *(const uint4 *) (slot + r * RB + 16 + 32 * j);
-            rg[r].qb = *(const uint4 *) (slot + r * RB + 32 + 32 * j);
-        }
-        float res[kDmaRowsPerGroup];
-#pragma unroll
-        for (int r = 0; r < kDmaRowsPerGroup; r++) res[r] = mi_wave_sum_u(F::item_dot(rg[r], j, alo, ahi, ss, ad, 0.0f));
-        const int row = r0 + kDmaRowsPerGroup * grp;
-        if (lane == 0) {
-            if (row + kDmaRowsPerGroup <= r1) {
-                *(float4 *) (dst + row) = make_float4(res[0], res[1], res[2], res[3]);
-            } else {
-                for (int r = 0; r < kDmaRowsPerGroup; r++)
-                    if (row + r < r1) dst[row + r] = res[r];
-            }
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the re-read DMAs past the end have landed)
-}
-#endif  // MI_DIAG
 
 // Workgroups that fit on the chip at once for this kernel instance (all of them are launched
 // in one wave, so no workgroup waits for another to retire). Speed only: nothing relies on
@@ -1916,46 +1745,10 @@ void launch_one(mi_mmv_group g, hipStream_t s) {
     rows = (rows + 3) / 4 * 4;
     g.rows_per_block = rows;
     g.blocks_per_member = (int) ((g.N + rows - 1) / rows);
-    g.stamps = mi_stamp_take(ORD ? "k_mmv_stream_ord" : "k_mmv_stream", (unsigned) (g.blocks_per_member * g.n));
     hipLaunchKernelGGL((k_mmv_stream<F, NC, PD, IPL, TAIL, ORD, PRO, XF, MR, IDS>), dim3((unsigned) (g.blocks_per_member * g.n)), dim3(256), lds,
                        s, g);
 }
 
-#if MI_DIAG
-// k_mmv_dma for a group (tree order, one column, packed Q4_K rows, K = 4096); false: not taken.
-// mmv_dma: 1 = 4 waves x 3 slots, 2 = 8 waves x 2 slots, 3 = 4 waves x 4 slots (+10: default load
-// policy instead of nontemporal); one workgroup per CU
-bool launch_dma(mi_mmv_group g, hipStream_t s) {
-    const int v = g_mi_tuning.mmv_dma;
-    const int64_t RB = g.K / 256 * 144;
-    if (g.K != 4096 || (int64_t) g.nb01 != RB || g.N >= (1 << 30)) return false;  // (9 pieces per group: the waits' immediates)
-    for (int i = 0; i < g.n; i++)
-        if (((uintptr_t) g.m[i].dst | (uintptr_t) g.m[i].W) % 16 != 0) return false;
-    const int shape = v % 10;
-    const bool nt = v < 10;
-    const int NW = shape == 2 ? 8 : 4, G = shape == 2 ? 2 : shape == 3 ? 4 : 3;
-    const size_t lds = ord_offset(lds_bytes<256>(1, g.K)) + (size_t) NW * G * 4 * RB;
-    if (lds > 160 * 1024) return false;
-    const int target = mi_cu_count();
-    int bpm = target / g.n;
-    if (bpm < 1) bpm = 1;
-    int64_t rows = (g.N + bpm - 1) / bpm;
-    const int64_t unit = (int64_t) NW * kDmaRowsPerGroup;
-    rows = (rows + unit - 1) / unit * unit;
-    g.rows_per_block = rows;
-    g.blocks_per_member = (int) ((g.N + rows - 1) / rows);
-    const void * fn;
-#define MI_DMA_K(NW_, G_, NT_) (const void *) k_mmv_dma<NW_, G_, NT_>
-    if (NW == 8) fn = nt ? MI_DMA_K(8, 2, true) : MI_DMA_K(8, 2, false);
-    else if (G == 4) fn = nt ? MI_DMA_K(4, 4, true) : MI_DMA_K(4, 4, false);
-    else fn = nt ? MI_DMA_K(4, 3, true) : MI_DMA_K(4, 3, false);
-#undef MI_DMA_K
-    (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    const dim3 grid((unsigned) (g.blocks_per_member * g.n)), block((unsigned) (64 * NW));
-    void * args[] = {&g};
-    return hipLaunchKernel(fn, grid, block, args, lds, s) == hipSuccess;
-}
-#endif  // MI_DIAG
 
 template <class F, int NC, int PD, int IPL, bool ORD, bool XF = false>
 void launch_tail(const mi_mmv_group & g, hipStream_t s) {
@@ -1989,11 +1782,6 @@ void launch_stream(const mi_mmv_group & g, int variant, hipStream_t s) {
             return;
         }
     }
-#if MI_DIAG  // measured slower (profiles/r06h_gemv_lds_dma_ab.txt): diagnostic builds only
-    if constexpr (NC == 1 && !ORD && std::is_same<F, FmtKQ<false>>::value) {
-        if (!pro_epi && g_mi_tuning.mmv_dma > 0 && launch_dma(g, s)) return;
-    }
-#endif
     if constexpr (NC == 1) {
         // tall lone members with rows of <= 16 items (GPT-2 lm_head: 50257 x 768, 12 Q4_K items per
         // row): four rows per wave step on 16 lanes each (MR = 4); variant 9x: the one-row form
@@ -2047,12 +1835,8 @@ void launch_stream_nc(const mi_mmv_group & g, int variant, hipStream_t s) {
 
 template <class F>
 void launch_stream_ord(const mi_mmv_group & g, int variant, hipStream_t s) {
-    if (mi_mmv_order()) {
-        mi_mmv_group h = g;
-        h.abl = mi_mmv_order() == 2;
-        launch_stream_nc<F, true>(h, variant, s);
-    } else
-        launch_stream_nc<F, false>(g, variant, s);
+    if (mi_mmv_order()) launch_stream_nc<F, true>(g, variant, s);
+    else launch_stream_nc<F, false>(g, variant, s);
 }
 
 

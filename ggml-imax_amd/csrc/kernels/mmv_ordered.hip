@@ -709,7 +709,7 @@ __global__ __launch_bounds__(kAttnThreads) void k_attn_ordered(mi_attn_desc a, c
 // KVCAP: the key-count bucket the launch was sized for (n_kv <= KVCAP), so only the key rounds and
 // V-slab loads the context needs are issued. q / K loads are 16-byte vector loads (host-checked
 // contiguity and alignment): at decode the load phase is issue-bound on only H workgroups.
-template <int D, int KVCAP, int ABL = 0>
+template <int D, int KVCAP>
 __global__ __launch_bounds__(512) void k_attn_fast(mi_attn_desc a, const uint16_t * __restrict__ exp_table) {
     constexpr int KVMAX = KVCAP;               // keys this instantiation serves
     constexpr int KR = KVMAX / 128;            // key rounds of the 128 quads
@@ -778,10 +778,6 @@ __global__ __launch_bounds__(512) void k_attn_fast(mi_attn_desc a, const uint16_
             p[k] = mul_rn(w, a.sm_scale);
         }
     }
-    if constexpr (ABL == 3) {  // timing ablation: loads + KQ only
-        if (q == 0 && quad < n_kv) *(float *) (a.out + (size_t) quad * 4) = p[quad] + vr[0].x + vr[VREG - 1].w;
-        return;
-    }
     // ---- 3. V slab into LDS
 #pragma unroll
     for (int i = 0; i < VREG; i++) {
@@ -810,7 +806,7 @@ __global__ __launch_bounds__(512) void k_attn_fast(mi_attn_desc a, const uint16_
     double ssum = 0.0;
     for (int k = tid; k < n_kv; k += 512) {
         const float w = p[k];
-        const float v = w == -INFINITY ? 0.0f : (ABL == 1 ? sub_rn(w, mx) : mi_h2f(exp_table[mi_f2h(sub_rn(w, mx))]));
+        const float v = w == -INFINITY ? 0.0f : mi_h2f(exp_table[mi_f2h(sub_rn(w, mx))]);
         p[k] = v;
         ssum += (double) v;  // fp16 values: every partial double sum is exact
     }
@@ -824,10 +820,6 @@ __global__ __launch_bounds__(512) void k_attn_fast(mi_attn_desc a, const uint16_
     for (int k = tid; k < n_kv; k += 512) p[k] = mul_rn(p[k], inv);
     __syncthreads();
 
-    if constexpr (ABL == 2) {  // timing ablation: no KQV
-        if (tid < D) *(float *) (a.out + (size_t) tid * a.o_nb[0] + (size_t) t * a.o_nb[1] + (size_t) h * a.o_nb[2]) = p[tid];
-        return;
-    }
     // ---- 5. KQV[d] = ggml_vec_dot_f32(n_kv, V_trans[:, d, h], p) from LDS, quad d
     const int npv = n_kv & ~31;
     for (int d0 = 0; d0 < D; d0 += 128) {
@@ -941,8 +933,7 @@ void mi_attn_ordered(const mi_attn_desc & a, const uint16_t * exp_table, hipStre
     static const bool lds_ok = [] {  // the V slab needs more than the default 64 KB of dynamic LDS
         bool ok = true;
         for (const void * f : {(const void *) k_attn_fast<64, 128>, (const void *) k_attn_fast<64, 256>, (const void *) k_attn_fast<64, 512>,
-                               (const void *) k_attn_fast<128, 128>, (const void *) k_attn_fast<128, 256>,
-                               (const void *) k_attn_fast<64, 512, 1>, (const void *) k_attn_fast<64, 512, 2>, (const void *) k_attn_fast<64, 512, 3>})
+                               (const void *) k_attn_fast<128, 128>, (const void *) k_attn_fast<128, 256>})
             ok &= hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess;
         (void) hipGetLastError();
         return ok;
@@ -953,14 +944,6 @@ void mi_attn_ordered(const mi_attn_desc & a, const uint16_t * exp_table, hipStre
     const dim3 grid((unsigned) a.H, (unsigned) a.N);
     if (fast_ok && a.D == 64 && a.n_kv <= 512) {
         const size_t lds = (size_t) a.n_kv * (64 + 2) * sizeof(float);
-#if MI_DIAG
-        switch (g_mi_tuning.attn_abl) {  // timing ablations only (results invalid): make DIAG=1
-            case 1: hipLaunchKernelGGL((k_attn_fast<64, 512, 1>), grid, dim3(512), lds, s, a, exp_table); return;
-            case 2: hipLaunchKernelGGL((k_attn_fast<64, 512, 2>), grid, dim3(512), lds, s, a, exp_table); return;
-            case 3: hipLaunchKernelGGL((k_attn_fast<64, 512, 3>), grid, dim3(512), lds, s, a, exp_table); return;
-            default: break;
-        }
-#endif
         if (a.n_kv <= 128) hipLaunchKernelGGL((k_attn_fast<64, 128>), grid, dim3(512), lds, s, a, exp_table);
         else if (a.n_kv <= 256) hipLaunchKernelGGL((k_attn_fast<64, 256>), grid, dim3(512), lds, s, a, exp_table);
         else hipLaunchKernelGGL((k_attn_fast<64, 512>), grid, dim3(512), lds, s, a, exp_table);

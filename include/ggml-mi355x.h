@@ -77,9 +77,10 @@ GGML_API void ggml_backend_mi355x_graph_stats(ggml_backend_t backend, int64_t * 
 // captures; fills min(n, available) entries and returns that count
 GGML_API int ggml_backend_mi355x_graph_stats_ex(ggml_backend_t backend, int64_t * stats, int n);
 
-// Launch-shape knobs of the streaming kernels, for A/B tuning inside one process:
-// "mmv_blocks" (resident workgroups of the fused GEMV), "mmv_variant" (see mi355x_kernels.h).
-// Returns false for an unknown name.
+// Launch-shape knobs of the kernels, for A/B tuning inside one process: "mmv_blocks" (resident
+// workgroups of the fused GEMV), "mmv_variant", ... (the fields of mi_tuning, mi355x_kernels.h).
+// GGML_MI355X_<NAME>=value in the environment sets the same knob at start-up, with the same range
+// check. Returns false for an unknown name or a value the knob does not accept.
 GGML_API bool ggml_backend_mi355x_set_tuning(const char * name, int value);
 
 // Runs the device activation quantizer that GGML_OP_MUL_MAT uses for `vec_dot_type`
@@ -90,16 +91,6 @@ GGML_API bool ggml_backend_mi355x_set_tuning(const char * name, int value);
 GGML_API bool ggml_backend_mi355x_quantize_activations(ggml_backend_t backend, int vec_dot_type, const float * x,
                                                        int64_t K, int64_t ncols, int8_t * qs, float * d, int16_t * s32);
 
-// Device phase stamps (diagnostic builds, `make -C ggml-imax_amd diaglib`): with slots > 0 the
-// decode kernels (k_mmv_stream, the F16 GEMVs, k_attn_proj, k_get_rows_add) write s_memrealtime
-// stamps (100 MHz chip clock) of every workgroup's first wave into a device buffer of `slots` words,
-// 8 per workgroup and launch, in launch order; slots = 0 turns them off. Returns false in release
-// builds (whose kernels carry no stamps). _read copies up to n words into `words` and the launch
-// log ("kernel workgroups offset" lines) into `log`, and returns the number of words written since
-// the last _reset.
-GGML_API bool ggml_backend_mi355x_stamps_enable(size_t slots);
-GGML_API void ggml_backend_mi355x_stamps_reset(void);
-GGML_API size_t ggml_backend_mi355x_stamps_read(uint64_t * words, size_t n, char * log, size_t log_size);
 // Repacked MFMA planes of Q4_K / Q5_K weights kept for long prompts (no reference counterpart: the
 // reference's CPU mul_mat dequantizes per call): how many weight tensors carry them, and their bytes
 GGML_API size_t ggml_backend_mi355x_planes_stats(size_t * bytes);

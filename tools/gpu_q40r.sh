@@ -9,5 +9,5 @@ tail -3 $OUT/pytest.log
 timeout -k 10 300 python -u tools/q40r_ab.py 3 > $OUT/ab.txt 2>&1
 cat $OUT/ab.txt
 # k_mmqt (128 x 64 tiles, K split over wave pairs) against k_mmqp at short-prompt widths
-PF_TYPES=q4_K PF_R=32 MMQ_VARIANTS=0,131200 PF_LONG=0 timeout -k 10 300 python -u tools/prefill_bench.py 64 128 32 > $OUT/pf_mmqt_short.txt 2>&1
+PF_TYPES=q4_K PF_R=32 MMQ_VARIANTS=0,131200 timeout -k 10 300 python -u tools/prefill_bench.py 64 128 32 > $OUT/pf_mmqt_short.txt 2>&1
 cat $OUT/pf_mmqt_short.txt
