@@ -17,6 +17,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <dlfcn.h>
+
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -39,14 +41,11 @@
         }                                                                                               \
     } while (0)
 
-#define MI_ASSERT(x)                                                                                    \
-    do {                                                                                                \
-        if (!(x)) {                                                                                     \
-            fflush(stdout);                                                                             \
-            fprintf(stderr, "ggml-mi355x: assertion failed at %s:%d: %s\n", __FILE__, __LINE__, #x);  \
-            abort();                                                                                    \
-        }                                                                                               \
-    } while (0)
+// the kernels' names of the ggml types (mi355x_types.h) are the ABI's values
+static_assert(MI_TYPE_F32 == GGML_TYPE_F32 && MI_TYPE_F16 == GGML_TYPE_F16 && MI_TYPE_Q4_0 == GGML_TYPE_Q4_0 && MI_TYPE_Q4_1 == GGML_TYPE_Q4_1 &&
+              MI_TYPE_Q5_0 == GGML_TYPE_Q5_0 && MI_TYPE_Q5_1 == GGML_TYPE_Q5_1 && MI_TYPE_Q8_0 == GGML_TYPE_Q8_0 && MI_TYPE_Q8_1 == GGML_TYPE_Q8_1 &&
+              MI_TYPE_Q4_K == GGML_TYPE_Q4_K && MI_TYPE_Q5_K == GGML_TYPE_Q5_K && MI_TYPE_Q6_K == GGML_TYPE_Q6_K && MI_TYPE_Q8_K == GGML_TYPE_Q8_K &&
+              MI_TYPE_I32 == GGML_TYPE_I32, "mi355x_types.h names ggml_type values");
 
 static constexpr size_t kBufferAlign = 256;   // tensor alignment inside device buffers
 static constexpr size_t kBufferSlack = 256;   // tail slack: kernels may over-read < 16 B past a row
@@ -413,10 +412,27 @@ static const ggml_backend_buffer_type_i k_mi_split_buft_i = {
 // backend context
 // ---------------------------------------------------------------------------------------------
 
+// The form a mul_mat's activation columns are converted to: how they are quantized (the weight
+// type's vec_dot_type; MI_ACT_NONE: src1 is read as it lies, F32 weights) and how they are laid out.
+// Valid pairs: q8_0 / q8_1 / q8_K in SOA; q8_0 / q8_K in ROWS, BLOCKED (their f16 expansion
+// f16(d * q), the operand of mmq.hip) and MFMA; f16 in ROWS and BLOCKED (plain f16 values).
+enum mi_act_layout : int {
+    MI_LAYOUT_SOA,      // the GEMVs' structure-of-arrays (mi_act_q8)
+    MI_LAYOUT_ROWS,     // f16, row-major [ncols][K]
+    MI_LAYOUT_BLOCKED,  // f16, the GEMM's K-blocked layout [K/16][ncols][16]
+    MI_LAYOUT_MFMA,     // the int8-MFMA layouts of the exact prefill GEMMs (mi_act_mmx, mmq_exact.hip)
+};
+struct mi_act_format {
+    mi_act_quant quant = MI_ACT_NONE;
+    mi_act_layout layout = MI_LAYOUT_SOA;
+    bool operator==(const mi_act_format & o) const { return quant == o.quant && layout == o.layout; }
+    bool operator!=(const mi_act_format & o) const { return !(*this == o); }
+};
+
 struct mi_act_cache_entry {
     const void * data;   // src1 data
     size_t nbytes;
-    int kind;            // 0 = q8_0, 1 = q8_K, 2 = f16
+    mi_act_format format;
     int64_t ne[4];
     size_t nb[4];
     void * dev;          // converted activations in scratch
@@ -512,24 +528,23 @@ static void scratch_reserve(mi_backend_ctx * ctx, size_t bytes) {
 // conformance harness does)
 // ---------------------------------------------------------------------------------------------
 
-static bool is_legacy_q1(ggml_type t) { return t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1; }
-
-static bool mm_src0_supported(ggml_type t) {
-    return is_legacy_q1(t) || t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K ||
-           t == GGML_TYPE_F16 || t == GGML_TYPE_F32;
-}
+// every row of the weight-type table has a mul_mat
+static bool mm_src0_supported(ggml_type t) { return mi_type(t).type == t; }
 
 static bool is_f32(const ggml_tensor * t) { return t && t->type == GGML_TYPE_F32; }
 static bool is_f16_or_f32(const ggml_tensor * t) { return t && (t->type == GGML_TYPE_F32 || t->type == GGML_TYPE_F16); }
 
 // the quantized vec_dot_type a src1 may already have for weight type t (GGML_TYPE_COUNT: none)
 static ggml_type q8_src1_type(ggml_type t) {
-    switch (t) {
-        case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: return GGML_TYPE_Q8_K;
-        case GGML_TYPE_Q4_0: case GGML_TYPE_Q8_0: case GGML_TYPE_Q5_0: return GGML_TYPE_Q8_0;
-        case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_1: return GGML_TYPE_Q8_1;
-        default: return GGML_TYPE_COUNT;
-    }
+    const mi_act_quant q = mi_type(t).act;
+    return q == MI_ACT_NONE || q == MI_ACT_F16 ? GGML_TYPE_COUNT : (ggml_type) mi_act_type(q);
+}
+
+// the q8 quantization whose rows have type t (MI_ACT_NONE: t is no such type)
+static mi_act_quant q8_quant_of(ggml_type t) {
+    for (const mi_act_quant q : {MI_ACT_Q8_0, MI_ACT_Q8_1, MI_ACT_Q8_K})
+        if (mi_act_type(q) == t) return q;
+    return MI_ACT_NONE;
 }
 
 static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
@@ -594,16 +609,14 @@ static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
                     return false;
             }
         case GGML_OP_GET_ROWS:
-            return (is_f16_or_f32(a) || is_legacy_q1(a->type) || a->type == GGML_TYPE_Q4_0 || a->type == GGML_TYPE_Q8_0 || a->type == GGML_TYPE_Q4_K ||
-                    a->type == GGML_TYPE_Q5_K || a->type == GGML_TYPE_Q6_K) &&
-                   b->type == GGML_TYPE_I32 && is_f32(op);
+            return mi_type(a->type).get_rows && b->type == GGML_TYPE_I32 && is_f32(op);
         case GGML_OP_CPY:
         case GGML_OP_DUP:
         case GGML_OP_CONT:
             // F32 -> Q8_K / Q8_0 / Q8_1 (from_float = quantize_row_q8_K / _q8_0 / _q8_1): whole rows of blocks
-            if (is_f32(a) && (op->type == GGML_TYPE_Q8_K || op->type == GGML_TYPE_Q8_0 || op->type == GGML_TYPE_Q8_1))
+            if (is_f32(a) && q8_quant_of(op->type) != MI_ACT_NONE)
                 return ggml_are_same_shape(a, op) && a->nb[0] == sizeof(float) && op->nb[0] == ggml_type_size(op->type) &&
-                       op->ne[0] % (op->type == GGML_TYPE_Q8_K ? 256 : 32) == 0;
+                       op->ne[0] % mi_act_block(q8_quant_of(op->type)) == 0;
             return is_f16_or_f32(a) && is_f16_or_f32(op);
         case GGML_OP_ROPE: {
             const int32_t * pp = (const int32_t *) op->op_params;
@@ -626,25 +639,25 @@ static bool mi_offload_op(ggml_backend_t, const ggml_tensor * op) {
 // GGML_OP_MUL_MAT
 // ---------------------------------------------------------------------------------------------
 
-static int act_kind(ggml_type wtype) {
-    switch (wtype) {
-        case GGML_TYPE_Q4_0: case GGML_TYPE_Q8_0: case GGML_TYPE_Q5_0: return 0;
-        case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: return 1;
-        case GGML_TYPE_F16: return 2;
-        case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_1: return 10;
-        default: return -1;
-    }
+// the activations of weight type t as its GEMV reads them: q8 SoA, or f16 rows
+static mi_act_format act_format_of(ggml_type t) {
+    const mi_act_quant q = mi_type(t).act;
+    return {q, q == MI_ACT_F16 ? MI_LAYOUT_ROWS : MI_LAYOUT_SOA};
 }
 
-// kinds: 0 q8_0, 1 q8_K, 2 f16, 3/4 q8_0/q8_K quants expanded to f16(d * q) (mmq.hip operand),
-// 5/6/7 = 2/3/4 in the GEMM's K-blocked layout [K/16][ncols][16], 8 q8_K / 9 q8_0 in the int8-MFMA
-// layouts of the exact prefill GEMMs (mmq_exact.hip), 10 q8_1 (q8_0 plus the blocks' s; the GEMVs only)
-static size_t act_bytes(int kind, int64_t K, int64_t ncols) {
-    if (kind == 10) return mi_act_q8_bytes(K, ncols, false, true);
-    if (kind == 8) return mi_act_mmx_bytes(K, ncols);
-    if (kind == 9) return mi_act_mmx0_bytes(K, ncols);
-    if (kind >= 2) return (size_t) K * ncols * 2;
-    return mi_act_q8_bytes(K, ncols, kind == 1);
+static mi_act_mmx mmx_carve(mi_act_quant q, void * base, int64_t K, int64_t ncols) {
+    return q == MI_ACT_Q8_K ? mi_act_mmx_carve(base, K, ncols) : mi_act_mmx0_carve(base, K, ncols);
+}
+
+// the only function that knows sizes
+static size_t act_bytes(mi_act_format f, int64_t K, int64_t ncols) {
+    switch (f.layout) {
+        case MI_LAYOUT_SOA: return mi_act_q8_bytes(K, ncols, f.quant);
+        case MI_LAYOUT_MFMA: return f.quant == MI_ACT_Q8_K ? mi_act_mmx_bytes(K, ncols) : mi_act_mmx0_bytes(K, ncols);
+        case MI_LAYOUT_ROWS:
+        case MI_LAYOUT_BLOCKED: return (size_t) K * ncols * 2;
+    }
+    return 0;
 }
 
 static mi_src_cols src_cols(const ggml_tensor * t) {
@@ -659,11 +672,11 @@ static mi_src_cols src_cols(const ggml_tensor * t) {
     return x;
 }
 
-// Converted activations for (src1, kind), reused by later mul_mats of the same graph that read
+// Converted activations for (src1, format), reused by later mul_mats of the same graph that read
 // the same, unmodified src1 (Q/K/V or gate/up projections share their input).
-static void * find_activations(const mi_backend_ctx * ctx, const ggml_tensor * src1, int kind) {
+static void * find_activations(const mi_backend_ctx * ctx, const ggml_tensor * src1, mi_act_format f) {
     for (const auto & e : ctx->act_cache) {
-        if (e.data == src1->data && e.kind == kind && memcmp(e.ne, src1->ne, sizeof(e.ne)) == 0 &&
+        if (e.data == src1->data && e.format == f && memcmp(e.ne, src1->ne, sizeof(e.ne)) == 0 &&
             memcmp(e.nb, src1->nb, sizeof(e.nb)) == 0) {
             return e.dev;
         }
@@ -671,59 +684,54 @@ static void * find_activations(const mi_backend_ctx * ctx, const ggml_tensor * s
     return nullptr;
 }
 
-static void cache_activations(mi_backend_ctx * ctx, const ggml_tensor * src1, int kind, void * dev) {
+static void cache_activations(mi_backend_ctx * ctx, const ggml_tensor * src1, mi_act_format f, void * dev) {
     mi_act_cache_entry e;
     e.data = src1->data;
     e.nbytes = ggml_nbytes(src1);
-    e.kind = kind;
+    e.format = f;
     memcpy(e.ne, src1->ne, sizeof(e.ne));
     memcpy(e.nb, src1->nb, sizeof(e.nb));
     e.dev = dev;
     ctx->act_cache.push_back(e);
 }
 
-static void * get_activations(mi_backend_ctx * ctx, const ggml_tensor * src1, int kind, int64_t K) {
-    if (void * hit = find_activations(ctx, src1, kind)) return hit;
+static void * get_activations(mi_backend_ctx * ctx, const ggml_tensor * src1, mi_act_format f, int64_t K) {
+    if (void * hit = find_activations(ctx, src1, f)) return hit;
     const int64_t ncols = src1->ne[1] * src1->ne[2] * src1->ne[3];
-    void * dev = scratch_take(ctx, act_bytes(kind, K, ncols));
+    void * dev = scratch_take(ctx, act_bytes(f, K, ncols));
     const mi_src_cols x = src_cols(src1);
-    if (src1->type == GGML_TYPE_Q8_1) {
-        MI_ASSERT(kind == 10);
-        const mi_act_q8 act = mi_act_q8_carve(dev, K, ncols, false, true);
-        mi_q8_rows_to_act(x, K, false, &act, nullptr, ctx->stream, true);
-    } else if (kind == 10) {
-        mi_quantize_q8_1(x, K, mi_act_q8_carve(dev, K, ncols, false, true), ctx->stream);
-    } else if (src1->type == GGML_TYPE_Q8_K || src1->type == GGML_TYPE_Q8_0) {
+    const bool blocked = f.layout == MI_LAYOUT_BLOCKED;
+    if (q8_quant_of(src1->type) != MI_ACT_NONE) {
         // already quantized by the reference's rules (e.g. a CPY F32 -> Q8_K): re-laid out only
-        MI_ASSERT(kind == 0 || kind == 1 || kind == 8 || kind == 9);
-        const bool q8K = src1->type == GGML_TYPE_Q8_K;
-        MI_ASSERT(q8K == (kind == 1 || kind == 8));
-        if (kind >= 8) {
-            const mi_act_mmx mx = q8K ? mi_act_mmx_carve(dev, K, ncols) : mi_act_mmx0_carve(dev, K, ncols);
-            mi_q8_rows_to_act(x, K, q8K, nullptr, &mx, ctx->stream);
+        MI_ASSERT(q8_quant_of(src1->type) == f.quant);
+        MI_ASSERT(f.layout == MI_LAYOUT_SOA || (f.layout == MI_LAYOUT_MFMA && f.quant != MI_ACT_Q8_1));
+        if (f.layout == MI_LAYOUT_MFMA) {
+            const mi_act_mmx mx = mmx_carve(f.quant, dev, K, ncols);
+            mi_q8_rows_to_act(x, K, f.quant, nullptr, &mx, ctx->stream);
         } else {
-            const mi_act_q8 act = mi_act_q8_carve(dev, K, ncols, q8K);
-            mi_q8_rows_to_act(x, K, q8K, &act, nullptr, ctx->stream);
+            const mi_act_q8 act = mi_act_q8_carve(dev, K, ncols, f.quant);
+            mi_q8_rows_to_act(x, K, f.quant, &act, nullptr, ctx->stream);
         }
-    } else if (kind == 8 || kind == 9) {
+    } else if (f.layout == MI_LAYOUT_MFMA) {
         mi_mmx_qgroup q;
         q.n = 1;
         q.K = K;
         q.m[0].x = x;
-        q.m[0].act = kind == 8 ? mi_act_mmx_carve(dev, K, ncols) : mi_act_mmx0_carve(dev, K, ncols);
-        if (kind == 8) mi_quantize_q8_K_mmx_group(q, ctx->stream);
+        q.m[0].act = mmx_carve(f.quant, dev, K, ncols);
+        if (f.quant == MI_ACT_Q8_K) mi_quantize_q8_K_mmx_group(q, ctx->stream);
         else mi_quantize_q8_0_mmx_group(q, ctx->stream);
-    } else if (kind == 2 || kind == 5) {
-        mi_convert_f16(x, K, (uint16_t *) dev, ctx->stream, kind == 5, src1->type == GGML_TYPE_F16);
-    } else if (kind >= 3) {
-        mi_quantize_expand_f16(x, K, ncols, kind == 4 || kind == 7, (uint16_t *) dev, ctx->stream, kind >= 6);
-    } else {
-        const mi_act_q8 act = mi_act_q8_carve(dev, K, ncols, kind == 1);
-        if (kind == 1) mi_quantize_q8_K(x, K, act, ctx->stream);
+    } else if (f.layout == MI_LAYOUT_SOA) {
+        const mi_act_q8 act = mi_act_q8_carve(dev, K, ncols, f.quant);
+        if (f.quant == MI_ACT_Q8_K) mi_quantize_q8_K(x, K, act, ctx->stream);
+        else if (f.quant == MI_ACT_Q8_1) mi_quantize_q8_1(x, K, act, ctx->stream);
         else mi_quantize_q8_0(x, K, act, ctx->stream);
+    } else if (f.quant == MI_ACT_F16) {
+        mi_convert_f16(x, K, (uint16_t *) dev, ctx->stream, blocked, src1->type == GGML_TYPE_F16);
+    } else {
+        mi_quantize_expand_f16(x, K, ncols, f.quant, (uint16_t *) dev, ctx->stream, blocked);
     }
     ctx->last_launches++;
-    cache_activations(ctx, src1, kind, dev);
+    cache_activations(ctx, src1, f, dev);
     return dev;
 }
 
@@ -744,37 +752,38 @@ static void invalidate_activations(mi_backend_ctx * ctx, const ggml_tensor * wri
 // the batched (prompt) GEMM applies: more than 8 columns of plain 2-D operands
 static bool mm_batched(const mi_mm_desc & m, const ggml_tensor * src1) {
     static const bool no_mmq = getenv("GGML_MI355X_NO_MMQ") != nullptr;
-    return !no_mmq && act_kind((ggml_type) m.type) >= 0 && src1->ne[1] > 8 && m.ne02 == 1 && m.ne03 == 1 && m.ne12 == 1 &&
+    return !no_mmq && mi_type(m.type).act != MI_ACT_NONE && src1->ne[1] > 8 && m.ne02 == 1 && m.ne03 == 1 && m.ne12 == 1 &&
            m.ne13 == 1 && mi_mmq_supported(m.type, m.K, m.nb01, m.nb1) && ((uintptr_t) m.W % 16) == 0;
 }
 
-// The activation format mul_mat_run converts src1 to for this mul_mat (act_bytes kinds), or -1
-// (F32 weights: src1 is read as it lies). Q4_K / Q5_K prompts: the exact-integer int8 GEMM's
-// q8_K layouts (8); Q4_0 / Q8_0 prompts: its q8_0 layouts (9); F16 prompts: f16 operands (2, or
-// K-blocked 5); decode: q8 SoA (0 / 1) or f16 (2). Q6_K has neither an exact MFMA GEMM nor a
-// dequantizer in the f16 GEMM (mi_mmq_supported / mi_mmqx_supported refuse it): q8_K SoA (1) at
-// any column count, the GEMV runs the prompt in 8-column chunks. Q4_1 / Q5_0 / Q5_1 likewise: q8_1
-// SoA (10) resp. q8_0 SoA (0) at any column count.
-static int mm_act_kind(const mi_mm_desc & m, const ggml_tensor * src1) {
-    const int kind = act_kind((ggml_type) m.type);
-    if (kind < 0) return -1;
-    if (kind == 10) return kind;
+// The activation format mul_mat_run converts src1 to for this mul_mat (quant MI_ACT_NONE, F32
+// weights: src1 is read as it lies). Q4_K / Q5_K / Q4_0 / Q8_0 prompts: the exact-integer int8
+// GEMM's MFMA layouts of their quantization; F16 prompts: f16 rows, or K-blocked; decode: the
+// weight type's own format (q8 SoA or f16 rows). Q6_K has neither an exact MFMA GEMM nor a
+// dequantizer in the f16 GEMM (mi_mmq_supported / mi_mmqx_supported refuse it): q8_K SoA at any
+// column count, the GEMV runs the prompt in 8-column chunks. Q4_1 / Q5_0 / Q5_1 likewise: q8_1
+// resp. q8_0 SoA at any column count.
+static mi_act_format mm_act_format(const mi_mm_desc & m, const ggml_tensor * src1) {
+    mi_act_format f = act_format_of((ggml_type) m.type);
+    if (f.quant == MI_ACT_NONE || f.quant == MI_ACT_Q8_1 || !mm_batched(m, src1)) return f;
     const int64_t ncols = src1->ne[1] * src1->ne[2] * src1->ne[3];
+    const bool exact = f.quant != MI_ACT_F16 && mi_mmqx_supported(m.type, m.K, m.nb1, ncols, m.nb01);
     if (src1->type != GGML_TYPE_F32 && src1->type != GGML_TYPE_F16) {
         // pre-quantized src1 (Q8_K / Q8_0 rows): the exact GEMMs' layouts, else the GEMV's
-        return mm_batched(m, src1) && mi_mmqx_supported(m.type, m.K, m.nb1, ncols, m.nb01) ? (kind == 1 ? 8 : 9) : kind;
+        if (exact) f.layout = MI_LAYOUT_MFMA;
+        return f;
     }
-    if (!mm_batched(m, src1)) return kind;
     // mmq_variant bit kMmqF16Gemm selects the f16 GEMM for the quantized types too (A/B
     // timing; the low bits are mmq_exact.hip's own kernel variants)
-    if (kind <= 1 && (g_mi_tuning.mmq_variant & kMmqF16Gemm) == 0 && mi_mmqx_supported(m.type, m.K, m.nb1, ncols, m.nb01)) return kind == 1 ? 8 : 9;
-    return (kind == 2 ? 2 : kind + 3) + (mi_mmq_wants_blocked() ? 3 : 0);
+    if (exact && (g_mi_tuning.mmq_variant & kMmqF16Gemm) == 0) f.layout = MI_LAYOUT_MFMA;
+    else f.layout = mi_mmq_wants_blocked() ? MI_LAYOUT_BLOCKED : MI_LAYOUT_ROWS;  // the f16 GEMM's operand: same quantization, expanded
+    return f;
 }
 
 // the repacked MFMA planes of the long Q4_K / Q5_K prompts' weights (before any capture: creating
 // them allocates); only graph leaves (weights), never a tensor a node of the graph writes
 static const char * planes_of(mi_backend_ctx * ctx, const ggml_tensor * a, const ggml_tensor * b) {
-    if (!g_mi_tuning.planes || (a->type != GGML_TYPE_Q4_K && a->type != GGML_TYPE_Q5_K) || a->op != GGML_OP_NONE || a->ne[2] != 1 ||
+    if (!g_mi_tuning.planes || !mi_type(a->type).planes || a->op != GGML_OP_NONE || a->ne[2] != 1 ||
         a->ne[3] != 1 || b->ne[1] * b->ne[2] * b->ne[3] < kMiPlanesMinCols || is_split_tensor(a))
         return nullptr;
     // only tensors of this backend's own device buffers: host and peer memory have write paths
@@ -790,8 +799,7 @@ static const char * planes_of(mi_backend_ctx * ctx, const ggml_tensor * a, const
 // k_q40_repack / k_q80_repack; created before any capture, renewed by the same write paths as the planes): the
 // same conditions as planes_of -- a graph leaf in this backend's own device buffer
 static const char * q40r_of(mi_backend_ctx * ctx, const ggml_tensor * a) {
-    const bool on = a->type == GGML_TYPE_Q4_0 ? g_mi_tuning.q40r : a->type == GGML_TYPE_Q8_0 ? g_mi_tuning.q80r : 0;
-    if (!on || a->op != GGML_OP_NONE || a->ne[2] != 1 || a->ne[3] != 1 || is_split_tensor(a))
+    if (!mi_aligned_copy_on(a->type) || a->op != GGML_OP_NONE || a->ne[2] != 1 || a->ne[3] != 1 || is_split_tensor(a))
         return nullptr;
     const ggml_backend_buffer_t buf = a->view_src ? a->view_src->buffer : a->buffer;
     if (!buffer_is_mi355x(buf) || ((mi_buffer_ctx *) buf->context)->device != ctx->device) return nullptr;
@@ -802,32 +810,23 @@ static const char * q40r_of(mi_backend_ctx * ctx, const ggml_tensor * a) {
 // weight must have one, else the canonical blocks (FmtQ0Pair / FmtQ0<true>) -- the same bits
 static void q40r_apply(mi_backend_ctx * ctx, mi_mmv_group & g, const ggml_tensor * const * w) {
     // (one column: with two, the aligned copy measured 2-3 % slower, profiles/r06s2_q40r_ab.txt)
-    const bool q4 = g.type == GGML_TYPE_Q4_0;
-    if ((!q4 && g.type != GGML_TYPE_Q8_0) || g.ncols != 1 || !(q4 ? g_mi_tuning.q40r : g_mi_tuning.q80r) || mi_mmv_order() != 0 ||
-        (q4 && g_mi_tuning.mmv_variant % 10 == 1)) return;
+    if (!mi_aligned_copy_on(g.type) || g.ncols != 1 || mi_mmv_order() != 0 ||
+        (g.type == GGML_TYPE_Q4_0 && g_mi_tuning.mmv_variant % 10 == 1)) return;
     const void * p[kMiMaxMembers];
     for (int m = 0; m < g.n; m++) {
         p[m] = q40r_of(ctx, w[m]);
         if (!p[m]) return;
     }
     for (int m = 0; m < g.n; m++) g.m[m].W = p[m];
-    g.nb01 = (size_t) (g.K / 32 * (q4 ? 18 : 34));
+    g.nb01 = (size_t) (g.K / mi_type(g.type).blck * mi_type(g.type).bytes);
     g.q0r = 1;
 }
 
-// The mul_mat of (src0, src1) with src0's rows taken from (W, N) and the output written at out
-// (column strides nb1..nb3): op_mul_mat runs the whole node through it, the split-buffer path
-// (op_mul_mat_split) each device's row slice.
-static void mul_mat_run(mi_backend_ctx * ctx, const ggml_tensor * src0, const void * W, int64_t N, const ggml_tensor * src1,
-                        float * out, size_t nb1, size_t nb2, size_t nb3) {
-    MI_ASSERT(src1->type == GGML_TYPE_F32 || (src1->type == GGML_TYPE_F16 && src0->type == GGML_TYPE_F16) ||
-              src1->type == q8_src1_type(src0->type));
-    MI_ASSERT(src0->nb[0] == ggml_type_size(src0->type));
-    MI_ASSERT(src1->nb[0] == ggml_type_size(src1->type));
-    MI_ASSERT(src0->ne[0] == src1->ne[0]);
-    MI_ASSERT(src1->ne[2] % src0->ne[2] == 0 && src1->ne[3] % src0->ne[3] == 0);
-
-    mi_mm_desc m;
+// The descriptor of the mul_mat of (src0, src1) with src0's rows taken from (W, N) and the output
+// written at out (column strides nb1..nb3). MUL_MAT_ID: src0 the expert stack, src1 its b.
+static mi_mm_desc mm_desc(const ggml_tensor * src0, const void * W, int64_t N, const ggml_tensor * src1, float * out, size_t nb1, size_t nb2,
+                          size_t nb3) {
+    mi_mm_desc m{};
     m.W = W;
     m.type = src0->type;
     m.K = src0->ne[0];
@@ -844,32 +843,51 @@ static void mul_mat_run(mi_backend_ctx * ctx, const ggml_tensor * src0, const vo
     m.nb1 = nb1;
     m.nb2 = nb2;
     m.nb3 = nb3;
+    return m;
+}
 
-    const int xkind = mm_act_kind(m, src1);
-    if (xkind < 0) {
+// The mul_mat of (src0, src1) with src0's rows taken from (W, N) and the output written at out
+// (column strides nb1..nb3): op_mul_mat runs the whole node through it, the split-buffer path
+// (op_mul_mat_split) each device's row slice.
+static void mul_mat_run(mi_backend_ctx * ctx, const ggml_tensor * src0, const void * W, int64_t N, const ggml_tensor * src1,
+                        float * out, size_t nb1, size_t nb2, size_t nb3) {
+    MI_ASSERT(src1->type == GGML_TYPE_F32 || (src1->type == GGML_TYPE_F16 && src0->type == GGML_TYPE_F16) ||
+              src1->type == q8_src1_type(src0->type));
+    MI_ASSERT(src0->nb[0] == ggml_type_size(src0->type));
+    MI_ASSERT(src1->nb[0] == ggml_type_size(src1->type));
+    MI_ASSERT(src0->ne[0] == src1->ne[0]);
+    MI_ASSERT(src1->ne[2] % src0->ne[2] == 0 && src1->ne[3] % src0->ne[3] == 0);
+
+    const mi_mm_desc m = mm_desc(src0, W, N, src1, out, nb1, nb2, nb3);
+    const mi_act_format f = mm_act_format(m, src1);
+    if (f.quant == MI_ACT_NONE) {
         MI_ASSERT(src0->type == GGML_TYPE_F32);
         mi_mul_mat_f32(m, src_cols(src1), ctx->stream);
     } else {
         const int64_t ncols = src1->ne[1] * src1->ne[2] * src1->ne[3];
-        void * xa = get_activations(ctx, src1, xkind, m.K);
-        if (xkind == 10) {
-            // Q4_1 / Q5_1 x q8_1: the GEMVs at any column count
-            mi_mul_mat_q(m, mi_act_q8_carve(xa, m.K, ncols, false, true), ctx->stream);
-        } else if (xkind == 8 || xkind == 9) {
-            // Q4_K / Q5_K / Q4_0 / Q8_0: the exact-integer int8 MFMA GEMMs (mmq_exact.hip)
-            const mi_act_mmx act = xkind == 8 ? mi_act_mmx_carve(xa, m.K, ncols) : mi_act_mmx0_carve(xa, m.K, ncols);
-            mi_mul_mat_mmqx(m.type, m.W, m.nb01, m.K, m.N, act, m.dst, m.nb1, ctx->stream, W == src0->data && N == src0->ne[1] ? planes_of(ctx, src0, src1) : nullptr);
-        } else if (xkind == 5 && m.type == GGML_TYPE_F16 && mi_mmf16p_supported(m.K, m.N, m.nb01, ncols, m.nb1)) {
-            // F16 weights, a short prompt: 32 x 32 tiles with the K split over each tile's 4 waves
-            mi_mul_mat_f16p(m.W, m.nb01, m.K, m.N, (const uint16_t *) xa, ncols, m.dst, m.nb1, ctx->stream);
-        } else if (xkind >= 3 || (xkind == 2 && mm_batched(m, src1))) {
-            // the GEMM's activation operand: f16 for F16 weights, else f16(d * q) of the q8 quants
-            // written by the quantizer itself (kinds 3/4, K-blocked 5..7)
-            mi_mul_mat_mmq(m.type, m.W, m.nb01, m.K, m.N, mi_act_q8{}, (const uint16_t *) xa, ncols, m.dst, m.nb1, nullptr, ctx->stream);
-        } else if (xkind == 2) {
-            mi_mul_mat_f16(m, (const uint16_t *) xa, ctx->stream);
-        } else {
-            mi_mul_mat_q(m, mi_act_q8_carve(xa, m.K, ncols, xkind == 1), ctx->stream);
+        void * xa = get_activations(ctx, src1, f, m.K);
+        const uint16_t * xh = (const uint16_t *) xa;
+        switch (f.layout) {
+            case MI_LAYOUT_SOA:  // the GEMVs, at any column count
+                mi_mul_mat_q(m, mi_act_q8_carve(xa, m.K, ncols, f.quant), ctx->stream);
+                break;
+            case MI_LAYOUT_MFMA:  // Q4_K / Q5_K / Q4_0 / Q8_0: the exact-integer int8 MFMA GEMMs (mmq_exact.hip)
+                mi_mul_mat_mmqx(m.type, m.W, m.nb01, m.K, m.N, mmx_carve(f.quant, xa, m.K, ncols), m.dst, m.nb1, ctx->stream,
+                                W == src0->data && N == src0->ne[1] ? planes_of(ctx, src0, src1) : nullptr);
+                break;
+            case MI_LAYOUT_ROWS:
+            case MI_LAYOUT_BLOCKED:
+                if (f.quant == MI_ACT_F16 && f.layout == MI_LAYOUT_BLOCKED && mi_mmf16p_supported(m.K, m.N, m.nb01, ncols, m.nb1)) {
+                    // F16 weights, a short prompt: 32 x 32 tiles with the K split over each tile's 4 waves
+                    mi_mul_mat_f16p(m.W, m.nb01, m.K, m.N, xh, ncols, m.dst, m.nb1, ctx->stream);
+                } else if (f.quant != MI_ACT_F16 || f.layout == MI_LAYOUT_BLOCKED || mm_batched(m, src1)) {
+                    // the GEMM's activation operand: f16 for F16 weights, else f16(d * q) of the q8 quants
+                    // written by the quantizer itself
+                    mi_mul_mat_mmq(m.type, m.W, m.nb01, m.K, m.N, mi_act_q8{}, xh, ncols, m.dst, m.nb1, nullptr, ctx->stream);
+                } else {
+                    mi_mul_mat_f16(m, xh, ctx->stream);  // f16 rows of a mul_mat that is not batched: the F16 GEMV
+                }
+                break;
         }
     }
     ctx->last_launches++;
@@ -877,25 +895,7 @@ static void mul_mat_run(mi_backend_ctx * ctx, const ggml_tensor * src0, const vo
 
 // the mul_mat descriptor of a whole MUL_MAT node (as mul_mat_run builds it)
 static mi_mm_desc mm_desc_of(const ggml_tensor * node) {
-    const ggml_tensor * src0 = node->src[0], * src1 = node->src[1];
-    mi_mm_desc m{};
-    m.W = src0->data;
-    m.type = src0->type;
-    m.K = src0->ne[0];
-    m.N = src0->ne[1];
-    m.ne02 = src0->ne[2];
-    m.ne03 = src0->ne[3];
-    m.nb01 = src0->nb[1];
-    m.nb02 = src0->nb[2];
-    m.nb03 = src0->nb[3];
-    m.ne11 = src1->ne[1];
-    m.ne12 = src1->ne[2];
-    m.ne13 = src1->ne[3];
-    m.dst = (float *) node->data;
-    m.nb1 = node->nb[1];
-    m.nb2 = node->nb[2];
-    m.nb3 = node->nb[3];
-    return m;
+    return mm_desc(node->src[0], node->src[0]->data, node->src[0]->ne[1], node->src[1], (float *) node->data, node->nb[1], node->nb[2], node->nb[3]);
 }
 
 static void op_mul_mat(mi_backend_ctx * ctx, ggml_tensor * dst) {
@@ -983,41 +983,25 @@ static void op_mul_mat_id(mi_backend_ctx * ctx, ggml_tensor * dst) {
         return;
     }
 
-    mi_mm_desc m{};
-    m.W = as->data;
-    m.type = as->type;
-    m.K = K;
-    m.N = N;
-    m.ne02 = n_as;
-    m.ne03 = 1;
-    m.nb01 = as->nb[1];
-    m.nb02 = as->nb[2];
-    m.nb03 = as->nb[3];
-    m.ne11 = ne11;
-    m.ne12 = n_tokens;
-    m.ne13 = 1;
-    m.dst = (float *) dst->data;
-    m.nb1 = dst->nb[1];
-    m.nb2 = dst->nb[2];
-    m.nb3 = dst->nb[3];
+    mi_mm_desc m = mm_desc(as, as->data, N, b, (float *) dst->data, dst->nb[1], dst->nb[2], dst->nb[3]);  // (ne03 = ne13 = 1: asserted above)
     m.id.ids = (const int32_t *) ids->data;
     m.id.nb0 = ids->nb[0];
     m.id.nb1 = ids->nb[1];
     m.id.n_as = (int) n_as;
     m.id.n_ids = (int) n_ids;
 
-    const int kind = act_kind(as->type);
+    const mi_act_format f = act_format_of(as->type);
     const int cap = g_mi_tuning.mmid_group == 8 ? 8 : 4;  // (chunks of 4 measured faster than 8 at every size, both orders)
-    const bool grouped = kind >= 0 && kind != 2 && g_mi_tuning.mmid_group && n_as <= kMiMmidMaxExperts &&
+    const bool grouped = f.layout == MI_LAYOUT_SOA && f.quant != MI_ACT_NONE && g_mi_tuning.mmid_group && n_as <= kMiMmidMaxExperts &&
                          n_tokens >= (g_mi_tuning.mmid_group > 1 ? 2 : mmid_group_min_tokens());
     // blockIdx.y counts the pairs, or the chunks of up to `cap` pairs
     MI_ASSERT((grouped ? mi_mmid_max_chunks(n_as, n_ids * n_tokens, cap) : n_ids * n_tokens) <= 65535 && "MUL_MAT_ID: too many pairs for one launch");
-    if (kind < 0) {
+    if (f.quant == MI_ACT_NONE) {
         MI_ASSERT(as->type == GGML_TYPE_F32);
         mi_mul_mat_f32(m, src_cols(b), ctx->stream);
     } else {
-        void * xa = get_activations(ctx, b, kind, K);
-        if (kind == 2) {
+        void * xa = get_activations(ctx, b, f, K);
+        if (f.quant == MI_ACT_F16) {
             mi_mul_mat_f16(m, (const uint16_t *) xa, ctx->stream);
         } else {
             if (grouped) {
@@ -1030,7 +1014,7 @@ static void op_mul_mat_id(mi_backend_ctx * ctx, ggml_tensor * dst) {
                 m.id.chunks = chunks;
                 m.id.pairs = plist;
             }
-            mi_mul_mat_q(m, mi_act_q8_carve(xa, K, ne11 * n_tokens, kind == 1, kind == 10), ctx->stream);
+            mi_mul_mat_q(m, mi_act_q8_carve(xa, K, ne11 * n_tokens, f.quant), ctx->stream);
         }
     }
     ctx->last_launches++;
@@ -1090,25 +1074,17 @@ static void op_mul_mat_split(mi_backend_ctx * ctx, ggml_tensor * dst) {
     struct remote {
         const mi_split_slice * sl;
         int64_t ld;
-        int xkind;        // act_bytes kind shipped, -1: the f32 columns
+        mi_act_format xf; // the format shipped (quant MI_ACT_NONE: the f32 columns)
         const void * xa;  // converted activations on the main device
     };
     std::vector<remote> rem;
     for (const auto & sl : extra->slices) {
         if (is_local(sl)) continue;
         const int64_t rows = sl.row_high - sl.row_low;
-        remote rm{&sl, (rows + 3) & ~(int64_t) 3, -1, src1->data};
-        mi_mm_desc m{};
-        m.W = sl.ptr;
-        m.type = src0->type;
-        m.K = K;
-        m.N = rows;
-        m.ne02 = m.ne03 = m.ne12 = m.ne13 = 1;
-        m.nb01 = src0->nb[1];
-        m.ne11 = ncols;
-        m.nb1 = (size_t) rm.ld * sizeof(float);
-        rm.xkind = mm_act_kind(m, src1);
-        if (rm.xkind >= 0) rm.xa = get_activations(ctx, src1, rm.xkind, K);
+        remote rm{&sl, (rows + 3) & ~(int64_t) 3, {}, src1->data};
+        const size_t ycol = (size_t) rm.ld * sizeof(float);
+        rm.xf = mm_act_format(mm_desc(src0, sl.ptr, rows, src1, nullptr, ycol, ycol * ncols, ycol * ncols), src1);
+        if (rm.xf.quant != MI_ACT_NONE) rm.xa = get_activations(ctx, src1, rm.xf, K);
         rem.push_back(rm);
     }
     if (!rem.empty()) {
@@ -1129,7 +1105,7 @@ static void op_mul_mat_split(mi_backend_ctx * ctx, ggml_tensor * dst) {
         mi_split_aux * a = split_aux(sl.slot, ctx->device);
         mi_device_guard g(a->ctx.device);
         MI_CHECK(hipStreamWaitEvent(a->ctx.stream, ctx->split_ready, 0));
-        const size_t xbytes = rm.xkind >= 0 ? act_bytes(rm.xkind, K, ncols) : (size_t) K * ncols * sizeof(float);
+        const size_t xbytes = rm.xf.quant != MI_ACT_NONE ? act_bytes(rm.xf, K, ncols) : (size_t) K * ncols * sizeof(float);
         const size_t ybytes = (size_t) rm.ld * ncols * sizeof(float);
         scratch_reserve(&a->ctx, xbytes + ybytes + 4 * kBufferAlign);  // stream-ordered reuse: earlier users ran on the same stream
         a->ctx.scratch_used = 0;
@@ -1145,12 +1121,12 @@ static void op_mul_mat_split(mi_backend_ctx * ctx, ggml_tensor * dst) {
         x1.data = xl;
         x1.view_src = nullptr;
         x1.view_offs = 0;
-        if (rm.xkind >= 0) {
+        if (rm.xf.quant != MI_ACT_NONE) {
             // the slot's mul_mat finds its activations already converted
             mi_act_cache_entry e;
             e.data = xl;
             e.nbytes = ggml_nbytes(src1);
-            e.kind = rm.xkind;
+            e.format = rm.xf;
             memcpy(e.ne, x1.ne, sizeof(e.ne));
             memcpy(e.nb, x1.nb, sizeof(e.nb));
             e.dev = xl;
@@ -1375,8 +1351,8 @@ static void op_companion(mi_backend_ctx * ctx, ggml_tensor * node) {
         case GGML_OP_DUP:
         case GGML_OP_CONT:
             MI_ASSERT(ggml_nelements(node) == ggml_nelements(a));
-            if (node->type == GGML_TYPE_Q8_K || node->type == GGML_TYPE_Q8_0 || node->type == GGML_TYPE_Q8_1) {
-                mi_quantize_rows_q8(src_cols(a), a->ne[0], node->type == GGML_TYPE_Q8_K, src_cols(node), st, node->type == GGML_TYPE_Q8_1);
+            if (q8_quant_of(node->type) != MI_ACT_NONE) {
+                mi_quantize_rows_q8(src_cols(a), a->ne[0], q8_quant_of(node->type), src_cols(node), st);
                 break;
             }
             mi_op_cpy(desc(node), desc(a), st);
@@ -1417,8 +1393,8 @@ static size_t graph_scratch_bytes(const ggml_cgraph * cgraph) {
         if (n->op == GGML_OP_MUL_MAT_ID) {
             // the converted activations and the grouping tables (whichever path runs)
             const ggml_tensor * b = n->src[1];
-            const int kind = act_kind(n->src[0]->type);
-            if (kind >= 0) total += (act_bytes(kind, b->ne[0], b->ne[1] * b->ne[2] * b->ne[3]) + kBufferAlign - 1) & ~(kBufferAlign - 1);
+            const mi_act_format f = act_format_of(n->src[0]->type);
+            if (f.quant != MI_ACT_NONE) total += (act_bytes(f, b->ne[0], b->ne[1] * b->ne[2] * b->ne[3]) + kBufferAlign - 1) & ~(kBufferAlign - 1);
             if (n->src[2]) total += mmid_tables_bytes(n->src[0]->ne[2], n->src[2]->ne[0] * n->src[2]->ne[1]);
             continue;
         }
@@ -1429,15 +1405,17 @@ static size_t graph_scratch_bytes(const ggml_cgraph * cgraph) {
             // sums (try_fuse_attn_proj; head dim >= 64, so at most K / 64 heads)
             total += ((size_t) (n->src[0]->ne[0] / 64) * n->src[0]->ne[1] * sizeof(float) + kBufferAlign - 1) & ~(kBufferAlign - 1);
         }
-        const int kind = act_kind(n->src[0]->type);
-        if (kind < 0) continue;
+        // The weight type's own format (q8 SoA or f16 rows) always; plus, above 8 columns, the
+        // larger of the f16 GEMM's operand and the exact GEMMs' MFMA layout, where the type has one --
+        // both counted, the choice is made at run time. Q8_1 activations feed the GEMVs only.
+        const mi_act_format f = act_format_of(n->src[0]->type);
+        if (f.quant == MI_ACT_NONE) continue;
         const ggml_tensor * b = n->src[1];
         const int64_t ncols = b->ne[1] * b->ne[2] * b->ne[3];
-        // q8 blocks and/or their f16 expansion (batched) -- both counted, the choice is made at run time
-        total += (act_bytes(kind, b->ne[0], ncols) + kBufferAlign - 1) & ~(kBufferAlign - 1);
-        if (ncols > 8 && kind != 10) {
-            const size_t big = std::max(act_bytes(kind + 3, b->ne[0], ncols),
-                                        kind == 1 ? act_bytes(8, b->ne[0], ncols) : kind == 0 ? act_bytes(9, b->ne[0], ncols) : 0);
+        total += (act_bytes(f, b->ne[0], ncols) + kBufferAlign - 1) & ~(kBufferAlign - 1);
+        if (ncols > 8 && f.quant != MI_ACT_Q8_1) {
+            const size_t big = std::max(act_bytes({f.quant, MI_LAYOUT_ROWS}, b->ne[0], ncols),
+                                        f.quant != MI_ACT_F16 ? act_bytes({f.quant, MI_LAYOUT_MFMA}, b->ne[0], ncols) : 0);
             total += (big + kBufferAlign - 1) & ~(kBufferAlign - 1);
         }
     }
@@ -1452,12 +1430,10 @@ static bool overlaps(const ggml_tensor * a, const ggml_tensor * b) {
     return a0 < b0 + ggml_nbytes(b) && b0 < a0 + ggml_nbytes(a);
 }
 
-// the streaming GEMV's weight alignment: 16-byte rows, except Q6_K, whose 210-byte blocks its
-// loads re-align themselves (rows of an odd superblock count are 2 mod 4: K = 11008 has 9030-byte
-// rows) -- a 16-byte tensor base and 2-byte rows
+// the streaming GEMV's weight alignment: a 16-byte tensor base and rows of the type's mmv_align
+// (16 bytes, Q6_K 2: mi355x_types.h); only for types mi_mmv_fused_supported accepts
 static bool fused_weight_aligned(const ggml_tensor * a) {
-    if (a->type == GGML_TYPE_Q6_K) return (uintptr_t) a->data % 16 == 0 && a->nb[1] % 2 == 0;
-    return ((uintptr_t) a->data | a->nb[1]) % 16 == 0;
+    return (uintptr_t) a->data % 16 == 0 && a->nb[1] % mi_type(a->type).mmv_align == 0;
 }
 
 static bool fused_mv_eligible(const ggml_tensor * n) {
@@ -1740,7 +1716,7 @@ static int try_fuse_f16_gemv(mi_backend_ctx * ctx, ggml_cgraph * g, int i, const
         return last;
     }
     if (overlaps(out, x)) {
-        uint16_t * tmp = (uint16_t *) scratch_take(ctx, act_bytes(2, w->ne[0], x->ne[1]));
+        uint16_t * tmp = (uint16_t *) scratch_take(ctx, act_bytes({MI_ACT_F16, MI_LAYOUT_ROWS}, w->ne[0], x->ne[1]));
         mi_convert_f16(src_cols(x), w->ne[0], tmp, ctx->stream);
         ctx->last_launches++;
         xh = tmp;
@@ -2122,9 +2098,6 @@ static bool ord_prefill_chunked(const ggml_tensor * n) {
     const ggml_tensor * a = n->src[0];
     const ggml_tensor * b = n->src[1];
     if (b->type != GGML_TYPE_F32 || b->ne[1] <= 8 || b->ne[1] > (mi_mmv_order() == 1 ? g_mi_tuning.ord_prefill_cols : g_mi_tuning.tree_prefill_cols)) return false;
-    if (a->type != GGML_TYPE_Q4_K && a->type != GGML_TYPE_Q5_K && a->type != GGML_TYPE_Q6_K && a->type != GGML_TYPE_Q4_0 &&
-        a->type != GGML_TYPE_Q8_0 && !is_legacy_q1(a->type))
-        return false;
     if (!mi_mmv_fused_supported(a->type, a->ne[0], 8)) return false;
     if (a->ne[2] != 1 || a->ne[3] != 1 || b->ne[2] != 1 || b->ne[3] != 1) return false;
     if (a->nb[0] != ggml_type_size(a->type) || b->nb[0] != sizeof(float) || n->nb[0] != sizeof(float)) return false;
@@ -2165,15 +2138,15 @@ static void run_ord_prefill_chunks(mi_backend_ctx * ctx, ggml_tensor * n) {
     if (ncols % 8) launch(8 * full, 1, (int) (ncols % 8));
 }
 
-// the activation kind of a MUL_MAT node that runs on an exact int8 prefill GEMM (Q4_K / Q5_K: 8,
-// Q4_0 / Q8_0: 9; > 8 plain columns), or -1
-static int prefill_mmx_kind(const ggml_tensor * n) {
-    if (n->op != GGML_OP_MUL_MAT || is_split_tensor(n->src[0]) || ord_prefill_chunked(n)) return -1;
+// the activation format of a MUL_MAT node that runs on an exact int8 prefill GEMM (q8_K or q8_0
+// in the MFMA layout; > 8 plain columns), or none (quant MI_ACT_NONE)
+static mi_act_format prefill_mmx_format(const ggml_tensor * n) {
+    if (n->op != GGML_OP_MUL_MAT || is_split_tensor(n->src[0]) || ord_prefill_chunked(n)) return {};
     const ggml_tensor * a = n->src[0], * b = n->src[1];
-    if (b->type != GGML_TYPE_F32 || a->nb[0] != ggml_type_size(a->type) || b->nb[0] != sizeof(float) || n->nb[0] != sizeof(float)) return -1;
-    if (a->ne[0] != b->ne[0]) return -1;
-    const int k = mm_act_kind(mm_desc_of(n), b);
-    return k == 8 || k == 9 ? k : -1;
+    if (b->type != GGML_TYPE_F32 || a->nb[0] != ggml_type_size(a->type) || b->nb[0] != sizeof(float) || n->nb[0] != sizeof(float)) return {};
+    if (a->ne[0] != b->ne[0]) return {};
+    const mi_act_format f = mm_act_format(mm_desc_of(n), b);
+    return f.layout == MI_LAYOUT_MFMA ? f : mi_act_format{};
 }
 
 // Batched (prompt) mul_mats that follow each other in the graph and are independent of each other
@@ -2186,8 +2159,8 @@ static int prefill_mmx_kind(const ggml_tensor * n) {
 static int run_prefill_group(mi_backend_ctx * ctx, ggml_cgraph * g, int i) {
     static const bool no_group = getenv("GGML_MI355X_NO_PREFILL_GROUP") != nullptr;
     ggml_tensor * first = g->nodes[i];
-    const int kind = prefill_mmx_kind(first);
-    if (no_group || kind < 0) return -1;
+    const mi_act_format f = prefill_mmx_format(first);
+    if (no_group || f.quant == MI_ACT_NONE) return -1;
     const ggml_type type = first->src[0]->type;
     const int64_t K = first->src[0]->ne[0];
     auto cols_of = [](const ggml_tensor * n) { return n->src[1]->ne[1] * n->src[1]->ne[2] * n->src[1]->ne[3]; };
@@ -2197,7 +2170,7 @@ static int run_prefill_group(mi_backend_ctx * ctx, ggml_cgraph * g, int i) {
     std::vector<int> at = {i};
     for (int j = next_node(g, i); j >= 0 && (int) members.size() < 4 * kMiMaxPrefillMembers; j = next_node(g, j)) {
         ggml_tensor * n = g->nodes[j];
-        if (prefill_mmx_kind(n) != kind || n->src[0]->type != type || n->src[0]->ne[0] != K || cols_of(n) != ncols) break;
+        if (prefill_mmx_format(n) != f || n->src[0]->type != type || n->src[0]->ne[0] != K || cols_of(n) != ncols) break;
         bool independent = true;
         for (ggml_tensor * m : members) {
             if (overlaps(n->src[1], m) || overlaps(n->src[0], m) || overlaps(n, m->src[0]) || overlaps(n, m->src[1]) || overlaps(n, m)) {
@@ -2223,17 +2196,17 @@ static int run_prefill_group(mi_backend_ctx * ctx, ggml_cgraph * g, int i) {
     std::vector<void *> xa(members.size(), nullptr);
     for (size_t k = 0; k < members.size(); k++) {
         const ggml_tensor * x = members[k]->src[1];
-        xa[k] = find_activations(ctx, x, kind);
+        xa[k] = find_activations(ctx, x, f);
         if (xa[k]) continue;
-        void * dev = scratch_take(ctx, act_bytes(kind, K, ncols));
+        void * dev = scratch_take(ctx, act_bytes(f, K, ncols));
         q.m[q.n].x = src_cols(x);
-        q.m[q.n].act = kind == 8 ? mi_act_mmx_carve(dev, K, ncols) : mi_act_mmx0_carve(dev, K, ncols);
+        q.m[q.n].act = mmx_carve(f.quant, dev, K, ncols);
         q.n++;
-        cache_activations(ctx, x, kind, dev);
+        cache_activations(ctx, x, f, dev);
         xa[k] = dev;
     }
     if (q.n > 0) {
-        if (kind == 8) mi_quantize_q8_K_mmx_group(q, ctx->stream);
+        if (f.quant == MI_ACT_Q8_K) mi_quantize_q8_K_mmx_group(q, ctx->stream);
         else mi_quantize_q8_0_mmx_group(q, ctx->stream);
         ctx->last_launches++;
     }
@@ -2243,7 +2216,7 @@ static int run_prefill_group(mi_backend_ctx * ctx, ggml_cgraph * g, int i) {
     gg.n = (int) members.size();
     for (size_t k = 0; k < members.size(); k++) {
         const ggml_tensor * n = members[k];
-        const mi_act_mmx act = kind == 8 ? mi_act_mmx_carve(xa[k], K, ncols) : mi_act_mmx0_carve(xa[k], K, ncols);
+        const mi_act_mmx act = mmx_carve(f.quant, xa[k], K, ncols);
         gg.m[k] = mi_mmx_member{n->src[0]->data, n->src[0]->nb[1], n->src[0]->ne[1], act, (float *) n->data, n->nb[1], 0, planes_of(ctx, n->src[0], n->src[1])};
     }
     mi_mul_mat_mmqx_group(gg, ctx->stream);
@@ -3217,6 +3190,45 @@ ggml_backend_buffer_type_t ggml_backend_mi355x_split_buffer_type(const float * t
     return buft;
 }
 
+} // extern "C"
+
+// The reference's type traits (ggml.h ggml_type_traits_t), looked up in the library that this one's
+// ggml_* references are bound to; the repo's own runtime exports none (null then).
+struct mi_ggml_type_traits {
+    const char * type_name;
+    int blck_size;
+    size_t type_size;
+    bool is_quantized;
+    void * to_float, * from_float, * from_float_reference, * vec_dot;
+    enum ggml_type vec_dot_type;
+    int64_t nrows;
+};
+typedef mi_ggml_type_traits (*mi_get_type_traits_t)(enum ggml_type);
+static mi_get_type_traits_t bound_type_traits() {
+    Dl_info info;
+    if (!dladdr((void *) &ggml_type_size, &info) || !info.dli_fname) return nullptr;
+    void * lib = dlopen(info.dli_fname, RTLD_LAZY | RTLD_NOLOAD);
+    return lib ? (mi_get_type_traits_t) dlsym(lib, "ggml_internal_get_type_traits") : nullptr;
+}
+
+// once per process: the weight-type table agrees with the ggml it runs under
+static bool check_type_table() {
+    const mi_get_type_traits_t traits = bound_type_traits();
+    for (const mi_type_info & t : kMiTypes) {
+        const ggml_type gt = (ggml_type) t.type;
+        MI_ASSERT(ggml_blck_size(gt) == t.blck && ggml_type_size(gt) == (size_t) t.bytes);
+        if (traits)
+            MI_ASSERT(traits(gt).vec_dot_type == (t.act == MI_ACT_NONE ? GGML_TYPE_F32 : (ggml_type) mi_act_type(t.act)));
+    }
+    for (const mi_act_quant q : {MI_ACT_Q8_0, MI_ACT_Q8_1, MI_ACT_Q8_K}) {
+        const ggml_type gt = (ggml_type) mi_act_type(q);
+        MI_ASSERT(ggml_blck_size(gt) == mi_act_block(q) && ggml_type_size(gt) == (size_t) mi_act_block_bytes(q));
+    }
+    return true;
+}
+
+extern "C" {
+
 bool ggml_backend_is_mi355x(ggml_backend_t backend) {
     return backend != nullptr && ggml_guid_matches(backend->guid, mi_guid());
 }
@@ -3226,6 +3238,8 @@ ggml_backend_t ggml_backend_mi355x_init(int device) {
         fprintf(stderr, "%s: invalid device %d (have %d)\n", __func__, device, device_count());
         return nullptr;
     }
+    static const bool table_checked = check_type_table();
+    (void) table_checked;
     auto * ctx = new mi_backend_ctx();
     ctx->device = device;
     ctx->name = "MI355X" + std::to_string(device);
@@ -3283,17 +3297,17 @@ size_t ggml_backend_mi355x_planes_stats(size_t * bytes) {
 bool ggml_backend_mi355x_quantize_activations(ggml_backend_t backend, int vec_dot_type, const float * x, int64_t K,
                                               int64_t ncols, int8_t * qs, float * d, int16_t * s32) {
     MI_ASSERT(ggml_backend_is_mi355x(backend));
-    const bool is_k = vec_dot_type == GGML_TYPE_Q8_K;
-    const bool is_1 = vec_dot_type == GGML_TYPE_Q8_1;  // s32: the fp16 bits of the blocks' s
-    if (!is_k && !is_1 && vec_dot_type != GGML_TYPE_Q8_0) return false;
-    if (K % (is_k ? 256 : 32) != 0) return false;
+    const mi_act_quant q = q8_quant_of((ggml_type) vec_dot_type);
+    const bool is_k = q == MI_ACT_Q8_K;
+    const bool is_1 = q == MI_ACT_Q8_1;  // s32: the fp16 bits of the blocks' s
+    if (q == MI_ACT_NONE || K % mi_act_block(q) != 0) return false;
     auto * ctx = (mi_backend_ctx *) backend->context;
     mi_device_guard g(ctx->device);
     const size_t xbytes = (size_t) K * ncols * sizeof(float);
     void * dx = nullptr;
     void * dq = nullptr;
     MI_CHECK(hipMalloc(&dx, xbytes));
-    MI_CHECK(hipMalloc(&dq, mi_act_q8_bytes(K, ncols, is_k, is_1)));
+    MI_CHECK(hipMalloc(&dq, mi_act_q8_bytes(K, ncols, q)));
     MI_CHECK(hipMemcpy(dx, x, xbytes, hipMemcpyHostToDevice));
     mi_src_cols src;
     src.base = (const char *) dx;
@@ -3301,13 +3315,13 @@ bool ggml_backend_mi355x_quantize_activations(ggml_backend_t backend, int vec_do
     src.ne2 = src.ne3 = 1;
     src.nb1 = (size_t) K * sizeof(float);
     src.nb2 = src.nb3 = src.nb1 * ncols;
-    const mi_act_q8 act = mi_act_q8_carve(dq, K, ncols, is_k, is_1);
+    const mi_act_q8 act = mi_act_q8_carve(dq, K, ncols, q);
     if (is_k) mi_quantize_q8_K(src, K, act, ctx->stream);
     else if (is_1) mi_quantize_q8_1(src, K, act, ctx->stream);
     else mi_quantize_q8_0(src, K, act, ctx->stream);
     MI_CHECK(hipStreamSynchronize(ctx->stream));
     MI_CHECK(hipMemcpy(qs, act.qs, (size_t) K * ncols, hipMemcpyDeviceToHost));
-    MI_CHECK(hipMemcpy(d, act.d, (size_t) (K / (is_k ? 256 : 32)) * ncols * sizeof(float), hipMemcpyDeviceToHost));
+    MI_CHECK(hipMemcpy(d, act.d, (size_t) (K / mi_act_block(q)) * ncols * sizeof(float), hipMemcpyDeviceToHost));
     if ((is_k || is_1) && s32) MI_CHECK(hipMemcpy(s32, act.s32, (size_t) (K / 32) * ncols * sizeof(int16_t), hipMemcpyDeviceToHost));
     MI_CHECK(hipFree(dx));
     MI_CHECK(hipFree(dq));

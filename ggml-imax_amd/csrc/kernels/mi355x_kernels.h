@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mi355x_types.h"
+
 // Activation columns of one mul_mat, quantized exactly as the reference CPU path quantizes
 // them (vec_dot_type from_float, src/ggml.c:11952-11974), stored structure-of-arrays in HBM:
 //   qs  [ncols][K]      int8 quants
@@ -62,8 +64,9 @@ struct mi_mm_desc {
     mi_mm_ids id;          // MUL_MAT_ID (then ne02 = n_as, ne12 = n_tokens, ne03 = ne13 = 1)
 };
 
-size_t mi_act_q8_bytes(int64_t K, int64_t ncols, bool is_q8K, bool is_q8_1 = false);
-mi_act_q8 mi_act_q8_carve(void * base, int64_t K, int64_t ncols, bool is_q8K, bool is_q8_1 = false);
+// q: MI_ACT_Q8_0, MI_ACT_Q8_1 or MI_ACT_Q8_K
+size_t mi_act_q8_bytes(int64_t K, int64_t ncols, mi_act_quant q);
+mi_act_q8 mi_act_q8_carve(void * base, int64_t K, int64_t ncols, mi_act_quant q);
 
 void mi_quantize_q8_0(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, hipStream_t s);
 void mi_quantize_q8_1(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, hipStream_t s);
@@ -73,7 +76,7 @@ void mi_quantize_q8_K(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, h
 void mi_convert_f16(const mi_src_cols & x, int64_t K, uint16_t * out, hipStream_t s, bool blocked = false, bool src_f16 = false);
 // quantize to q8_K / q8_0 exactly as above and store f16(d * q) as [ncols][K] (no q8 blocks):
 // the activation operand of mi_mul_mat_mmq for quantized weights
-void mi_quantize_expand_f16(const mi_src_cols & x, int64_t K, int64_t ncols, bool is_q8K, uint16_t * xh, hipStream_t s,
+void mi_quantize_expand_f16(const mi_src_cols & x, int64_t K, int64_t ncols, mi_act_quant q, uint16_t * xh, hipStream_t s,
                             bool blocked = false);
 // the layout mi_mul_mat_mmq expects for xh under the current tuning (true: K-blocked)
 bool mi_mmq_wants_blocked();
@@ -125,7 +128,7 @@ struct mi_mmv_group {
         int mode = 0;  // 0 none, 1 norm, 2 rms_norm
     } pro;
     int pro_off = 0;   // set by the launcher: LDS byte offset of the normalized columns
-    int q0r = 0;       // Q4_0 / Q8_0: every member's W is its 16-byte-aligned repacked copy (mi_planes_get type 2 / 8), nb01 = K / 32 * 18 / 34
+    int q0r = 0;       // Q4_0 / Q8_0: every member's W is its 16-byte-aligned repacked copy (mi_planes_get), nb01 = K / 32 * the block's bytes
     int pro_q = 0;     // set by the launcher (g_mi_tuning.mmv_pro4): one Q8_K column's norm prologue quantizes from registers
     mi_mmv_member m[kMiMaxMembers];
     // GGML_OP_MUL_MAT_ID decode (behind m: the other fields keep their places; ncols == 1, no prologue / epilogue): ids_w != nullptr makes every
@@ -204,6 +207,9 @@ extern thread_local int tl_mi_graph_order;
 inline int mi_mmv_order() { return g_mi_tuning.mmv_order >= 0 ? g_mi_tuning.mmv_order : tl_mi_graph_order; }
 size_t mi_mmv_fused_lds_bytes(int type, int64_t K, int64_t ncols);
 void mi_mul_mat_q_fused(mi_mmv_group & g, hipStream_t s);
+// its per-format launchers, specialized in mmv_fused_q4k.hip, _q5k, _q6k, _q40, _q80, _q41, _q50, _q51 (one
+// translation unit each, so that the formats build in parallel)
+template <int T> void mi_mmv_launch(const mi_mmv_group & g, int variant, hipStream_t s);
 // Batched (prefill) mul_mat on MFMA: 2-D weights [K, N] of type Q4_0/Q8_0/Q4_K/Q5_K/F16,
 // `ncols` activation columns already converted: xh = f16 [ncols][K] (F16 weights: the f16
 // activations; quantized weights: f16(d * q) from mi_quantize_expand_f16), or, for quantized
@@ -254,9 +260,8 @@ void mi_quantize_q8_0_mmx_group(mi_mmx_qgroup & q, hipStream_t s);
 // src1 of the weight's vec_dot type (quantize.hip): GGML_OP_CPY F32 -> Q8_K / Q8_0 / Q8_1 rows in the
 // reference block layouts (dst columns addressed like src1's), and such rows -> the GEMV's q8 SoA
 // (act) or the prefill GEMMs' MFMA layout (mx); exactly one of act / mx non-null (Q8_1: act)
-void mi_quantize_rows_q8(const mi_src_cols & x, int64_t K, bool is_q8K, const mi_src_cols & dst, hipStream_t s, bool is_q8_1 = false);
-void mi_q8_rows_to_act(const mi_src_cols & xs, int64_t K, bool is_q8K, const mi_act_q8 * act, const mi_act_mmx * mx, hipStream_t s,
-                       bool is_q8_1 = false);
+void mi_quantize_rows_q8(const mi_src_cols & x, int64_t K, mi_act_quant q, const mi_src_cols & dst, hipStream_t s);
+void mi_q8_rows_to_act(const mi_src_cols & xs, int64_t K, mi_act_quant q, const mi_act_q8 * act, const mi_act_mmx * mx, hipStream_t s);
 bool mi_mmqx_supported(int type, int64_t K, size_t ycol, int64_t ncols, size_t nb01);
 // Independent Q4_K / Q5_K (q8_K activations) or Q4_0 / Q8_0 (q8_0 activations, mi_act_mmx0_*)
 // mul_mats (same type, K and activation column count) in one launch:
@@ -290,10 +295,14 @@ void mi_mul_mat_mmqx(int type, const void * W, size_t nb01, int64_t K, int64_t N
 // weight memory must be followed by mi_planes_refresh over the written bytes (a repack launch on
 // s for every overlapping entry; capturable); freeing the memory by mi_planes_drop.
 constexpr int64_t kMiPlanesMinCols = 129;  // prompts of more columns take the planes kernel
-// Types 2 / 8 (Q4_0 / Q8_0, g_mi_tuning.q40r / q80r): the tree-order decode GEMV's 16-byte-aligned
-// copy instead (k_q40_repack / k_q80_repack: per row the quants of every block, then their f16
-// scales; K / 32 * 18 / 34 bytes a row).
+// Types with mi_type().aligned_copy (Q4_0 / Q8_0, g_mi_tuning.q40r / q80r): the tree-order decode
+// GEMV's 16-byte-aligned copy instead (k_q40_repack / k_q80_repack: per row the quants of every
+// block, then their f16 scales; as many bytes a row as the canonical blocks).
 const char * mi_planes_get(int type, const void * W, size_t nb01, int64_t K, int64_t N, hipStream_t s);
+// the knob of a type's aligned copy (false: the type has none)
+inline bool mi_aligned_copy_on(int type) {
+    return mi_type(type).aligned_copy && (type == MI_TYPE_Q4_0 ? g_mi_tuning.q40r : g_mi_tuning.q80r) != 0;
+}
 void mi_planes_refresh(const void * lo, size_t bytes, hipStream_t s);
 void mi_planes_drop(const void * lo, size_t bytes);
 size_t mi_planes_count();
@@ -303,7 +312,7 @@ size_t mi_planes_bytes();
 bool mi_mul_mat_mmqr_group(mi_mmx_group & g, hipStream_t s);
 
 // ---- companion ops (ops.hip) ----
-// a tensor view as the element-wise kernels see it: f32 (type 0), f16 (1) or i32 (26) elements
+// a tensor view as the element-wise kernels see it: MI_TYPE_F32, MI_TYPE_F16 or MI_TYPE_I32 elements
 struct mi_tensor_desc {
     char * data;
     int type;

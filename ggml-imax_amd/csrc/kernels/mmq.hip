@@ -75,8 +75,8 @@ struct WRaw;
 // Q4_K / Q5_K: header (d, dmin, 12 scale bytes) + 16 quant bytes (+ 16 qh bytes)
 template <int TYPE>
 struct WRaw {
-    static constexpr bool Q5 = TYPE == 13;
-    static constexpr int BS = Q5 ? 176 : 144;
+    static constexpr bool Q5 = TYPE == MI_TYPE_Q5_K;
+    static constexpr int BS = mi_type(Q5 ? MI_TYPE_Q5_K : MI_TYPE_Q4_K).bytes;
     uint4 hdr, qs, qh;
     __device__ __forceinline__ void load(const uint8_t * row, int64_t k) {
         // k: first of the 16 elements; within superblock s = k/256, 64-group j, part p = 0..3
@@ -156,9 +156,9 @@ struct WRawF16 {
 };
 
 template <int TYPE> struct raw_of { using T = WRaw<TYPE>; };
-template <> struct raw_of<2> { using T = WRawQ0<false>; };
-template <> struct raw_of<8> { using T = WRawQ0<true>; };
-template <> struct raw_of<1> { using T = WRawF16; };
+template <> struct raw_of<MI_TYPE_Q4_0> { using T = WRawQ0<false>; };
+template <> struct raw_of<MI_TYPE_Q8_0> { using T = WRawQ0<true>; };
+template <> struct raw_of<MI_TYPE_F16> { using T = WRawF16; };
 
 // ---- the GEMM ---------------------------------------------------------------------------------
 template <int TYPE, int SK>
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256 * SK) void k_mmq2(const uint8_t * __restrict__ 
     };
     auto store_stage = [&](int buf, const Raw & rw, const uint4 (&xv)[4], int64_t k0) {
         _Float16 * pa = la[buf] + ar * LDS_STRIDE + ak;
-        if constexpr (TYPE == 1) {
+        if constexpr (TYPE == MI_TYPE_F16) {
             *(uint4 *) pa = alive ? rw.a : make_uint4(0, 0, 0, 0);
             *(uint4 *) (pa + 8) = alive ? rw.b : make_uint4(0, 0, 0, 0);
         } else {
@@ -349,7 +349,7 @@ __global__ __launch_bounds__(256 * SK) void k_mmq3(const uint8_t * __restrict__ 
     };
     auto store_stage = [&](int buf, const Raw & rw, int64_t k0) {
         _Float16 * pa = la0 + buf * (BM * LDS_STRIDE) + ar * LDS_STRIDE + ak;
-        if constexpr (TYPE == 1) {
+        if constexpr (TYPE == MI_TYPE_F16) {
             *(uint4 *) pa = alive ? rw.a : make_uint4(0, 0, 0, 0);
             *(uint4 *) (pa + 8) = alive ? rw.b : make_uint4(0, 0, 0, 0);
         } else {
@@ -560,23 +560,23 @@ void mi_mul_mat_f16p(const void * W, size_t nb01, int64_t K, int64_t N, const ui
 bool mi_mmq_wants_blocked() { return (g_mi_tuning.mmq_variant & kMmqActLds) == 0; }
 
 bool mi_mmq_supported(int type, int64_t K, size_t nb01, size_t ycol) {
-    if (type != 12 && type != 13 && type != 2 && type != 8 && type != 1) return false;
+    if (!mi_type(type).mmq) return false;
     if (K % 256 != 0) return false;
-    if (type == 1 && nb01 % 16 != 0) return false;
+    if (type == MI_TYPE_F16 && nb01 % 16 != 0) return false;
     return ycol % 16 == 0;
 }
 
 size_t mi_mmq_scratch_bytes(int type, int64_t K, int64_t ncols) {
-    return type == 1 ? 0 : (size_t) K * ncols * sizeof(uint16_t);
+    return type == MI_TYPE_F16 ? 0 : (size_t) K * ncols * sizeof(uint16_t);
 }
 
 void mi_mul_mat_mmq(int type, const void * W, size_t nb01, int64_t K, int64_t N, const mi_act_q8 & act, const uint16_t * xh,
                     int64_t ncols, float * dst, size_t ycol, uint16_t * scratch, hipStream_t s) {
-    if (type != 1 && xh == nullptr) {
+    if (type != MI_TYPE_F16 && xh == nullptr) {
         // quantized activations -> f16(d * q) once for all column tiles
         const int64_t total8 = K * ncols / 8;
         const unsigned grid = (unsigned) std::min<int64_t>((total8 + 255) / 256, 8192);
-        if (type == 12 || type == 13) hipLaunchKernelGGL(k_act_to_f16<256>, dim3(grid), dim3(256), 0, s, act, K, scratch, total8);
+        if (mi_type(type).act == MI_ACT_Q8_K) hipLaunchKernelGGL(k_act_to_f16<256>, dim3(grid), dim3(256), 0, s, act, K, scratch, total8);
         else hipLaunchKernelGGL(k_act_to_f16<32>, dim3(grid), dim3(256), 0, s, act, K, scratch, total8);
         xh = scratch;
     }
@@ -603,14 +603,11 @@ void mi_mul_mat_mmq(int type, const void * W, size_t nb01, int64_t K, int64_t N,
     else if (v3) hipLaunchKernelGGL((k_mmq3<T, 1, 0, false>), grid, dim3(256), 0, s, w, nb01, K, N, xh, ncols, dst, ycol);       \
     else if (sk2) hipLaunchKernelGGL((k_mmq2<T, 2>), grid, dim3(512), 0, s, w, nb01, K, N, xh, ncols, dst, ycol);      \
     else hipLaunchKernelGGL((k_mmq2<T, 1>), grid, dim3(256), 0, s, w, nb01, K, N, xh, ncols, dst, ycol);
-    switch (type) {
-        case 12: MI_MMQ_LAUNCH(12) break;
-        case 13: MI_MMQ_LAUNCH(13) break;
-        case 2: MI_MMQ_LAUNCH(2) break;
-        case 8: MI_MMQ_LAUNCH(8) break;
-        case 1: MI_MMQ_LAUNCH(1) break;
-        default: break;
-    }
+    mi_dispatch_type(type, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        if constexpr (mi_type(T).mmq) { MI_MMQ_LAUNCH(T) }
+        else MI_ASSERT(!"mi_mul_mat_mmq: no dequantizer for this weight type");
+    });
 #undef MI_MMQ_LAUNCH
 #undef MI_MMQ3
 }

@@ -1222,7 +1222,7 @@ template <bool Q8, int RING = 2>
 __global__ __launch_bounds__(256, 2) void k_mmq0p(mi_mmx_group grp) {
     MI_MMX_MEMBER(grp);
     constexpr int NW = 4;
-    constexpr int BS = Q8 ? 34 : 18;
+    constexpr int BS = mi_type(Q8 ? MI_TYPE_Q8_0 : MI_TYPE_Q4_0).bytes;
     constexpr int UB = 8 * BS;  // bytes of a row's 8-block unit: 144 / 272
     constexpr int NG = kCfoldGroups / NW;
     __shared__ __attribute__((aligned(16))) float red[kCfoldGroups * 16 * 64];  // [group][el][lane]
@@ -1401,7 +1401,7 @@ __global__ __launch_bounds__(256, 2) void k_mmq0p(mi_mmx_group grp) {
 template <bool Q8, int NWV, int LEAD, int NR = 1>
 __global__ __launch_bounds__(64 * NWV, NR == 2 ? 2 : 1) void k_mmq0x(mi_mmx_group grp) {
     MI_MMX_MEMBER(grp);
-    constexpr int BS = Q8 ? 34 : 18;
+    constexpr int BS = mi_type(Q8 ? MI_TYPE_Q8_0 : MI_TYPE_Q4_0).bytes;
     constexpr int UB = 8 * BS;                // bytes of a row's unit
     constexpr int ND = Q8 ? 9 : 5;            // dwords covering a block (2-byte aligned)
     constexpr int XR = 256 + 16;              // LDS row stride of the operand plane
@@ -1872,10 +1872,11 @@ __global__ __launch_bounds__(1024) void k_mmqd16(mi_mmx_group grp) {
 bool mi_mmqx_supported(int type, int64_t K, size_t ycol, int64_t ncols, size_t nb01) {
     // buffer descriptors address < 2 GiB: activations K * ncols bytes, a 64-row weight block;
     // Q4_0 / Q8_0: 16-byte aligned 8-block units (K % 256 == 0, rows of 16-byte multiples)
-    if (type == 2 || type == 8) {
+    if (!mi_type(type).mmqx) return false;
+    if (mi_type(type).blck == 32) {
         return K % 256 == 0 && K >= 256 && nb01 % 16 == 0 && K * ncols < ((int64_t) 1 << 31) && (int64_t) nb01 * 32 < ((int64_t) 1 << 31);
     }
-    return (type == 12 || type == 13) && K % 256 == 0 && K >= 256 && ycol % 16 == 0 && K * ncols < ((int64_t) 1 << 31) &&
+    return K % 256 == 0 && K >= 256 && ycol % 16 == 0 && K * ncols < ((int64_t) 1 << 31) &&
            (int64_t) nb01 * XBM < ((int64_t) 1 << 31);
 }
 
@@ -1897,7 +1898,7 @@ static int64_t mmx_deal(mi_mmx_group & g, int64_t tr, int64_t tc) {
 // NR = 2 with 8 waves (64 x 256). Every one keeps the family's canonical combine: the same bits.
 static void mmq0_group(mi_mmx_group & g, hipStream_t s) {
     const int var = g_mi_tuning.mmq_variant;
-    const bool q8 = g.type == 8;
+    const bool q8 = g.type == MI_TYPE_Q8_0;
     int pick;
     if (var & kMmqShortKernels) pick = 0;
     else if (var & kMmqLongKernels) pick = (var & kMmq0xRows2W8) ? 4 : (var & kMmq0xRows2) ? 3 : (var & kMmqHalfWidth) ? 2 : 1;
@@ -1955,8 +1956,9 @@ static bool mmx_dst_local(const mi_mmx_group & g) {
 // runs them. One decision per kernel, top to bottom; the first that applies launches.
 void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
     if (g.n <= 0) return;
-    if (g.type == 2 || g.type == 8) return mmq0_group(g, s);
-    const bool q4 = g.type == 12;
+    MI_ASSERT(mi_type(g.type).mmqx);
+    if (mi_type(g.type).blck == 32) return mmq0_group(g, s);
+    const bool q4 = g.type == MI_TYPE_Q4_K;
     const int S = (int) (g.K / 256);
     const int64_t ncols = g.m[0].act.ncols;  // every member has the same column count
     const int var = g_mi_tuning.mmq_variant;
@@ -1975,8 +1977,8 @@ void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
     } while (0)
 #define MI_MMQX_T(KERN, TR, TC, NT, LDS, ...)                                      \
     do {                                                                          \
-        if (q4) MI_MMQX((KERN<12, ##__VA_ARGS__>), TR, TC, NT, LDS);              \
-        else MI_MMQX((KERN<13, ##__VA_ARGS__>), TR, TC, NT, LDS);                 \
+        if (q4) MI_MMQX((KERN<MI_TYPE_Q4_K, ##__VA_ARGS__>), TR, TC, NT, LDS);              \
+        else MI_MMQX((KERN<MI_TYPE_Q5_K, ##__VA_ARGS__>), TR, TC, NT, LDS);              \
     } while (0)
 
     // k_mmqr: long prompts on repacked planes (mmq_planes.hip) when every member carries them (each
@@ -1994,7 +1996,7 @@ void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
     constexpr int kAsksOther = kMmqShortKernels | kMmqLongKernels | kMmqd1 | kMmqNoD16 | kMmqNoShortT | kMmqd16 | kMmqd16Wide | kMmqp8;
     if (q4 && ncols > 32 && ncols <= 128 && dst_local && g_mi_tuning.mmqt_short > 0 && !(var & kAsksOther) &&
         tiles(128, 64) >= g_mi_tuning.mmqt_short) {
-        MI_MMQX((k_mmqt<12>), 128, 64, 512, 0);
+        MI_MMQX((k_mmqt<MI_TYPE_Q4_K>), 128, 64, 512, 0);
         return;
     }
 
@@ -2031,14 +2033,14 @@ void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
     // k_mmqw, B=256 18.5 vs 19.7, profiles/r04i_pf_long_mmqt.txt)
     const bool mmqx_asked = (var & (kMmqxOnly | kMmqxLead1)) != 0;
     if (q4 && !mmqx_asked) {
-        MI_MMQX((k_mmqt<12>), 128, 64, 512, 0);
+        MI_MMQX((k_mmqt<MI_TYPE_Q4_K>), 128, 64, 512, 0);
         return;
     }
 
     // k_mmqw: Q5_K, warp-specialized (4 loader + 8 MFMA waves; Q5_K B=512 46.2 -> 43.8 us grouped,
     // profiles/r03r_prefill_mmqw.txt); its loader loop needs S % 4 == 0
     if (!q4 && !mmqx_asked && S % 4 == 0) {
-        MI_MMQX((k_mmqw<13, 4>), XBM, XBN, 768, 0);
+        MI_MMQX((k_mmqw<MI_TYPE_Q5_K, 4>), XBM, XBN, 768, 0);
         return;
     }
 

@@ -129,9 +129,9 @@ __device__ __forceinline__ float cfold_groups(int ngroups, At && at) {
 
 template <int TYPE>
 struct XFmt {
-    static constexpr bool Q5 = TYPE == 13;
+    static constexpr bool Q5 = TYPE == MI_TYPE_Q5_K;
     static constexpr int NP = Q5 ? 3 : 2;
-    static constexpr int BS = Q5 ? 176 : 144;
+    static constexpr int BS = mi_type(Q5 ? MI_TYPE_Q5_K : MI_TYPE_Q4_K).bytes;
     static constexpr int SHIFT = Q5 ? 2 : 3;  // T = sum_p P_p << (SHIFT * p)
     __device__ static __forceinline__ uint32_t factor(int sc, int p) {
         if constexpr (Q5) return (uint32_t) ((sc >> (2 * p)) & 3);

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(64) void k_planes_repack(const uint8_t * __restrict
                                                       char * __restrict__ planes) {
     using P = PFmt<TYPE>;
     constexpr int NP = P::NP;
-    constexpr bool Q5 = TYPE == 13;
+    constexpr bool Q5 = TYPE == MI_TYPE_Q5_K;
     constexpr int BS = XFmt<TYPE>::BS;
     const int lane = (int) threadIdx.x;
     const int r = lane & 31, h = lane >> 5;
@@ -280,11 +280,11 @@ __global__ __launch_bounds__(256) void k_q40_repack(const uint8_t * __restrict__
     const int64_t n = blockIdx.x;
     const int64_t b = (int64_t) blockIdx.y * 256 + threadIdx.x;
     if (b >= nblk) return;
-    const uint16_t * src = (const uint16_t *) (W + (size_t) n * nb01 + (size_t) b * 18);  // 2-byte aligned
+    const uint16_t * src = (const uint16_t *) (W + (size_t) n * nb01 + (size_t) b * mi_type(MI_TYPE_Q4_0).bytes);  // 2-byte aligned
     uint16_t h[9];
 #pragma unroll
     for (int i = 0; i < 9; i++) h[i] = src[i];
-    uint8_t * row = out + (size_t) n * (size_t) nblk * 18;
+    uint8_t * row = out + (size_t) n * (size_t) nblk * mi_type(MI_TYPE_Q4_0).bytes;
     uint4 q;
     q.x = h[1] | ((uint32_t) h[2] << 16);
     q.y = h[3] | ((uint32_t) h[4] << 16);
@@ -300,11 +300,11 @@ __global__ __launch_bounds__(256) void k_q80_repack(const uint8_t * __restrict__
     const int64_t n = blockIdx.x;
     const int64_t b = (int64_t) blockIdx.y * 256 + threadIdx.x;
     if (b >= nblk) return;
-    const uint16_t * src = (const uint16_t *) (W + (size_t) n * nb01 + (size_t) b * 34);  // 2-byte aligned
+    const uint16_t * src = (const uint16_t *) (W + (size_t) n * nb01 + (size_t) b * mi_type(MI_TYPE_Q8_0).bytes);  // 2-byte aligned
     uint16_t h[17];
 #pragma unroll
     for (int i = 0; i < 17; i++) h[i] = src[i];
-    uint8_t * row = out + (size_t) n * (size_t) nblk * 34;
+    uint8_t * row = out + (size_t) n * (size_t) nblk * mi_type(MI_TYPE_Q8_0).bytes;
 #pragma unroll
     for (int v = 0; v < 2; v++) {
         uint4 q;
@@ -335,18 +335,18 @@ std::atomic<uint64_t> g_planes_gen{0};       // bumped whenever an entry is crea
 int planes_enabled() { return g_mi_tuning.planes; }
 
 void launch_repack(const PlanesEntry & e, const void * W, hipStream_t s) {
-    if (e.type == 2 || e.type == 8) {
+    if (mi_type(e.type).aligned_copy) {
         const int64_t nblk = e.K / 32;
         const dim3 grid((unsigned) e.N, (unsigned) ((nblk + 255) / 256));
-        if (e.type == 2) hipLaunchKernelGGL(k_q40_repack, grid, dim3(256), 0, s, (const uint8_t *) W, e.nb01, nblk, (uint8_t *) e.planes);
+        if (e.type == MI_TYPE_Q4_0) hipLaunchKernelGGL(k_q40_repack, grid, dim3(256), 0, s, (const uint8_t *) W, e.nb01, nblk, (uint8_t *) e.planes);
         else hipLaunchKernelGGL(k_q80_repack, grid, dim3(256), 0, s, (const uint8_t *) W, e.nb01, nblk, (uint8_t *) e.planes);
         return;
     }
     const int S = (int) (e.K / 256);
     const int64_t nt = (e.N + 31) / 32;
     const dim3 grid((unsigned) S, (unsigned) nt);
-    if (e.type == 12) hipLaunchKernelGGL((k_planes_repack<12>), grid, dim3(64), 0, s, (const uint8_t *) W, e.nb01, e.N, S, (int64_t) 0, e.planes);
-    else hipLaunchKernelGGL((k_planes_repack<13>), grid, dim3(64), 0, s, (const uint8_t *) W, e.nb01, e.N, S, (int64_t) 0, e.planes);
+    if (e.type == MI_TYPE_Q4_K) hipLaunchKernelGGL((k_planes_repack<MI_TYPE_Q4_K>), grid, dim3(64), 0, s, (const uint8_t *) W, e.nb01, e.N, S, (int64_t) 0, e.planes);
+    else hipLaunchKernelGGL((k_planes_repack<MI_TYPE_Q5_K>), grid, dim3(64), 0, s, (const uint8_t *) W, e.nb01, e.N, S, (int64_t) 0, e.planes);
 }
 
 } // namespace
@@ -354,10 +354,11 @@ void launch_repack(const PlanesEntry & e, const void * W, hipStream_t s) {
 const char * mi_planes_get(int type, const void * W, size_t nb01, int64_t K, int64_t N, hipStream_t s) {
     // (Q4_K: the planes kernel beats the canonical one; Q5_K's 3 planes do not fit its LDS stages.
     // Q4_0 / Q8_0: the 16-byte-aligned decode copies, g_mi_tuning.q40r / q80r)
-    const bool q0 = type == 2 || type == 8;  // the aligned decode copies (Q4_0 / Q8_0)
-    if (type == 2 ? !g_mi_tuning.q40r : type == 8 ? !g_mi_tuning.q80r : (!planes_enabled() || type != 12)) return nullptr;
+    const mi_type_info ti = mi_type(type);
+    const bool q0 = ti.aligned_copy;  // the aligned decode copies (Q4_0 / Q8_0)
+    if (q0 ? !mi_aligned_copy_on(type) : (!planes_enabled() || !ti.planes)) return nullptr;
     if (K % 256 != 0 || N <= 0 || !W) return nullptr;
-    const int64_t row_min = q0 ? K / 32 * (type == 2 ? 18 : 34) : K / 256 * (type == 12 ? 144 : 176);
+    const int64_t row_min = K / ti.blck * ti.bytes;
     if (nb01 % (q0 ? 2 : 4) != 0 || (int64_t) nb01 < row_min) return nullptr;
     std::lock_guard<std::mutex> lk(g_planes_mu);
     auto it = g_planes.find((uintptr_t) W);
@@ -385,7 +386,7 @@ const char * mi_planes_get(int type, const void * W, size_t nb01, int64_t K, int
     e.K = K;
     e.N = N;
     e.span = (size_t) (N - 1) * nb01 + (size_t) row_min;
-    e.bytes = q0 ? (size_t) N * (size_t) row_min : (size_t) ((N + 31) / 32) * (K / 256) * (type == 12 ? PFmt<12>::RB : PFmt<13>::RB);
+    e.bytes = q0 ? (size_t) N * (size_t) row_min : (size_t) ((N + 31) / 32) * (K / 256) * (type == MI_TYPE_Q4_K ? PFmt<MI_TYPE_Q4_K>::RB : PFmt<MI_TYPE_Q5_K>::RB);
     (void) hipGetDevice(&e.device);
     void * p = nullptr;
     if (hipMalloc(&p, e.bytes) != hipSuccess) {
@@ -444,13 +445,13 @@ size_t mi_planes_bytes() {
 }
 
 bool mi_mul_mat_mmqr_group(mi_mmx_group & g, hipStream_t s) {
-    if (g.n <= 0 || g.type != 12 || g.K % 256 != 0) return false;
+    if (g.n <= 0 || !mi_type(g.type).planes || g.K % 256 != 0) return false;
     int64_t tiles = 0;
     for (int i = 0; i < g.n; i++) {
         if (!g.m[i].planes) return false;
         g.m[i].tile_begin = tiles;
         tiles += ((g.m[i].N + 63) / 64) * ((g.m[i].act.ncols + 127) / 128);
     }
-    hipLaunchKernelGGL((k_mmqr<12>), dim3((unsigned) tiles), dim3(512), 0, s, g);
+    hipLaunchKernelGGL((k_mmqr<MI_TYPE_Q4_K>), dim3((unsigned) tiles), dim3(512), 0, s, g);
     return true;
 }

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void k_mmv_kq(const uint8_t * __restrict__ W, 
     if (row >= g.N) return;
     mmv_item<NC, ID> bi;
     if (!bi.init(g)) return;
-    constexpr int BS = Q5 ? 176 : 144;
+    constexpr int BS = mi_type(Q5 ? MI_TYPE_Q5_K : MI_TYPE_Q4_K).bytes;
     const uint8_t * wrow = W + bi.wofs + row * g.nb01;
     const int nsb = (int) (g.K / 256);
 
@@ -201,20 +201,21 @@ __global__ __launch_bounds__(256) void k_mmv_kq(const uint8_t * __restrict__ W, 
 
 // ---------------------------------------------------------------- 32-element blocks x Q8_0 / Q8_1
 //
-// T is the weight's ggml_type: Q4_0 (2, 18 B: fp16 d, qs[16]), Q8_0 (8, 34 B: fp16 d, int8 qs[32]),
-// Q4_1 (3, 20 B: fp16 d, m, qs[16]), Q5_0 (6, 22 B: fp16 d, qh[4], qs[16]), Q5_1 (7, 24 B: fp16 d, m,
-// qh[4], qs[16]). In the nibble formats element j < 16 is the low nibble of qs[j], element j >= 16
-// the high nibble of qs[j - 16]; bit j of the little-endian qh is the fifth bit of element j.
+// T is the weight's ggml_type: Q4_0 (18 B: fp16 d, qs[16]), Q8_0 (34 B: fp16 d, int8 qs[32]),
+// Q4_1 (20 B: fp16 d, m, qs[16]), Q5_0 (22 B: fp16 d, qh[4], qs[16]), Q5_1 (24 B: fp16 d, m,
+// qh[4], qs[16]); the facts below are its row of the table in mi355x_types.h. In the nibble
+// formats element j < 16 is the low nibble of qs[j], element j >= 16 the high nibble of
+// qs[j - 16]; bit j of the little-endian qh is the fifth bit of element j.
 // Values: Q4_0 (q - 8) d, Q5_0 (q - 16) d, Q4_1 / Q5_1 q d + m. Q4_1 / Q5_1 dot with Q8_1
 // activations, whose per-block s = fp16(d * sum(qs)) lies as fp16 bits in act.s32.
 template <int T> struct q32_fmt {
-    static constexpr bool Q8 = T == 8;
-    static constexpr bool HAS_M = T == 3 || T == 7;   // fp16 m after d, Q8_1 activations
-    static constexpr bool HAS_QH = T == 6 || T == 7;  // fifth bits
-    static constexpr int BS = T == 2 ? 18 : T == 8 ? 34 : T == 3 ? 20 : T == 6 ? 22 : 24;
+    static constexpr bool Q8 = T == MI_TYPE_Q8_0;
+    static constexpr bool HAS_M = mi_type(T).has_m;    // fp16 m after d, Q8_1 activations
+    static constexpr bool HAS_QH = mi_type(T).has_qh;  // fifth bits
+    static constexpr int BS = mi_type(T).bytes;
     static constexpr int QH = HAS_M ? 4 : 2;          // offset of qh
     static constexpr int QS = (HAS_M ? 4 : 2) + (HAS_QH ? 4 : 0);  // offset of the quants
-    static constexpr int SUB = T == 2 ? 8 : T == 6 ? 16 : 0;  // subtracted from every level
+    static constexpr int SUB = mi_type(T).sub;  // subtracted from every level
 };
 
 // four fifth bits (bits 0..3 of x) to bit 4 of four bytes: bit b of x * 0x00204081 lands at b, b + 7,
@@ -396,7 +397,7 @@ __global__ __launch_bounds__(256) void k_mmv_kq_ord(const uint8_t * __restrict__
     const int64_t rc = live ? row : g.N - 1;  // (dead groups run a valid row: no early exit before the shuffles)
     mmv_item<NC, ID> bi;
     if (!bi.init(g)) return;
-    constexpr int BS = Q5 ? 176 : 144;
+    constexpr int BS = mi_type(Q5 ? MI_TYPE_Q5_K : MI_TYPE_Q4_K).bytes;
     const uint8_t * wrow = W + bi.wofs + rc * g.nb01;
     const int nsb = (int) (g.K / 256);
 
@@ -515,7 +516,7 @@ __global__ __launch_bounds__(256) void k_mmv_q6k(const uint8_t * __restrict__ W,
         const int s = it >> 2;
         const int h = (it >> 1) & 1;
         const int u = it & 1;
-        const uint8_t * blk = wrow + (size_t) s * 210;
+        const uint8_t * blk = wrow + (size_t) s * mi_type(MI_TYPE_Q6_K).bytes;
         uint32_t la[4], lb[4], hh[4];
         load_qs_unaligned<16>(blk + 64 * h + 16 * u, la);
         load_qs_unaligned<16>(blk + 64 * h + 32 + 16 * u, lb);
@@ -576,7 +577,7 @@ __global__ __launch_bounds__(256) void k_mmv_q6k_ord(const uint8_t * __restrict_
     for (int c = 0; c < NC; c++) A[c] = 0.0f;
 
     for (int s = 0; s < nsb; s++) {
-        const uint8_t * blk = wrow + (size_t) s * 210;
+        const uint8_t * blk = wrow + (size_t) s * mi_type(MI_TYPE_Q6_K).bytes;
         const float dw = mi_h2f(*(const uint16_t *) (blk + 208));
         int q[8], sc[8];
 #pragma unroll
@@ -634,61 +635,51 @@ mmv_geom make_geom(const mi_mm_desc & m, int NC) {
 
 } // namespace
 
-#define MI_MMV_LAUNCH(KERNEL, NC, ...)                                                          \
-    do {                                                                                         \
-        const mmv_geom g = make_geom(m, NC);                                                     \
-        const dim3 grid((unsigned) ((m.N + kRowsPerBlock - 1) / kRowsPerBlock),                  \
-                        (unsigned) (g.col_chunks * m.ne12 * m.ne13));                            \
-        hipLaunchKernelGGL((KERNEL<NC, ##__VA_ARGS__>), grid, dim3(256), 0, s, (const uint8_t *) m.W, \
-                           act_or_x, m.dst, g);                                                  \
-    } while (0)
-
-#define MI_MMV_SWITCH(KERNEL, ...)                                  \
-    switch (nc) {                                                   \
-        case 1: MI_MMV_LAUNCH(KERNEL, 1, ##__VA_ARGS__); break;     \
-        case 2: MI_MMV_LAUNCH(KERNEL, 2, ##__VA_ARGS__); break;     \
-        case 3: MI_MMV_LAUNCH(KERNEL, 3, ##__VA_ARGS__); break;     \
-        case 4: MI_MMV_LAUNCH(KERNEL, 4, ##__VA_ARGS__); break;     \
-        default: MI_MMV_LAUNCH(KERNEL, 8, ##__VA_ARGS__); break;    \
+// One launch of weight type T's GEMV (its family by the table: 32-element blocks, Q6_K, Q4_K / Q5_K) in
+// tree order (a wave per row) or the reference CPU's order (ORD: 8 rows per wave), NC columns per
+// workgroup. ID as mmv_item; grid_y 0: the column chunks of every (i12, i13) batch.
+template <int T, int NC, int ID, bool ORD>
+static void mmv_launch(const mi_mm_desc & m, const mi_act_q8 & act, unsigned grid_y, hipStream_t s) {
+    const mmv_geom g = make_geom(m, NC);
+    const dim3 grid((unsigned) (ORD ? (m.N + 31) / 32 : (m.N + kRowsPerBlock - 1) / kRowsPerBlock),
+                    grid_y ? grid_y : (unsigned) (g.col_chunks * m.ne12 * m.ne13));
+    const uint8_t * W = (const uint8_t *) m.W;
+    constexpr bool Q5 = T == MI_TYPE_Q5_K;
+    if constexpr (mi_type(T).blck == 32) {
+        if constexpr (ORD) hipLaunchKernelGGL((k_mmv_q0_ord<NC, T, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
+        else hipLaunchKernelGGL((k_mmv_q0<NC, T, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
+    } else if constexpr (T == MI_TYPE_Q6_K) {
+        if constexpr (ORD) hipLaunchKernelGGL((k_mmv_q6k_ord<NC, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
+        else hipLaunchKernelGGL((k_mmv_q6k<NC, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
+    } else {
+        if constexpr (ORD) hipLaunchKernelGGL((k_mmv_kq_ord<NC, Q5, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
+        else hipLaunchKernelGGL((k_mmv_kq<NC, Q5, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
     }
+}
 
 // GGML_OP_MUL_MAT_ID: pair by pair (ID 1, one column per workgroup), or, with the device-built
 // chunk table, up to chunk_cap (8 or 4) gathered columns of one expert per workgroup (ID 2; the grid covers the
 // worst-case chunk count, workgroups past the real one exit at once). Same per-column arithmetic as
 // the plain kernels in both orders.
-static void mi_mul_mat_q_ids(const mi_mm_desc & m, const mi_act_q8 & act, hipStream_t s) {
-    const bool grouped = m.id.chunks != nullptr;
-    const bool cap4 = m.id.chunk_cap == 4;
+template <int T, bool ORD>
+static void mmv_launch_ids(const mi_mm_desc & m, const mi_act_q8 & act, hipStream_t s) {
     const int64_t pairs = (int64_t) m.id.n_ids * m.ne12;
-    const unsigned gy = (unsigned) (grouped ? mi_mmid_max_chunks(m.id.n_as, pairs, m.id.chunk_cap) : pairs);
-    const bool ord = mi_mmv_order() == 1;
-    const mmv_geom g = make_geom(m, 1);
-    const dim3 grid((unsigned) (ord ? (m.N + 31) / 32 : (m.N + kRowsPerBlock - 1) / kRowsPerBlock), gy);
-#define MI_MMID_LAUNCH(KERNEL, ...)                                                                                       \
-    do {                                                                                                                   \
-        if (grouped && cap4) hipLaunchKernelGGL((KERNEL<4, ##__VA_ARGS__, 2>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); \
-        else if (grouped) hipLaunchKernelGGL((KERNEL<8, ##__VA_ARGS__, 2>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); \
-        else hipLaunchKernelGGL((KERNEL<1, ##__VA_ARGS__, 1>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); \
-    } while (0)
-#define MI_MMID_LAUNCH0(KERNEL)                                                                                            \
-    do {                                                                                                                   \
-        if (grouped && cap4) hipLaunchKernelGGL((KERNEL<4, 2>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); \
-        else if (grouped) hipLaunchKernelGGL((KERNEL<8, 2>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g);     \
-        else hipLaunchKernelGGL((KERNEL<1, 1>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g);             \
-    } while (0)
-    switch (m.type) {
-        case 12: if (ord) MI_MMID_LAUNCH(k_mmv_kq_ord, false); else MI_MMID_LAUNCH(k_mmv_kq, false); break;
-        case 13: if (ord) MI_MMID_LAUNCH(k_mmv_kq_ord, true); else MI_MMID_LAUNCH(k_mmv_kq, true); break;
-        case 14: if (ord) MI_MMID_LAUNCH0(k_mmv_q6k_ord); else MI_MMID_LAUNCH0(k_mmv_q6k); break;
-        case 2: if (ord) MI_MMID_LAUNCH(k_mmv_q0_ord, 2); else MI_MMID_LAUNCH(k_mmv_q0, 2); break;
-        case 8: if (ord) MI_MMID_LAUNCH(k_mmv_q0_ord, 8); else MI_MMID_LAUNCH(k_mmv_q0, 8); break;
-        case 3: if (ord) MI_MMID_LAUNCH(k_mmv_q0_ord, 3); else MI_MMID_LAUNCH(k_mmv_q0, 3); break;
-        case 6: if (ord) MI_MMID_LAUNCH(k_mmv_q0_ord, 6); else MI_MMID_LAUNCH(k_mmv_q0, 6); break;
-        case 7: if (ord) MI_MMID_LAUNCH(k_mmv_q0_ord, 7); else MI_MMID_LAUNCH(k_mmv_q0, 7); break;
-        default: break;
+    if (!m.id.chunks) mmv_launch<T, 1, 1, ORD>(m, act, (unsigned) pairs, s);
+    else if (m.id.chunk_cap == 4) mmv_launch<T, 4, 2, ORD>(m, act, (unsigned) mi_mmid_max_chunks(m.id.n_as, pairs, 4), s);
+    else mmv_launch<T, 8, 2, ORD>(m, act, (unsigned) mi_mmid_max_chunks(m.id.n_as, pairs, m.id.chunk_cap), s);
+}
+
+// A plain mul_mat: columns per workgroup by the column count. Tree order 1, 2, 3, 4 or 8; the
+// reference order 1, 2, 4 or 8.
+template <int T, bool ORD>
+static void mmv_launch_cols(const mi_mm_desc & m, const mi_act_q8 & act, hipStream_t s) {
+    switch (m.ne11 >= 5 ? 8 : (int) m.ne11) {
+        case 1: mmv_launch<T, 1, 0, ORD>(m, act, 0, s); break;
+        case 2: mmv_launch<T, 2, 0, ORD>(m, act, 0, s); break;
+        case 3: mmv_launch<T, ORD ? 4 : 3, 0, ORD>(m, act, 0, s); break;
+        case 4: mmv_launch<T, 4, 0, ORD>(m, act, 0, s); break;
+        default: mmv_launch<T, 8, 0, ORD>(m, act, 0, s); break;
     }
-#undef MI_MMID_LAUNCH
-#undef MI_MMID_LAUNCH0
 }
 
 // The counting sort of the reference's MUL_MAT_ID (src/ggml.c:12169-12184: per-expert row lists in
@@ -759,87 +750,16 @@ void mi_mmid_group(const mi_mm_ids & id, int64_t n_tokens, int4 * chunks, int32_
 }
 
 void mi_mul_mat_q(const mi_mm_desc & m, const mi_act_q8 & act, hipStream_t s) {
-    if (m.id.ids) {
-        mi_mul_mat_q_ids(m, act, s);
-        return;
-    }
-    const int nc = m.ne11 >= 5 ? 8 : (int) m.ne11;
-    const mi_act_q8 act_or_x = act;
-    const bool q32 = m.type == 2 || m.type == 8 || m.type == 3 || m.type == 6 || m.type == 7;
-    if (mi_mmv_order() == 1 && q32) {  // reference CPU order: 8 rows per wave
-#define MI_MMV_ORD_LAUNCH(NC)                                                                               \
-        do {                                                                                                 \
-            const mmv_geom g = make_geom(m, NC);                                                             \
-            const dim3 grid((unsigned) ((m.N + 31) / 32), (unsigned) (g.col_chunks * m.ne12 * m.ne13));     \
-            switch (m.type) {                                                                                \
-                case 8: hipLaunchKernelGGL((k_mmv_q0_ord<NC, 8>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); break; \
-                case 3: hipLaunchKernelGGL((k_mmv_q0_ord<NC, 3>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); break; \
-                case 6: hipLaunchKernelGGL((k_mmv_q0_ord<NC, 6>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); break; \
-                case 7: hipLaunchKernelGGL((k_mmv_q0_ord<NC, 7>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); break; \
-                default: hipLaunchKernelGGL((k_mmv_q0_ord<NC, 2>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); break; \
-            }                                                                                                \
-        } while (0)
-        switch (nc) {
-            case 1: MI_MMV_ORD_LAUNCH(1); break;
-            case 2: MI_MMV_ORD_LAUNCH(2); break;
-            case 3: case 4: MI_MMV_ORD_LAUNCH(4); break;
-            default: MI_MMV_ORD_LAUNCH(8); break;
+    const bool ord = mi_mmv_order() == 1;
+    mi_dispatch_type(m.type, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        if constexpr (mi_type_quantized(T)) {
+            if (m.id.ids && ord) mmv_launch_ids<T, true>(m, act, s);
+            else if (m.id.ids) mmv_launch_ids<T, false>(m, act, s);
+            else if (ord) mmv_launch_cols<T, true>(m, act, s);
+            else mmv_launch_cols<T, false>(m, act, s);
+        } else {
+            MI_ASSERT(!"mi_mul_mat_q: not a quantized weight type");
         }
-#undef MI_MMV_ORD_LAUNCH
-        return;
-    }
-    if (mi_mmv_order() == 1 && (m.type == 12 || m.type == 13)) {  // reference CPU order, K-quants: 8 rows per wave
-        const bool q5 = m.type == 13;
-#define MI_MMV_KORD_LAUNCH(NC)                                                                               \
-        do {                                                                                                  \
-            const mmv_geom g = make_geom(m, NC);                                                              \
-            const dim3 grid((unsigned) ((m.N + 31) / 32), (unsigned) (g.col_chunks * m.ne12 * m.ne13));      \
-            if (q5) hipLaunchKernelGGL((k_mmv_kq_ord<NC, true>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); \
-            else hipLaunchKernelGGL((k_mmv_kq_ord<NC, false>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); \
-        } while (0)
-        switch (nc) {
-            case 1: MI_MMV_KORD_LAUNCH(1); break;
-            case 2: MI_MMV_KORD_LAUNCH(2); break;
-            case 3: case 4: MI_MMV_KORD_LAUNCH(4); break;
-            default: MI_MMV_KORD_LAUNCH(8); break;
-        }
-#undef MI_MMV_KORD_LAUNCH
-        return;
-    }
-    if (m.type == 14) {  // Q6_K: reference CPU order (8 rows per wave) or tree order (a wave per row)
-        if (mi_mmv_order() == 1) {
-#define MI_MMV_Q6ORD_LAUNCH(NC)                                                                              \
-        do {                                                                                                  \
-            const mmv_geom g = make_geom(m, NC);                                                              \
-            const dim3 grid((unsigned) ((m.N + 31) / 32), (unsigned) (g.col_chunks * m.ne12 * m.ne13));      \
-            hipLaunchKernelGGL((k_mmv_q6k_ord<NC>), grid, dim3(256), 0, s, (const uint8_t *) m.W, act, m.dst, g); \
-        } while (0)
-            switch (nc) {
-                case 1: MI_MMV_Q6ORD_LAUNCH(1); break;
-                case 2: MI_MMV_Q6ORD_LAUNCH(2); break;
-                case 3: case 4: MI_MMV_Q6ORD_LAUNCH(4); break;
-                default: MI_MMV_Q6ORD_LAUNCH(8); break;
-            }
-#undef MI_MMV_Q6ORD_LAUNCH
-            return;
-        }
-        switch (nc) {
-            case 1: MI_MMV_LAUNCH(k_mmv_q6k, 1); break;
-            case 2: MI_MMV_LAUNCH(k_mmv_q6k, 2); break;
-            case 3: MI_MMV_LAUNCH(k_mmv_q6k, 3); break;
-            case 4: MI_MMV_LAUNCH(k_mmv_q6k, 4); break;
-            default: MI_MMV_LAUNCH(k_mmv_q6k, 8); break;
-        }
-        return;
-    }
-    switch (m.type) {
-        case 12: MI_MMV_SWITCH(k_mmv_kq, false); break;  // Q4_K
-        case 13: MI_MMV_SWITCH(k_mmv_kq, true); break;   // Q5_K
-        case 2:  MI_MMV_SWITCH(k_mmv_q0, 2); break;  // Q4_0
-        case 8:  MI_MMV_SWITCH(k_mmv_q0, 8); break;  // Q8_0
-        case 3:  MI_MMV_SWITCH(k_mmv_q0, 3); break;  // Q4_1
-        case 6:  MI_MMV_SWITCH(k_mmv_q0, 6); break;  // Q5_0
-        case 7:  MI_MMV_SWITCH(k_mmv_q0, 7); break;  // Q5_1
-        default: break;
-    }
+    });
 }

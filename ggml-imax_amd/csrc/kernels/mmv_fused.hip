@@ -99,26 +99,17 @@ thread_local int tl_mi_graph_order = 0;
 
 bool mi_tuning_set(const char * name, int value) { return knob_set(g_mi_tuning, name, value); }
 
-// per-format launchers (mmv_fused_q4k.hip, _q5k, _q6k, _q40, _q80, _q41, _q50, _q51: one translation unit each)
-void mi_mmv_launch_q4k(const mi_mmv_group & g, int variant, hipStream_t s);
-void mi_mmv_launch_q5k(const mi_mmv_group & g, int variant, hipStream_t s);
-void mi_mmv_launch_q40(const mi_mmv_group & g, int variant, hipStream_t s);
-void mi_mmv_launch_q80(const mi_mmv_group & g, int variant, hipStream_t s);
-void mi_mmv_launch_q6k(const mi_mmv_group & g, int variant, hipStream_t s);
-void mi_mmv_launch_q41(const mi_mmv_group & g, int variant, hipStream_t s);
-void mi_mmv_launch_q50(const mi_mmv_group & g, int variant, hipStream_t s);
-void mi_mmv_launch_q51(const mi_mmv_group & g, int variant, hipStream_t s);
 
 // LDS of the quantized activations: qs [NC][K] int8 | d [NC][K/QKA] f32 | s32 [NC][K/32] int16
 // (lds_bytes in mmv_fused_impl.h)
 size_t mi_mmv_fused_lds_bytes(int type, int64_t K, int64_t ncols) {
     const int nc = ncols <= 2 ? (int) ncols : (ncols <= 4 ? 4 : 8);
-    const int64_t qka = (type == 12 || type == 13 || type == 14) ? 256 : 32;
+    const int64_t qka = mi_act_block(mi_type(type).act);
     return (size_t) nc * (K + (K / qka) * 4 + (K / 32) * 2);
 }
 
 bool mi_mmv_fused_supported(int type, int64_t K, int64_t ncols) {
-    if (type != 12 && type != 13 && type != 14 && type != 2 && type != 8 && type != 3 && type != 6 && type != 7) return false;
+    if (!mi_type(type).mmv_variant) return false;
     if (ncols < 1 || ncols > 8 || K % 256 != 0) return false;
     // more than 4 columns whose activations do not fit run as two launches of <= 4 columns
     return mi_mmv_fused_lds_bytes(type, K, ncols < 4 ? ncols : 4) <= 64 * 1024;  // + <= 36 KB of order scratch
@@ -148,26 +139,12 @@ void mi_mul_mat_q_fused(mi_mmv_group & g, hipStream_t s) {
 }
 
 static void mi_mul_mat_q_fused_launch(mi_mmv_group & g, hipStream_t s) {
-    // variant 0 = per-type default, from interleaved A/B runs on MI355X (tools/mmv_tune.py):
-    // prefetch depth 2 for Q4_K / Q8_0 / Q4_0 (Q4_0 in block pairs: 4096 x 11008 5.34 -> 5.58
-    // TB/s), depth 1 for Q5_K (fewer VGPRs, more waves)
-    // (Nontemporal weight loads -- the guide's nt-weights -- measured 30-37 % SLOWER on every
-    // shape, profiles/r04g_nt_ab.txt: removed.) Round-4 defaults from two interleaved sweeps on two
-    // boxes (profiles/r04p_gemv_sweep.txt, r04r_gemv_sweep.txt): Q4_K depth 3 (4096^2 +2..4 %,
-    // 4096 x 11008 +2..4 %), Q5_K depth 2 (+2 %), Q4_0 pairs depth 3 (+1..4 %), Q8_0 depth 1 (+1 %)
+    // variant 0 = the per-type default (the table in mi355x_types.h, with the measurements behind it)
     int variant = g_mi_tuning.mmv_variant;
-    // (Q4_1 / Q5_0 / Q5_1: depth 2 like the other 5- and 6-dword items, not tuned: DESIGN section 14)
-    if (variant == 0)
-        variant = g.type == 12 ? 31 : g.type == 13 || g.type == 14 || g.type == 3 || g.type == 6 || g.type == 7 ? 21 : g.type == 2 ? 32 : 11;
-    switch (g.type) {
-        case 12: mi_mmv_launch_q4k(g, variant, s); break;
-        case 13: mi_mmv_launch_q5k(g, variant, s); break;
-        case 14: mi_mmv_launch_q6k(g, variant, s); break;
-        case 3: mi_mmv_launch_q41(g, variant, s); break;
-        case 6: mi_mmv_launch_q50(g, variant, s); break;
-        case 7: mi_mmv_launch_q51(g, variant, s); break;
-        case 2: mi_mmv_launch_q40(g, variant, s); break;
-        case 8: mi_mmv_launch_q80(g, variant, s); break;
-        default: break;
-    }
+    if (variant == 0) variant = mi_type(g.type).mmv_variant;
+    mi_dispatch_type(g.type, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        if constexpr (mi_type(T).mmv_variant != 0) mi_mmv_launch<T>(g, variant, s);
+        else MI_ASSERT(!"no streaming GEMV for this weight type");
+    });
 }

@@ -172,7 +172,7 @@ struct FmtKQ {
     static constexpr bool KL = false;  // load() does not need K
     static constexpr int QKA = 256;  // activation block
     static constexpr int ITEM = 64;  // elements per item
-    static constexpr int BS = Q5 ? 176 : 144;
+    static constexpr int BS = mi_type(Q5 ? MI_TYPE_Q5_K : MI_TYPE_Q4_K).bytes;
     struct Regs {
         uint4 hdr, qa, qb;
         uint4 ha, hb;  // Q5 only
@@ -391,7 +391,7 @@ struct FmtQ0 {
     static constexpr bool KL = false;
     static constexpr int QKA = 32;
     static constexpr int ITEM = 32;
-    static constexpr int BS = Q8 ? 34 : 18;
+    static constexpr int BS = mi_type(Q8 ? MI_TYPE_Q8_0 : MI_TYPE_Q4_0).bytes;
     static constexpr int NQ = Q8 ? 8 : 4;  // quant dwords per block
     struct Regs {
         uint32_t w[NQ + 1];  // the dwords covering d and the quants
@@ -526,7 +526,7 @@ struct FmtQ0 {
     }
 };
 
-// Q4_1 (T = 3, 20 B: fp16 d, m, qs[16]), Q5_0 (6, 22 B: fp16 d, qh[4], qs[16]) and Q5_1 (7, 24 B:
+// Q4_1 (20 B: fp16 d, m, qs[16]), Q5_0 (22 B: fp16 d, qh[4], qs[16]) and Q5_1 (24 B:
 // fp16 d, m, qh[4], qs[16]) blocks of 32. Element j < 16 is the low nibble of qs[j], element j >= 16
 // the high nibble of qs[j - 16]; bit j of the little-endian qh is its fifth bit. Values q d + m
 // (Q4_1 / Q5_1, against Q8_1 activations: S1) resp. (q - 16) d (Q5_0, against Q8_0). Rows start
@@ -537,17 +537,18 @@ struct FmtQ1 {
     static constexpr bool KL = false;
     static constexpr int QKA = 32;
     static constexpr int ITEM = 32;
-    static constexpr bool HAS_M = T != 6, HAS_QH = T != 3;
+    static constexpr bool HAS_M = mi_type(T).has_m, HAS_QH = mi_type(T).has_qh;
+    static constexpr bool Q50 = T == MI_TYPE_Q5_0;  // no m: the block is only 2-byte aligned
     static constexpr bool S1 = HAS_M;  // the activations' 16-bit slot: fp16 s (Q8_1), else the integer sum
-    static constexpr int BS = T == 3 ? 20 : T == 6 ? 22 : 24;
-    static constexpr int NW = T == 3 ? 5 : 6;
+    static constexpr int BS = mi_type(T).bytes;
+    static constexpr int NW = HAS_QH ? 6 : 5;
     struct Regs {
         uint32_t w[NW];
         uint32_t off;  // Q5_0: byte offset of the block in w[0], 0 or 2
     };
     __device__ static __forceinline__ void load(Regs & r, const uint8_t * row, int item) {
         const uint32_t blk = (uint32_t) item * BS;
-        r.off = T == 6 ? blk & 2 : 0;
+        r.off = Q50 ? blk & 2 : 0;
         const uint32_t base = blk - r.off;
 #pragma unroll
         for (int i = 0; i < NW; i++) r.w[i] = *(const uint32_t *) (row + base + 4 * i);  // (Q5_0: 256 B tail slack)
@@ -559,7 +560,7 @@ struct FmtQ1 {
     };
     __device__ static __forceinline__ void unpack(const Regs & r, Blk & b) {
         uint32_t qs[4], qh = 0;
-        if constexpr (T == 6) {
+        if constexpr (Q50) {
             b.d = mi_h2f((uint16_t) ((r.off ? r.w[0] >> 16 : r.w[0]) & 0xFFFF));
             b.m = 0.0f;
             qh = r.off ? r.w[1] : __builtin_amdgcn_alignbyte(r.w[1], r.w[0], 2);
@@ -880,7 +881,7 @@ struct FmtQ6K {
     static constexpr bool KL = false;
     static constexpr int QKA = 256;
     static constexpr int ITEM = 64;
-    static constexpr int BS = 210;
+    static constexpr int BS = mi_type(MI_TYPE_Q6_K).bytes;
     struct Regs {
         uint32_t la[5], lb[5], hh[5];  // the dwords covering the two ql ranges and the qh range
         uint32_t sc[3];                // ... the eight scales of the 128-half

@@ -2,7 +2,7 @@
 // compiled as a translation unit of their own so that the formats build in parallel
 #include "mmv_fused_impl.h"
 
-void mi_mmv_launch_q40(const mi_mmv_group & g, int variant, hipStream_t s) {
+template <> void mi_mmv_launch<MI_TYPE_Q4_0>(const mi_mmv_group & g, int variant, hipStream_t s) {
     // tree order: pairs of blocks per item (variant % 10 == 1: single blocks), on the repacked
     // 16-byte-aligned copy when the backend handed one over (g.q0r)
     if (g.q0r) launch_stream_nc<FmtQ0R, false>(g, variant, s);

@@ -2,6 +2,6 @@
 // compiled as a translation unit of their own so that the formats build in parallel
 #include "mmv_fused_impl.h"
 
-void mi_mmv_launch_q4k(const mi_mmv_group & g, int variant, hipStream_t s) {
+template <> void mi_mmv_launch<MI_TYPE_Q4_K>(const mi_mmv_group & g, int variant, hipStream_t s) {
     launch_stream_ord<FmtKQ<false>>(g, variant, s);
 }

@@ -2,6 +2,6 @@
 // compiled as a translation unit of their own so that the formats build in parallel
 #include "mmv_fused_impl.h"
 
-void mi_mmv_launch_q50(const mi_mmv_group & g, int variant, hipStream_t s) {
-    launch_stream_ord<FmtQ1<6>>(g, variant, s);
+template <> void mi_mmv_launch<MI_TYPE_Q5_0>(const mi_mmv_group & g, int variant, hipStream_t s) {
+    launch_stream_ord<FmtQ1<MI_TYPE_Q5_0>>(g, variant, s);
 }

@@ -39,11 +39,11 @@ __device__ __forceinline__ size_t off4(const size_t * nb, int64_t i0, int64_t i1
 }
 
 __device__ __forceinline__ float ld_f(const char * p, int type) {
-    return type == 1 ? mi_h2f(*(const uint16_t *) p) : *(const float *) p;
+    return type == MI_TYPE_F16 ? mi_h2f(*(const uint16_t *) p) : *(const float *) p;
 }
 
 __device__ __forceinline__ void st_f(char * p, int type, float v) {
-    if (type == 1) *(uint16_t *) p = mi_f2h(v);
+    if (type == MI_TYPE_F16) *(uint16_t *) p = mi_f2h(v);
     else *(float *) p = v;
 }
 
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void k_cpy(mi_tensor_desc d, mi_tensor_desc a,
         unflatten(i, d.ne, j0, j1, j2, j3);
         const char * sp = a.data + off4(a.nb, i0, i1, i2, i3);
         char * dp = d.data + off4(d.nb, j0, j1, j2, j3);
-        if (a.type == d.type && a.type == 1) *(uint16_t *) dp = *(const uint16_t *) sp;
+        if (a.type == d.type && a.type == MI_TYPE_F16) *(uint16_t *) dp = *(const uint16_t *) sp;
         else st_f(dp, d.type, ld_f(sp, a.type));
     }
 }
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void k_cpy_multi(mi_cpy_batch b) {
         unflatten(i, d.ne, j0, j1, j2, j3);
         const char * sp = a.data + off4(a.nb, i0, i1, i2, i3);
         char * dp = d.data + off4(d.nb, j0, j1, j2, j3);
-        if (a.type == d.type && a.type == 1) *(uint16_t *) dp = *(const uint16_t *) sp;
+        if (a.type == d.type && a.type == MI_TYPE_F16) *(uint16_t *) dp = *(const uint16_t *) sp;
         else st_f(dp, d.type, ld_f(sp, a.type));
     }
 }
@@ -143,43 +143,43 @@ __global__ __launch_bounds__(256) void k_get_rows(mi_tensor_desc d, mi_tensor_de
 // fma(d * sc, q, -(dmin * m)) (:2181-2218, :2464-2507; the -mfma build emits vfmsub132ps there).
 template <int TYPE>
 __device__ __forceinline__ float dequant_elem(const uint8_t * row, int64_t c) {
-    if constexpr (TYPE == 2 || TYPE == 8) {  // Q4_0 (18 B) / Q8_0 (34 B) blocks of 32
-        constexpr int BS = TYPE == 2 ? 18 : 34;
+    constexpr mi_type_info I = mi_type(TYPE);
+    constexpr int BS = I.bytes;
+    if constexpr (TYPE == MI_TYPE_Q4_0 || TYPE == MI_TYPE_Q8_0) {  // Q4_0 (18 B) / Q8_0 (34 B) blocks of 32
         const uint8_t * blk = row + (c >> 5) * BS;
         const int j = (int) (c & 31);
         uint16_t dh;
         __builtin_memcpy(&dh, blk, 2);
         const float d = mi_h2f(dh);
-        if constexpr (TYPE == 2) {
+        if constexpr (TYPE == MI_TYPE_Q4_0) {
             const uint8_t b = blk[2 + (j & 15)];
-            return (float) ((j < 16 ? (b & 0x0F) : (b >> 4)) - 8) * d;
+            return (float) ((j < 16 ? (b & 0x0F) : (b >> 4)) - I.sub) * d;
         } else {
             return (float) (int8_t) blk[2 + j] * d;
         }
-    } else if constexpr (TYPE == 3 || TYPE == 6 || TYPE == 7) {
+    } else if constexpr (I.blck == 32) {
         // Q4_1 (20 B: fp16 d, m, qs[16]) / Q5_0 (22 B: fp16 d, qh[4], qs[16]) / Q5_1 (24 B: fp16 d, m,
         // qh[4], qs[16]) blocks of 32: dequantize_row_q4_1 / _q5_0 / _q5_1 (src/ggml-quants.c:1000-1072),
         // q * d + m resp. (q - 16) * d. The product of a 5-bit level and an fp16 scale is exact in f32,
         // so the reference build's contraction of q * d + m changes nothing. Q5_0 blocks are only
         // 2-byte aligned: bytes and 2-byte copies only.
-        constexpr int BS = TYPE == 3 ? 20 : TYPE == 6 ? 22 : 24;
-        constexpr int QH = TYPE == 6 ? 2 : 4, QS = TYPE == 3 ? 4 : QH + 4;
+        constexpr int QH = I.has_m ? 4 : 2, QS = I.has_qh ? QH + 4 : QH;
         const uint8_t * blk = row + (c >> 5) * BS;
         const int j = (int) (c & 31);
         uint16_t dh;
         __builtin_memcpy(&dh, blk, 2);
         const uint8_t b = blk[QS + (j & 15)];
         int q = j < 16 ? (b & 0x0F) : (b >> 4);
-        if constexpr (TYPE != 3) q |= ((blk[QH + (j >> 3)] >> (j & 7)) & 1) << 4;  // bit j of the little-endian qh
-        if constexpr (TYPE == 6) return (float) (q - 16) * mi_h2f(dh);
+        if constexpr (I.has_qh) q |= ((blk[QH + (j >> 3)] >> (j & 7)) & 1) << 4;  // bit j of the little-endian qh
+        if constexpr (!I.has_m) return (float) (q - I.sub) * mi_h2f(dh);
         else {
             uint16_t mh;
             __builtin_memcpy(&mh, blk + 2, 2);
             return add_rn(mul_rn((float) q, mi_h2f(dh)), mi_h2f(mh));
         }
-    } else if constexpr (TYPE == 14) {  // Q6_K (210 B) superblocks: ql[128] qh[64] int8 scales[16] fp16 d
+    } else if constexpr (TYPE == MI_TYPE_Q6_K) {  // Q6_K (210 B) superblocks: ql[128] qh[64] int8 scales[16] fp16 d
         // dequantize_row_q6_K (:2713-2758): d * sc * q, two separately rounded multiplies
-        const uint8_t * blk = row + (c >> 8) * 210;
+        const uint8_t * blk = row + (c >> 8) * BS;
         const int e = (int) (c & 255), h = e >> 7, t = (e >> 5) & 3, p = e & 31;
         uint16_t dh;
         __builtin_memcpy(&dh, blk + 208, 2);
@@ -188,8 +188,8 @@ __device__ __forceinline__ float dequant_elem(const uint8_t * row, int64_t c) {
         const int sc = (int8_t) blk[192 + (e >> 4)];
         return mul_rn(mul_rn(mi_h2f(dh), (float) sc), (float) q);
     } else {  // Q4_K (144 B) / Q5_K (176 B) superblocks of 256
-        constexpr bool Q5 = TYPE == 13;
-        const uint8_t * blk = row + (c >> 8) * (Q5 ? 176 : 144);
+        constexpr bool Q5 = TYPE == MI_TYPE_Q5_K;
+        const uint8_t * blk = row + (c >> 8) * BS;
         const int e = (int) (c & 255), g = e >> 6, l = e & 31, hi = (e >> 5) & 1;
         uint16_t dh, mh;
         __builtin_memcpy(&dh, blk, 2);
@@ -224,11 +224,11 @@ __global__ __launch_bounds__(256) void k_get_rows_q(mi_tensor_desc d, mi_tensor_
 // get_rows(a, ia) + get_rows(b, ib) in one pass (the GPT-2 token + position embedding,
 // main-backend.cpp:475-478): each element is read exactly as k_get_rows / k_get_rows_q read it
 // and the two f32 values are added once, as the ADD node does. 1-D index vectors, f32 dst rows.
-template <int T>  // 0: f32 / f16 (ld_f), else the quantized type
+template <int T>  // the table's type
 __device__ __forceinline__ float emb_elem(const mi_tensor_desc & a, int32_t r, int64_t c) {
     // (f32 / f16 resolved at compile time: a runtime type select put the loads under a branch)
-    if constexpr (T == 0) return *(const float *) (a.data + c * a.nb[0] + (size_t) r * a.nb[1]);
-    else if constexpr (T == 1) return mi_h2f(*(const uint16_t *) (a.data + c * a.nb[0] + (size_t) r * a.nb[1]));
+    if constexpr (T == MI_TYPE_F32) return *(const float *) (a.data + c * a.nb[0] + (size_t) r * a.nb[1]);
+    else if constexpr (T == MI_TYPE_F16) return mi_h2f(*(const uint16_t *) (a.data + c * a.nb[0] + (size_t) r * a.nb[1]));
     else return dequant_elem<T>((const uint8_t *) a.data + (size_t) r * a.nb[1], c);
 }
 
@@ -492,23 +492,15 @@ void mi_op_cpy(const mi_tensor_desc & d, const mi_tensor_desc & a, hipStream_t s
 
 void mi_op_get_rows(const mi_tensor_desc & d, const mi_tensor_desc & a, const mi_tensor_desc & idx, hipStream_t s) {
     const int64_t n = d.ne[0] * d.ne[1] * d.ne[2] * d.ne[3];
-    switch (a.type) {
-        case 2: hipLaunchKernelGGL(k_get_rows_q<2>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
-        case 8: hipLaunchKernelGGL(k_get_rows_q<8>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
-        case 3: hipLaunchKernelGGL(k_get_rows_q<3>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
-        case 6: hipLaunchKernelGGL(k_get_rows_q<6>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
-        case 7: hipLaunchKernelGGL(k_get_rows_q<7>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
-        case 12: hipLaunchKernelGGL(k_get_rows_q<12>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
-        case 13: hipLaunchKernelGGL(k_get_rows_q<13>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
-        case 14: hipLaunchKernelGGL(k_get_rows_q<14>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
-        default: hipLaunchKernelGGL(k_get_rows, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n); break;
-    }
+    mi_dispatch_type(a.type, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        if constexpr (mi_type_quantized(T)) hipLaunchKernelGGL(k_get_rows_q<T>, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n);
+        else hipLaunchKernelGGL(k_get_rows, dim3(grid_for(n)), dim3(256), 0, s, d, a, idx, n);
+    });
 }
 
-template <int TA>
-static void launch_get_rows_add(const mi_tensor_desc & d, const mi_tensor_desc & a, const mi_tensor_desc & ia, const mi_tensor_desc & b,
-                                const mi_tensor_desc & ib, int64_t n, hipStream_t s) {
-    (void) n;
+void mi_op_get_rows_add(const mi_tensor_desc & d, const mi_tensor_desc & a, const mi_tensor_desc & ia, const mi_tensor_desc & b,
+                        const mi_tensor_desc & ib, hipStream_t s) {
     if (d.ne[0] >= ((int64_t) 1 << 31)) abort();  // row length indexed with 32 bits (never an embedding)
     const int ne0 = (int) d.ne[0];
     // grid.y is at most 65535 rows: longer index vectors in chunks (descriptors advanced by rows)
@@ -520,35 +512,11 @@ static void launch_get_rows_add(const mi_tensor_desc & d, const mi_tensor_desc &
         ibc.data += r0 * ib.nb[0];
         dc.ne[1] = nr;
         const dim3 g((unsigned) std::min<int64_t>((ne0 + 1023) / 1024, 64), (unsigned) nr);
-        switch (b.type) {
-            case 2: hipLaunchKernelGGL((k_get_rows_add<TA, 2>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0); break;
-            case 8: hipLaunchKernelGGL((k_get_rows_add<TA, 8>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0); break;
-            case 3: hipLaunchKernelGGL((k_get_rows_add<TA, 3>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0); break;
-            case 6: hipLaunchKernelGGL((k_get_rows_add<TA, 6>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0); break;
-            case 7: hipLaunchKernelGGL((k_get_rows_add<TA, 7>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0); break;
-            case 12: hipLaunchKernelGGL((k_get_rows_add<TA, 12>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0); break;
-            case 13: hipLaunchKernelGGL((k_get_rows_add<TA, 13>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0); break;
-            case 14: hipLaunchKernelGGL((k_get_rows_add<TA, 14>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0); break;
-            case 1: hipLaunchKernelGGL((k_get_rows_add<TA, 1>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0); break;
-            default: hipLaunchKernelGGL((k_get_rows_add<TA, 0>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0); break;
-        }
-    }
-}
-
-void mi_op_get_rows_add(const mi_tensor_desc & d, const mi_tensor_desc & a, const mi_tensor_desc & ia, const mi_tensor_desc & b,
-                        const mi_tensor_desc & ib, hipStream_t s) {
-    const int64_t n = d.ne[0] * d.ne[1];
-    switch (a.type) {
-        case 2: launch_get_rows_add<2>(d, a, ia, b, ib, n, s); break;
-        case 8: launch_get_rows_add<8>(d, a, ia, b, ib, n, s); break;
-        case 3: launch_get_rows_add<3>(d, a, ia, b, ib, n, s); break;
-        case 6: launch_get_rows_add<6>(d, a, ia, b, ib, n, s); break;
-        case 7: launch_get_rows_add<7>(d, a, ia, b, ib, n, s); break;
-        case 12: launch_get_rows_add<12>(d, a, ia, b, ib, n, s); break;
-        case 13: launch_get_rows_add<13>(d, a, ia, b, ib, n, s); break;
-        case 14: launch_get_rows_add<14>(d, a, ia, b, ib, n, s); break;
-        case 1: launch_get_rows_add<1>(d, a, ia, b, ib, n, s); break;
-        default: launch_get_rows_add<0>(d, a, ia, b, ib, n, s); break;
+        mi_dispatch_type(a.type, [&](auto ta) {
+            mi_dispatch_type(b.type, [&](auto tb) {
+                hipLaunchKernelGGL((k_get_rows_add<decltype(ta)::value, decltype(tb)::value>), g, dim3(256), 0, s, dc, a, iac, b, ibc, ne0);
+            });
+        });
     }
 }
 

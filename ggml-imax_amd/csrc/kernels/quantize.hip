@@ -32,14 +32,14 @@ static __device__ __forceinline__ int64_t xh_index(int64_t c, int64_t k, int64_t
     return nblk ? ((k >> 4) * nblk + c) * 16 + (k & 15) : c * K + k;
 }
 
-size_t mi_act_q8_bytes(int64_t K, int64_t ncols, bool is_q8K, bool is_q8_1) {
+size_t mi_act_q8_bytes(int64_t K, int64_t ncols, mi_act_quant q) {
     const size_t qs = (size_t) (K * ncols + 255) & ~(size_t) 255;
-    const size_t d = ((size_t) (K / (is_q8K ? 256 : 32)) * ncols * sizeof(float) + 255) & ~(size_t) 255;
-    const size_t s = is_q8K || is_q8_1 ? (((size_t) (K / 32) * ncols * sizeof(int16_t) + 255) & ~(size_t) 255) : 0;
+    const size_t d = ((size_t) (K / mi_act_block(q)) * ncols * sizeof(float) + 255) & ~(size_t) 255;
+    const size_t s = q != MI_ACT_Q8_0 ? (((size_t) (K / 32) * ncols * sizeof(int16_t) + 255) & ~(size_t) 255) : 0;
     return qs + d + s;
 }
 
-mi_act_q8 mi_act_q8_carve(void * base, int64_t K, int64_t ncols, bool is_q8K, bool is_q8_1) {
+mi_act_q8 mi_act_q8_carve(void * base, int64_t K, int64_t ncols, mi_act_quant q) {
     char * p = (char *) base;
     mi_act_q8 a;
     a.K = K;
@@ -47,8 +47,8 @@ mi_act_q8 mi_act_q8_carve(void * base, int64_t K, int64_t ncols, bool is_q8K, bo
     a.qs = (int8_t *) p;
     p += ((size_t) (K * ncols) + 255) & ~(size_t) 255;
     a.d = (float *) p;
-    p += ((size_t) (K / (is_q8K ? 256 : 32)) * ncols * sizeof(float) + 255) & ~(size_t) 255;
-    a.s32 = is_q8K || is_q8_1 ? (int16_t *) p : nullptr;
+    p += ((size_t) (K / mi_act_block(q)) * ncols * sizeof(float) + 255) & ~(size_t) 255;
+    a.s32 = q != MI_ACT_Q8_0 ? (int16_t *) p : nullptr;
     return a;
 }
 
@@ -189,11 +189,11 @@ void mi_quantize_q8_K(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, h
                        nullptr);
 }
 
-void mi_quantize_expand_f16(const mi_src_cols & x, int64_t K, int64_t ncols, bool is_q8K, uint16_t * xh, hipStream_t s,
+void mi_quantize_expand_f16(const mi_src_cols & x, int64_t K, int64_t ncols, mi_act_quant q, uint16_t * xh, hipStream_t s,
                             bool blocked) {
     const int64_t xb = blocked ? ncols : 0;
     if (ncols == 0 || K < 32) return;
-    if (is_q8K) {
+    if (q == MI_ACT_Q8_K) {
         hipLaunchKernelGGL(k_quantize_q8_K<true>, dim3((unsigned) ncols, (unsigned) ((K / 256 + 3) / 4)), dim3(256), 0, s, x, K,
                            mi_act_q8{}, xh, xb);
     } else {
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256) void k_quantize_rows_q8_K(mi_src_cols x, int64
     float d;
     mi_q8K_superblock(v, lane, packed, sum32, d);
     (void) sum32;
-    char * blk = (char *) col_base(dl, c) + (size_t) b * 292;
+    char * blk = (char *) col_base(dl, c) + (size_t) b * mi_act_block_bytes(MI_ACT_Q8_K);
     int s = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) s += (int) (int8_t) (packed >> (8 * i));
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void k_quantize_rows_q8_0(mi_src_cols x, int64
     const float d = amax / 127.f;
     const float id = amax != 0.0f ? 127.f / amax : 0.0f;
     const float q = __builtin_rintf(__fmul_rn(v, id));
-    char * blk = (char *) col_base(dl, c) + (size_t) b * (S1 ? 36 : 34);
+    char * blk = (char *) col_base(dl, c) + (size_t) b * mi_act_block_bytes(S1 ? MI_ACT_Q8_1 : MI_ACT_Q8_0);
     blk[(S1 ? 4 : 2) + l] = (char) (int8_t) (int) q;
     if (l == 0) *(uint16_t *) blk = mi_f2h(d);
     if constexpr (S1) {
@@ -289,16 +289,16 @@ __global__ __launch_bounds__(256) void k_quantize_rows_q8_0(mi_src_cols x, int64
     }
 }
 
-void mi_quantize_rows_q8(const mi_src_cols & x, int64_t K, bool is_q8K, const mi_src_cols & dst, hipStream_t s, bool is_q8_1) {
+void mi_quantize_rows_q8(const mi_src_cols & x, int64_t K, mi_act_quant q, const mi_src_cols & dst, hipStream_t s) {
     const int64_t ncols = x.ne1 * x.ne2 * x.ne3;
     if (ncols == 0) return;
-    if (is_q8K) {
+    if (q == MI_ACT_Q8_K) {
         const bool a16 = (((uintptr_t) x.base) | x.nb1 | x.nb2 | x.nb3) % 16 == 0;
         const dim3 grid((unsigned) ncols, (unsigned) ((K / 256 + 3) / 4));
         if (a16) hipLaunchKernelGGL(k_quantize_rows_q8_K<true>, grid, dim3(256), 0, s, x, K, dst);
         else hipLaunchKernelGGL(k_quantize_rows_q8_K<false>, grid, dim3(256), 0, s, x, K, dst);
     }
-    else if (is_q8_1) hipLaunchKernelGGL(k_quantize_rows_q8_0<true>, dim3((unsigned) ncols, (unsigned) ((K / 32 + 7) / 8)), dim3(256), 0, s, x, K, dst);
+    else if (q == MI_ACT_Q8_1) hipLaunchKernelGGL(k_quantize_rows_q8_0<true>, dim3((unsigned) ncols, (unsigned) ((K / 32 + 7) / 8)), dim3(256), 0, s, x, K, dst);
     else hipLaunchKernelGGL(k_quantize_rows_q8_0<false>, dim3((unsigned) ncols, (unsigned) ((K / 32 + 7) / 8)), dim3(256), 0, s, x, K, dst);
 }
 
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(256) void k_q8K_rows_to_act(mi_src_cols xs, int64_t
     const int64_t b = (int64_t) blockIdx.y * 4 + wave;
     if (b >= K / 256) return;
     const uint32_t c = blockIdx.x;
-    const char * blk = col_base(xs, c) + (size_t) b * 292;
+    const char * blk = col_base(xs, c) + (size_t) b * mi_act_block_bytes(MI_ACT_Q8_K);
     const uint32_t packed = *(const uint32_t *) (blk + 4 + lane * 4);
     const float d = *(const float *) blk;
     int s = 0;
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(256) void k_q8_0_rows_to_act(mi_src_cols xs, int64_
     const int l = threadIdx.x & 31;
     if (b >= K / 32) return;
     const uint32_t c = blockIdx.x;
-    const char * blk = col_base(xs, c) + (size_t) b * (S1 ? 36 : 34);
+    const char * blk = col_base(xs, c) + (size_t) b * mi_act_block_bytes(S1 ? MI_ACT_Q8_1 : MI_ACT_Q8_0);
     const int8_t q = (int8_t) blk[(S1 ? 4 : 2) + l];
     const float d = mi_h2f(*(const uint16_t *) blk);
     if constexpr (MMX) {
@@ -360,19 +360,18 @@ __global__ __launch_bounds__(256) void k_q8_0_rows_to_act(mi_src_cols xs, int64_
     }
 }
 
-void mi_q8_rows_to_act(const mi_src_cols & xs, int64_t K, bool is_q8K, const mi_act_q8 * act, const mi_act_mmx * mx, hipStream_t s,
-                       bool is_q8_1) {
+void mi_q8_rows_to_act(const mi_src_cols & xs, int64_t K, mi_act_quant q, const mi_act_q8 * act, const mi_act_mmx * mx, hipStream_t s) {
     const int64_t ncols = xs.ne1 * xs.ne2 * xs.ne3;
     if (ncols == 0) return;
     const mi_act_q8 a = act ? *act : mi_act_q8{};
     const mi_act_mmx m = mx ? *mx : mi_act_mmx{};
-    if (is_q8K) {
+    if (q == MI_ACT_Q8_K) {
         const dim3 grid((unsigned) ncols, (unsigned) ((K / 256 + 3) / 4));
         if (mx) hipLaunchKernelGGL(k_q8K_rows_to_act<true>, grid, dim3(256), 0, s, xs, K, a, m);
         else hipLaunchKernelGGL(k_q8K_rows_to_act<false>, grid, dim3(256), 0, s, xs, K, a, m);
     } else {
         const dim3 grid((unsigned) ncols, (unsigned) ((K / 32 + 7) / 8));
-        if (is_q8_1) hipLaunchKernelGGL((k_q8_0_rows_to_act<false, true>), grid, dim3(256), 0, s, xs, K, a, m);  // (GEMV layout only)
+        if (q == MI_ACT_Q8_1) hipLaunchKernelGGL((k_q8_0_rows_to_act<false, true>), grid, dim3(256), 0, s, xs, K, a, m);  // (GEMV layout only)
         else if (mx) hipLaunchKernelGGL(k_q8_0_rows_to_act<true>, grid, dim3(256), 0, s, xs, K, a, m);
         else hipLaunchKernelGGL(k_q8_0_rows_to_act<false>, grid, dim3(256), 0, s, xs, K, a, m);
     }

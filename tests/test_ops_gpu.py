@@ -148,15 +148,62 @@ def test_silu_exact(libs):
     assert_exact(a, b, "silu")
 
 
-@pytest.mark.parametrize("src_type", [F16, F32])
+def host_quantize(libs, qtype, w, K):
+    """Rows of `qtype`: the oracle's quantizer where it has the type, else the runtime's ggml_quantize_chunk
+    (tests/test_legacy_quants.py and tests/test_q6k.py pin it to the reference's bytes)."""
+    import pyoracle as orc
+    if qtype in orc.TYPE_NAMES:
+        return orc.quantize(qtype, w, K)
+    rt = libs[0]
+    w = np.ascontiguousarray(w, np.float32)
+    out = np.empty(G.row_size(qtype, K) * (w.size // K), np.uint8)
+    assert rt.ggml_quantize_chunk(qtype, w.ctypes.data, out.ctypes.data, 0, w.size // K, K, None) == out.nbytes
+    return out
+
+
+def host_dequantize(libs, qtype, wq, n):
+    """dequantize_row_* on the host: the oracle's where it has the type, else the reference library's own
+    to_float (ggml_internal_get_type_traits)."""
+    import ctypes
+    import pyoracle as orc
+    if qtype in orc.TYPE_NAMES:
+        return orc.dequantize(qtype, wq, n)
+
+    class Traits(ctypes.Structure):
+        _fields_ = [("type_name", ctypes.c_char_p), ("blck_size", ctypes.c_int), ("type_size", ctypes.c_size_t),
+                    ("is_quantized", ctypes.c_bool), ("to_float", ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64)),
+                    ("from_float", ctypes.c_void_p), ("from_float_reference", ctypes.c_void_p), ("vec_dot", ctypes.c_void_p),
+                    ("vec_dot_type", ctypes.c_int), ("nrows", ctypes.c_int64)]
+
+    f = libs[2].handles[0].ggml_internal_get_type_traits
+    f.restype = Traits
+    f.argtypes = [ctypes.c_int]
+    wq = np.ascontiguousarray(wq)
+    out = np.empty(n, np.float32)
+    f(qtype).to_float(wq.ctypes.data, out.ctypes.data, n)
+    return out
+
+
+@pytest.mark.parametrize("src_type", [F16, F32, G.GGML_TYPE_Q5_1, G.GGML_TYPE_Q6_K])
 def test_get_rows_plus_add_exact(libs, src_type):
-    """get_rows(wte f16) + get_rows(wpe f32) as the GPT-2 embedding (main-backend.cpp:475-478)."""
-    E, V, N = 768, 997, 9
-    w = rnd(6, E * V, 0.1)
-    wv = w.astype(np.float16) if src_type == F16 else w
-    p = rnd(7, E * 64, 0.1)
-    ids = np.array([5, 996, 0, 17, 17, 300, 2, 9, 500], dtype=np.int32)
-    pos = np.arange(N, dtype=np.int32) + 3
+    """get_rows(wte f16) + get_rows(wpe f32) as the GPT-2 embedding (main-backend.cpp:475-478).
+    With a quantized first table (a 32-element type with a fifth-bit plane, a K-quant: the fused
+    launch is instantiated for every pair of table types) the one fused launch must give the bits of
+    the unfused nodes on the same backend -- each get_rows and the add as a graph of its own. Those
+    rows are 512 wide, which crosses a block boundary of either type, and one index repeats."""
+    if src_type in (F16, F32):
+        E, V, N = 768, 997, 9
+        w = rnd(6, E * V, 0.1)
+        wv = w.astype(np.float16) if src_type == F16 else w
+        p = rnd(7, E * 64, 0.1)
+        ids = np.array([5, 996, 0, 17, 17, 300, 2, 9, 500], dtype=np.int32)
+        pos = np.arange(N, dtype=np.int32) + 3
+    else:
+        E, V, N = 512, 7, 3
+        wv = host_quantize(libs, src_type, rnd(26, E * V, 0.1), E)
+        p = rnd(27, E * 64, 0.1)
+        ids = np.array([6, 2, 6], dtype=np.int32)
+        pos = np.array([1, 0, 5], dtype=np.int32)
 
     def build(L, c):
         wt = L.ggml_new_tensor_2d(c, src_type, E, V)
@@ -166,17 +213,40 @@ def test_get_rows_plus_add_exact(libs, src_type):
         out = L.ggml_add(c, L.ggml_get_rows(c, wt, it), L.ggml_get_rows(c, pt, qt))
         return [(wt, wv), (pt, p), (it, ids), (qt, pos)], out
 
-    a, b = both(libs, build)
-    assert_exact(a, b, "get_rows+add")
+    if src_type in (F16, F32):
+        a, b = both(libs, build)
+        assert_exact(a, b, "get_rows+add")
+        return
+
+    rt, be, _, _ = libs
+    a = G.graph_once(rt, be, lambda c: build(rt, c))
+    assert rt.ggml_backend_mi355x_last_launch_count(be) == 1  # the fused launch
+
+    def rows_of(ttype, nrows, data, idx):
+        def build_rows(c):
+            t = rt.ggml_new_tensor_2d(c, ttype, E, nrows)
+            i = rt.ggml_new_tensor_1d(c, I32, N)
+            return [(t, data), (i, idx)], rt.ggml_get_rows(c, t, i)
+        return G.graph_once(rt, be, build_rows)
+
+    ra, rb = rows_of(src_type, V, wv, ids), rows_of(F32, 64, p, pos)
+
+    def build_add(c):
+        x = rt.ggml_new_tensor_2d(c, F32, E, N)
+        y = rt.ggml_new_tensor_2d(c, F32, E, N)
+        return [(x, ra), (y, rb)], rt.ggml_add(c, x, y)
+
+    b = G.graph_once(rt, be, build_add)
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-@pytest.mark.parametrize("qtype", [G.GGML_TYPE_Q4_0, G.GGML_TYPE_Q8_0, G.GGML_TYPE_Q4_K, G.GGML_TYPE_Q5_K])
+@pytest.mark.parametrize("qtype", [G.GGML_TYPE_Q4_0, G.GGML_TYPE_Q8_0, G.GGML_TYPE_Q4_K, G.GGML_TYPE_Q5_K,
+                                   G.GGML_TYPE_Q4_1, G.GGML_TYPE_Q5_0, G.GGML_TYPE_Q5_1, G.GGML_TYPE_Q6_K])
 def test_get_rows_quantized_exact(libs, qtype):
     """get_rows of a quantized wte (a quantized GPT-2's embedding, ggml.c:12874-12918 dequantizes the
     picked rows with the type's to_float) + get_rows(wpe f32): identical bits."""
-    import pyoracle as orc
     E, V, N = 768, 997, 9
-    wq = orc.quantize(qtype, rnd(16, E * V, 0.1), E)
+    wq = host_quantize(libs, qtype, rnd(16, E * V, 0.1), E)
     p = rnd(7, E * 64, 0.1)
     ids = np.array([5, 996, 0, 17, 17, 300, 2, 9, 500], dtype=np.int32)
     pos = np.arange(N, dtype=np.int32) + 3
@@ -200,7 +270,7 @@ def test_get_rows_quantized_exact(libs, qtype):
         return [(wt, wq), (it, ids)], rt.ggml_get_rows(c, wt, it)
 
     rows = G.graph_once(rt, be, build_rows).reshape(N, E)
-    deq = orc.dequantize(qtype, wq, E * V).reshape(V, E)[ids]
+    deq = host_dequantize(libs, qtype, wq, E * V).reshape(V, E)[ids]
     assert np.array_equal(rows.view(np.uint32), deq.view(np.uint32))
 
 
