@@ -547,6 +547,8 @@ static mi_act_quant q8_quant_of(ggml_type t) {
     return MI_ACT_NONE;
 }
 
+static float op_param_f(const ggml_tensor * t, int i);
+
 static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
     const ggml_tensor * a = op->src[0];
     const ggml_tensor * b = op->src[1];
@@ -574,6 +576,22 @@ static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
             if (!mm_src0_supported(a->type) || is_split_tensor(a)) return false;
             if (a->nb[0] != ggml_type_size(a->type) || b->nb[0] != ggml_type_size(b->type)) return false;
             return b->type == GGML_TYPE_F32 && ids && ids->type == GGML_TYPE_I32;
+        }
+        case GGML_OP_FLASH_ATTN_EXT: {
+            // F32 q, an F16 K/V cache (any row / head / batch strides) of a head size the kernels are
+            // built for, heads that divide, a contiguous F16 mask padded as the builder asks, or none
+            const ggml_tensor * v = op->src[2];
+            const ggml_tensor * mask = op->src[3];
+            if (!is_f32(a) || a->nb[0] != sizeof(float) || !is_f32(op) || !ggml_is_contiguous(op)) return false;
+            if (!b || !v || b->type != GGML_TYPE_F16 || v->type != GGML_TYPE_F16 || b->nb[0] != 2 || v->nb[0] != 2) return false;
+            if (!mi_fa_head_size_ok(b->ne[0]) || a->ne[0] != b->ne[0] || v->ne[0] != b->ne[0] || v->ne[1] != b->ne[1]) return false;
+            if (b->ne[1] < 1 || a->ne[1] < 1) return false;
+            if (a->ne[2] % b->ne[2] != 0 || a->ne[2] % v->ne[2] != 0 || a->ne[3] % b->ne[3] != 0 || a->ne[3] % v->ne[3] != 0) return false;
+            if (mask && (mask->type != GGML_TYPE_F16 || !ggml_is_contiguous(mask) || mask->ne[0] < b->ne[1] ||
+                         mask->ne[1] < GGML_PAD(a->ne[1], GGML_KQ_MASK_PAD)))
+                return false;
+            if (op_param_f(op, 1) > 0.0f && !mask) return false;
+            return !is_split_tensor(a) && !is_split_tensor(b) && !is_split_tensor(v) && !(mask && is_split_tensor(mask));
         }
         case GGML_OP_ADD:
         case GGML_OP_SUB:
@@ -1377,6 +1395,55 @@ static void op_companion(mi_backend_ctx * ctx, ggml_tensor * node) {
     ctx->last_launches++;
 }
 
+// GGML_OP_FLASH_ATTN_EXT (flash_attn.hip): reads src[0..3] where they lie -- no converted copy of any
+// of them is made or cached -- and writes dst; the partials of a split KV range come from the graph's
+// scratch (graph_scratch_bytes), a region of its own per node
+static mi_fa_desc fa_desc(const ggml_tensor * node) {
+    const ggml_tensor * q = node->src[0];
+    const ggml_tensor * k = node->src[1];
+    const ggml_tensor * v = node->src[2];
+    const ggml_tensor * mask = node->src[3];
+    mi_fa_desc d = {};
+    d.q = (const char *) q->data;
+    d.k = (const char *) k->data;
+    d.v = (const char *) v->data;
+    d.mask = mask ? (const char *) mask->data : nullptr;
+    d.dst = (float *) node->data;
+    d.D = (int) q->ne[0];
+    d.N = (int) q->ne[1];
+    d.nh = (int) q->ne[2];
+    d.ne3 = (int) q->ne[3];
+    d.kv = (int) k->ne[1];
+    d.nh_k = (int) k->ne[2];
+    d.nh_v = (int) v->ne[2];
+    d.ne3_k = (int) k->ne[3];
+    d.ne3_v = (int) v->ne[3];
+    d.nbq1 = q->nb[1]; d.nbq2 = q->nb[2]; d.nbq3 = q->nb[3];
+    d.nbk1 = k->nb[1]; d.nbk2 = k->nb[2]; d.nbk3 = k->nb[3];
+    d.nbv1 = v->nb[1]; d.nbv2 = v->nb[2]; d.nbv3 = v->nb[3];
+    d.nbm1 = mask ? mask->nb[1] : 0;
+    d.scale = op_param_f(node, 0);
+    d.max_bias = op_param_f(node, 1);
+    return d;
+}
+
+static void op_flash_attn_ext(mi_backend_ctx * ctx, ggml_tensor * node) {
+    const ggml_tensor * q = node->src[0];
+    const ggml_tensor * k = node->src[1];
+    const ggml_tensor * v = node->src[2];
+    const ggml_tensor * mask = node->src[3];
+    MI_ASSERT(q->type == GGML_TYPE_F32 && q->nb[0] == sizeof(float) && k->type == GGML_TYPE_F16 && v->type == GGML_TYPE_F16);
+    MI_ASSERT(k->nb[0] == 2 && v->nb[0] == 2 && mi_fa_head_size_ok(k->ne[0]) && q->ne[0] == k->ne[0] && v->ne[0] == k->ne[0]);
+    MI_ASSERT(v->ne[1] == k->ne[1] && q->ne[2] % k->ne[2] == 0 && q->ne[2] % v->ne[2] == 0 && q->ne[3] % k->ne[3] == 0 && q->ne[3] % v->ne[3] == 0);
+    MI_ASSERT(!mask || (mask->type == GGML_TYPE_F16 && ggml_is_contiguous(mask) && mask->ne[0] >= k->ne[1] && mask->ne[1] >= q->ne[1]));
+    MI_ASSERT(node->type == GGML_TYPE_F32 && ggml_is_contiguous(node));
+    // op_params[2], the precision: GGML_PREC_DEFAULT and GGML_PREC_F32 run the same f32-accumulating kernels
+    mi_fa_desc d = fa_desc(node);
+    const size_t part = mi_fa_part_bytes(d);
+    if (part) d.part = (float *) scratch_take(ctx, part);
+    ctx->last_launches += mi_flash_attn_ext(d, ctx->stream);
+}
+
 // ---------------------------------------------------------------------------------------------
 // graph execution
 // ---------------------------------------------------------------------------------------------
@@ -1396,6 +1463,11 @@ static size_t graph_scratch_bytes(const ggml_cgraph * cgraph) {
             const mi_act_format f = act_format_of(n->src[0]->type);
             if (f.quant != MI_ACT_NONE) total += (act_bytes(f, b->ne[0], b->ne[1] * b->ne[2] * b->ne[3]) + kBufferAlign - 1) & ~(kBufferAlign - 1);
             if (n->src[2]) total += mmid_tables_bytes(n->src[0]->ne[2], n->src[2]->ne[0] * n->src[2]->ne[1]);
+            continue;
+        }
+        if (n->op == GGML_OP_FLASH_ATTN_EXT) {
+            // the partials of a split KV range, per node: two nodes never share a live region
+            total += (mi_fa_part_bytes(fa_desc(n)) + kBufferAlign - 1) & ~(kBufferAlign - 1);
             continue;
         }
         if (n->op != GGML_OP_MUL_MAT) continue;
@@ -2949,6 +3021,10 @@ static enum ggml_status mi_graph_launch_nodes(mi_backend_ctx * ctx, ggml_cgraph 
             case GGML_OP_MUL_MAT_ID:
                 // always its own launch(es): no fusion pass absorbs it or takes it as producer / consumer
                 op_mul_mat_id(ctx, node);
+                break;
+            case GGML_OP_FLASH_ATTN_EXT:
+                // its own launch(es) as well; reads src[0..3] in place, writes dst (invalidated below)
+                op_flash_attn_ext(ctx, node);
                 break;
             default:
                 op_companion(ctx, node);

@@ -522,6 +522,38 @@ void ggml_mul_mat_set_prec(struct ggml_tensor * a, enum ggml_prec prec) {
     set_op_params(a, &p, sizeof(p));
 }
 
+// src/ggml.c:6494-6539 ggml_flash_attn_ext: q f32 [D, N, nh], k/v f16 [D, kv, nh_kv], mask f16
+// [>= kv, >= PAD(N, GGML_KQ_MASK_PAD)] or NULL -> dst f32 [D, nh, N, ne3] (the permute(0,2,1,3) of the
+// attention output); op_params = {scale, max_bias, prec}
+struct ggml_tensor * ggml_flash_attn_ext(struct ggml_context * ctx, struct ggml_tensor * q, struct ggml_tensor * k,
+                                         struct ggml_tensor * v, struct ggml_tensor * mask, float scale, float max_bias) {
+    // ggml_can_mul_mat(k, q)
+    GGML_ASSERT(k->ne[0] == q->ne[0] && q->ne[2] % k->ne[2] == 0 && q->ne[3] % k->ne[3] == 0);
+    if (mask) {
+        GGML_ASSERT(ggml_is_contiguous(mask));
+        GGML_ASSERT(mask->ne[2] == 1);
+        GGML_ASSERT(mask->ne[3] == 1);
+        GGML_ASSERT(mask->ne[1] >= GGML_PAD(q->ne[1], GGML_KQ_MASK_PAD));
+    }
+    if (max_bias > 0.0f) GGML_ASSERT(mask);
+    const int64_t ne[4] = {q->ne[0], q->ne[2], q->ne[1], q->ne[3]};
+    ggml_tensor * r = ggml_new_tensor(ctx, GGML_TYPE_F32, 4, ne);
+    const float params[2] = {scale, max_bias};
+    set_op_params(r, params, sizeof(params));
+    r->op = GGML_OP_FLASH_ATTN_EXT;
+    r->src[0] = q;
+    r->src[1] = k;
+    r->src[2] = v;
+    r->src[3] = mask;
+    return r;
+}
+
+// src/ggml.c:6541-6549: the precision sits after scale and max_bias
+void ggml_flash_attn_ext_set_prec(struct ggml_tensor * a, enum ggml_prec prec) {
+    GGML_ASSERT(a->op == GGML_OP_FLASH_ATTN_EXT);
+    a->op_params[2] = (int32_t) prec;
+}
+
 static ggml_tensor * unary_like(ggml_context * ctx, ggml_tensor * a, ggml_op op, bool inplace) {
     ggml_tensor * r = inplace ? ggml_view_tensor(ctx, a) : ggml_dup_tensor(ctx, a);
     r->op = op;

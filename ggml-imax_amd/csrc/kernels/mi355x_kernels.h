@@ -366,6 +366,28 @@ struct mi_router_desc {
 };
 void mi_router_fused(const mi_router_desc & r, const uint16_t * exp_table, hipStream_t s);
 
+// ---- GGML_OP_FLASH_ATTN_EXT (flash_attn.hip; src/ggml.c:15572-15751) ----
+// q f32 [D, N, nh, ne3] (nb0 == 4), k / v f16 [D, kv, nh_k / nh_v, ne3_k / ne3_v] (nb0 == 2), mask f16
+// rows of nbm1 bytes or null, dst f32 [D, nh, N, ne3] contiguous.
+struct mi_fa_desc {
+    const char * q;
+    const char * k;
+    const char * v;
+    const char * mask;
+    float * dst;
+    float * part;  // split partials, mi_fa_part_bytes (null when mi_fa_splits == 1)
+    int D, N, nh, ne3, kv;
+    int nh_k, nh_v, ne3_k, ne3_v;
+    size_t nbq1, nbq2, nbq3, nbk1, nbk2, nbk3, nbv1, nbv2, nbv3, nbm1;
+    float scale, max_bias;
+};
+bool mi_fa_head_size_ok(int64_t D);
+// the number of workgroups the KV range is split over: a pure function of the shape
+int mi_fa_splits(const mi_fa_desc & d);
+size_t mi_fa_part_bytes(const mi_fa_desc & d);
+// one launch, or the split kernel and its combine; returns the number of launches
+int mi_flash_attn_ext(const mi_fa_desc & d, hipStream_t s);
+
 // Decode-regime F16 mul_mat (2-D weights, few f32 src1 columns of contiguous K) that converts the
 // activations itself and applies the graph's following bias add / residual add / GELU.
 struct mi_f16_epilogue {

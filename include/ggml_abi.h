@@ -46,6 +46,7 @@ extern "C" {
 
 #define GGML_UNUSED(x) (void)(x)
 #define GGML_PAD(x, n) (((x) + (n) - 1) & ~((n) - 1))
+#define GGML_KQ_MASK_PAD 32  // rows of a flash-attention mask are padded to this (include/ggml/ggml.h:1743)
 
 GGML_API void ggml_print_backtrace(void);
 
@@ -311,6 +312,9 @@ GGML_API struct ggml_tensor * ggml_mul_mat(struct ggml_context * ctx, struct ggm
 GGML_API struct ggml_tensor * ggml_mul_mat_id(struct ggml_context * ctx, struct ggml_tensor * as, struct ggml_tensor * b,
                                               struct ggml_tensor * ids);
 GGML_API void ggml_mul_mat_set_prec(struct ggml_tensor * a, enum ggml_prec prec);
+GGML_API struct ggml_tensor * ggml_flash_attn_ext(struct ggml_context * ctx, struct ggml_tensor * q, struct ggml_tensor * k,
+                                                  struct ggml_tensor * v, struct ggml_tensor * mask, float scale, float max_bias);
+GGML_API void ggml_flash_attn_ext_set_prec(struct ggml_tensor * a, enum ggml_prec prec);
 GGML_API struct ggml_tensor * ggml_dup(struct ggml_context * ctx, struct ggml_tensor * a);
 GGML_API struct ggml_tensor * ggml_add(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);
 GGML_API struct ggml_tensor * ggml_add_inplace(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);
