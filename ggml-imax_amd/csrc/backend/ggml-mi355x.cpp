@@ -45,7 +45,7 @@
 static_assert(MI_TYPE_F32 == GGML_TYPE_F32 && MI_TYPE_F16 == GGML_TYPE_F16 && MI_TYPE_Q4_0 == GGML_TYPE_Q4_0 && MI_TYPE_Q4_1 == GGML_TYPE_Q4_1 &&
               MI_TYPE_Q5_0 == GGML_TYPE_Q5_0 && MI_TYPE_Q5_1 == GGML_TYPE_Q5_1 && MI_TYPE_Q8_0 == GGML_TYPE_Q8_0 && MI_TYPE_Q8_1 == GGML_TYPE_Q8_1 &&
               MI_TYPE_Q4_K == GGML_TYPE_Q4_K && MI_TYPE_Q5_K == GGML_TYPE_Q5_K && MI_TYPE_Q6_K == GGML_TYPE_Q6_K && MI_TYPE_Q8_K == GGML_TYPE_Q8_K &&
-              MI_TYPE_I32 == GGML_TYPE_I32, "mi355x_types.h names ggml_type values");
+              MI_TYPE_Q2_K == GGML_TYPE_Q2_K && MI_TYPE_Q3_K == GGML_TYPE_Q3_K && MI_TYPE_I32 == GGML_TYPE_I32, "mi355x_types.h names ggml_type values");
 
 static constexpr size_t kBufferAlign = 256;   // tensor alignment inside device buffers
 static constexpr size_t kBufferSlack = 256;   // tail slack: kernels may over-read < 16 B past a row

@@ -1,5 +1,6 @@
 // ggml_quants_host.cpp -- ggml_quantize_chunk (include/ggml/ggml.h:2240-2254) for the weight
-// formats on the hot path: Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q4_K, Q5_K, Q6_K (+ F16 / F32 passthrough).
+// formats on the hot path: Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K (+ F16 / F32
+// passthrough).
 //
 // These produce the bytes the MI355X kernels consume. They must be bit-identical to the
 // reference's imatrix == NULL path (src/ggml.c:21594-21660 -> src/ggml-quants.c reference
@@ -25,6 +26,9 @@ struct blk_q5_K { ggml_fp16_t d, dmin; uint8_t scales[12]; uint8_t qh[32]; uint8
 struct blk_q6_K { uint8_t ql[128]; uint8_t qh[64]; int8_t scales[16]; ggml_fp16_t d; };
 static_assert(sizeof(blk_q4_0) == 18 && sizeof(blk_q8_0) == 34 && sizeof(blk_q4_K) == 144 && sizeof(blk_q5_K) == 176, "blocks");
 static_assert(sizeof(blk_q6_K) == 210, "blocks");
+struct blk_q2_K { uint8_t scales[16]; uint8_t qs[64]; ggml_fp16_t d, dmin; };
+struct blk_q3_K { uint8_t hmask[32]; uint8_t qs[64]; uint8_t scales[12]; ggml_fp16_t d; };
+static_assert(sizeof(blk_q2_K) == 84 && sizeof(blk_q3_K) == 110, "blocks");
 struct blk_q4_1 { ggml_fp16_t d, m; uint8_t qs[16]; };
 struct blk_q5_0 { ggml_fp16_t d; uint8_t qh[4]; uint8_t qs[16]; };
 struct blk_q5_1 { ggml_fp16_t d, m; uint8_t qh[4]; uint8_t qs[16]; };
@@ -432,6 +436,253 @@ void quantize_q6_K_rows(const float * x, blk_q6_K * y, int64_t n) {
     }
 }
 
+// src/ggml-quants.c:1275-1354 make_qkx2_quants(n = 16, nmax = 3, weights |x|, rmin -0.5, rdelta 0.1,
+// nstep 15, use_mad = true), the (scale, min) search of one Q2_K sub-block by weighted absolute
+// error. search_scale_min above is its n = 32 squared-error form and leaves the roundings to this
+// file's compiler; here they are written out as the reference's x86 build (inlined into
+// quantize_row_q2_K_reference, gcc -O3 -mfma) performs them. All of it is scalar code there and
+// every product that feeds an add is contracted: sum_x = fma(w, x, sum_x) after a first rounded
+// w0 x0; nearest_int(iscale (x - min)) = fma(iscale, x - min, 1.5 * 2^23); diff = fma(scale, l, min)
+// - x; the error sums fma(w, |diff|, .); sum_l2 = fma(w l, l, .) and sum_xl = fma(w l, x, .) with
+// w l rounded once; D = fma(sum_w, sum_l2, -(sum_l sum_l)), the min's numerator
+// fma(sum_l2, sum_x, -(sum_l sum_xl)), the scale's fma(-sum_l, sum_x, sum_w sum_xl); and
+// rmin + rdelta is + nmax is fma(0.1, is, -0.5) + 3.
+float search_scale_min_mad16(const float * x, uint8_t * L, float * out_min) {
+    constexpr int n = 16, nmax = 3, nstep = 15;
+    uint8_t Laux[n];
+    float w[n];
+    for (int i = 0; i < n; ++i) w[i] = fabsf(x[i]);
+    float lo = x[0], hi = x[0];
+    float sum_w = w[0];
+    float sum_x = mul_rn(w[0], x[0]);
+    for (int i = 1; i < n; ++i) {
+        if (x[i] < lo) lo = x[i];
+        if (x[i] > hi) hi = x[i];
+        sum_w += w[i];
+        sum_x = fmaf(w[i], x[i], sum_x);
+    }
+    if (lo > 0) lo = 0;
+    if (hi == lo) {
+        memset(L, 0, n);
+        *out_min = -lo;
+        return 0.f;
+    }
+    float iscale = nmax / (hi - lo);
+    float scale = 1 / iscale;
+    float best = 0;
+    for (int i = 0; i < n; ++i) {
+        int l = rne_int_fma(iscale, x[i] - lo);
+        L[i] = (uint8_t) clampv(l, 0, nmax);
+        float diff = fabsf(fmaf(scale, (float) L[i], lo) - x[i]);
+        best = fmaf(w[i], diff, best);
+    }
+    for (int is = 0; is <= nstep; ++is) {
+        iscale = (fmaf(0.1f, (float) is, -0.5f) + (float) nmax) / (hi - lo);
+        float sum_l = 0, sum_l2 = 0, sum_xl = 0;
+        for (int i = 0; i < n; ++i) {
+            int l = clampv(rne_int_fma(iscale, x[i] - lo), 0, nmax);
+            Laux[i] = (uint8_t) l;
+            const float wl = mul_rn(w[i], (float) l);
+            sum_l2 = fmaf(wl, (float) l, sum_l2);
+            sum_xl = fmaf(wl, x[i], sum_xl);
+            sum_l += wl;
+        }
+        const float D = fmaf(sum_w, sum_l2, -mul_rn(sum_l, sum_l));
+        if (D > 0) {
+            float this_min = fmaf(sum_l2, sum_x, -mul_rn(sum_l, sum_xl)) / D;
+            float this_scale;
+            if (this_min > 0) {
+                this_min = 0;
+                this_scale = sum_xl / sum_l2;
+            } else {
+                this_scale = fmaf(-sum_l, sum_x, mul_rn(sum_w, sum_xl)) / D;
+            }
+            float mad = 0;
+            for (int i = 0; i < n; ++i) {
+                const float diff = fabsf(fmaf(this_scale, (float) Laux[i], this_min) - x[i]);
+                mad = fmaf(w[i], diff, mad);
+            }
+            if (mad < best) {
+                memcpy(L, Laux, n);
+                best = mad;
+                scale = this_scale;
+                lo = this_min;
+            }
+        }
+    }
+    *out_min = -lo;
+    return scale;
+}
+
+// the quants of Q2_K and Q3_K (and Q6_K's ql halves): byte qs[32 h + b] holds, at bit 2 t, the low
+// two bits of element 128 h + 32 t + b
+template <typename T> void pack_2bit(const T * L, uint8_t * qs) {
+    for (int j = 0; j < kQKK; j += 128)
+        for (int l = 0; l < 32; ++l)
+            qs[j / 4 + l] = (uint8_t) (L[j + l] | (L[j + l + 32] << 2) | (L[j + l + 64] << 4) | (L[j + l + 96] << 6));
+}
+
+// src/ggml-quants.c:1369-1444 quantize_row_q2_K_reference. nearest_int(iscale * v) of the 4-bit
+// scales and mins is the contracted fma; the final levels are nearest_int((x + dmin m) / d), where
+// x + dmin m is one fma (dmin m is exact anyway: fp16 times a 4-bit integer) and the bias is added
+// to the rounded quotient.
+void quantize_q2_K_rows(const float * x, blk_q2_K * y, int64_t n) {
+    uint8_t L[kQKK];
+    float mins[kQKK / 16], scales[kQKK / 16];
+    for (int64_t b = 0; b < n / kQKK; ++b, x += kQKK) {
+        float max_scale = 0, max_min = 0;
+        for (int j = 0; j < kQKK / 16; ++j) {
+            scales[j] = search_scale_min_mad16(x + 16 * j, L + 16 * j, &mins[j]);
+            if (scales[j] > max_scale) max_scale = scales[j];
+            if (mins[j] > max_min) max_min = mins[j];
+        }
+        if (max_scale > 0) {
+            const float iscale = 15.f / max_scale;
+            for (int j = 0; j < kQKK / 16; ++j) y[b].scales[j] = (uint8_t) rne_int_fma(iscale, scales[j]);
+            y[b].d = ggml_fp32_to_fp16(max_scale / 15.f);
+        } else {
+            memset(y[b].scales, 0, kQKK / 16);
+            y[b].d = ggml_fp32_to_fp16(0.f);
+        }
+        if (max_min > 0) {
+            const float iscale = 15.f / max_min;
+            for (int j = 0; j < kQKK / 16; ++j) y[b].scales[j] |= (uint8_t) (rne_int_fma(iscale, mins[j]) << 4);
+            y[b].dmin = ggml_fp32_to_fp16(max_min / 15.f);
+        } else {
+            y[b].dmin = ggml_fp32_to_fp16(0.f);
+        }
+        for (int j = 0; j < kQKK / 16; ++j) {
+            const float d = ggml_fp16_to_fp32(y[b].d) * (float) (y[b].scales[j] & 0xF);
+            if (!d) continue;
+            const float dmin = ggml_fp16_to_fp32(y[b].dmin), m = (float) (y[b].scales[j] >> 4);
+            for (int ii = 0; ii < 16; ++ii) {
+                int l = rne_int(fmaf(dmin, m, x[16 * j + ii]) / d);
+                L[16 * j + ii] = (uint8_t) clampv(l, 0, 3);
+            }
+        }
+        pack_2bit(L, y[b].qs);
+    }
+}
+
+// src/ggml-quants.c:1173-1230 make_q3_quants(n = 16, nmax = 4, do_rmse = true): the symmetric scale
+// of one Q3_K sub-block, weights x^2, refined by up to five passes that move one level at a time.
+// Roundings as the reference's x86 build performs them (inlined into quantize_row_q3_K_reference,
+// scalar throughout): w x and w l are rounded products, then sumlx = fma(w x, l, sumlx) and
+// suml2 = fma(w l, l, suml2); in the refinement slx = fma(-(w x), l, sumlx), sl2 = fma(-(w l), l,
+// suml2), the candidate level nearest_int((x sl2) / slx) with the bias added to the rounded
+// quotient, and the updates again fma(w x, new_l, slx) / fma(w new_l, new_l, sl2); the comparison
+// multiplies (slx slx) suml2 and (sumlx sumlx) sl2 from the left. L gets the levels + 4.
+float search_scale_q3(const float * x, int8_t * L) {
+    constexpr int n = 16, nmax = 4;
+    float max = 0;
+    float amax = 0;
+    for (int i = 0; i < n; ++i) {
+        float ax = fabsf(x[i]);
+        if (ax > amax) { amax = ax; max = x[i]; }
+    }
+    if (!amax) {  // all zero
+        for (int i = 0; i < n; ++i) L[i] = 0;
+        return 0.f;
+    }
+    const float iscale = -nmax / max;
+    float sumlx = 0;
+    float suml2 = 0;
+    for (int i = 0; i < n; ++i) {
+        int l = clampv(rne_int_fma(iscale, x[i]), -nmax, nmax - 1);
+        L[i] = (int8_t) l;
+        const float w = mul_rn(x[i], x[i]);
+        sumlx = fmaf(mul_rn(w, x[i]), (float) l, sumlx);
+        suml2 = fmaf(mul_rn(w, (float) l), (float) l, suml2);
+    }
+    for (int itry = 0; itry < 5; ++itry) {
+        int n_changed = 0;
+        for (int i = 0; i < n; ++i) {
+            const float w = mul_rn(x[i], x[i]);
+            const float wx = mul_rn(w, x[i]);
+            const float lf = (float) L[i];
+            float slx = fmaf(-wx, lf, sumlx);
+            if (slx > 0) {
+                float sl2 = fmaf(-mul_rn(w, lf), lf, suml2);
+                int new_l = clampv(rne_int(mul_rn(x[i], sl2) / slx), -nmax, nmax - 1);
+                if (new_l != L[i]) {
+                    const float nf = (float) new_l;
+                    sl2 = fmaf(mul_rn(w, nf), nf, sl2);
+                    slx = fmaf(wx, nf, slx);
+                    if (sl2 > 0 && mul_rn(mul_rn(slx, slx), suml2) > mul_rn(mul_rn(sumlx, sumlx), sl2)) {
+                        L[i] = (int8_t) new_l;
+                        sumlx = slx;
+                        suml2 = sl2;
+                        ++n_changed;
+                    }
+                }
+            }
+        }
+        if (!n_changed) break;
+    }
+    for (int i = 0; i < n; ++i) L[i] = (int8_t) (L[i] + nmax);
+    return sumlx / suml2;
+}
+
+// the 6-bit scale of Q3_K sub-block j (0..63, the value + 32): low four bits in the nibbles of
+// scales[0..7], upper two bits in scales[8 + j % 4] at bit 2 (j / 4)
+inline int q3_scale(const uint8_t * scales, int j) {
+    const int lo = j < 8 ? scales[j] & 0xF : scales[j - 8] >> 4;
+    return lo | (((scales[8 + j % 4] >> (2 * (j / 4))) & 3) << 4);
+}
+
+// src/ggml-quants.c:1766-1877 quantize_row_q3_K_reference. nearest_int(iscale * scale) is the
+// contracted fma, cut to int8_t before the clamp as there; the final levels are
+// nearest_int(x / d) with the bias added to the rounded quotient. A sub-block whose d * sc is zero
+// keeps the levels of the search.
+void quantize_q3_K_rows(const float * x, blk_q3_K * y, int64_t n) {
+    int8_t L[kQKK];
+    float scales[kQKK / 16];
+    for (int64_t b = 0; b < n / kQKK; ++b, x += kQKK) {
+        float max_scale = 0;
+        float amax = 0;
+        for (int j = 0; j < kQKK / 16; ++j) {
+            scales[j] = search_scale_q3(x + 16 * j, L + 16 * j);
+            const float scale = fabsf(scales[j]);
+            if (scale > amax) {
+                amax = scale;
+                max_scale = scales[j];
+            }
+        }
+        memset(y[b].scales, 0, 12);
+        if (max_scale) {
+            const float iscale = -32.f / max_scale;
+            for (int j = 0; j < kQKK / 16; ++j) {
+                int8_t l = (int8_t) rne_int_fma(iscale, scales[j]);
+                l = (int8_t) (clampv((int) l, -32, 31) + 32);
+                if (j < 8) y[b].scales[j] = (uint8_t) (l & 0xF);
+                else y[b].scales[j - 8] |= (uint8_t) ((l & 0xF) << 4);
+                l = (int8_t) (l >> 4);
+                y[b].scales[j % 4 + 8] |= (uint8_t) (l << (2 * (j / 4)));
+            }
+            y[b].d = ggml_fp32_to_fp16(1 / iscale);
+        } else {
+            y[b].d = ggml_fp32_to_fp16(0.f);
+        }
+        for (int j = 0; j < kQKK / 16; ++j) {
+            const float d = ggml_fp16_to_fp32(y[b].d) * (float) (q3_scale(y[b].scales, j) - 32);
+            if (!d) continue;
+            for (int ii = 0; ii < 16; ++ii) {
+                int l = rne_int(x[16 * j + ii] / d);
+                L[16 * j + ii] = (int8_t) (clampv(l, -4, 3) + 4);
+            }
+        }
+        // bit 4 h + t of hmask[b]: the high bit of element 128 h + 32 t + b
+        memset(y[b].hmask, 0, kQKK / 8);
+        for (int j = 0; j < kQKK; ++j) {
+            if (L[j] > 3) {
+                y[b].hmask[j % 32] |= (uint8_t) (1u << (j / 32));
+                L[j] = (int8_t) (L[j] - 4);
+            }
+        }
+        pack_2bit(L, y[b].qs);
+    }
+}
+
 } // namespace
 
 extern "C" {
@@ -460,6 +711,8 @@ size_t ggml_quantize_chunk(enum ggml_type type, const float * src, void * dst, i
         case GGML_TYPE_Q5_0: quantize_q5_0_rows(in, (blk_q5_0 *) out, n); break;
         case GGML_TYPE_Q5_1: quantize_q5_1_rows(in, (blk_q5_1 *) out, n); break;
         case GGML_TYPE_Q8_0: quantize_q8_0_rows(in, (blk_q8_0 *) out, n); break;
+        case GGML_TYPE_Q2_K: quantize_q2_K_rows(in, (blk_q2_K *) out, n); break;
+        case GGML_TYPE_Q3_K: quantize_q3_K_rows(in, (blk_q3_K *) out, n); break;
         case GGML_TYPE_Q4_K: quantize_q4_K_rows(in, (blk_q4_K *) out, n); break;
         case GGML_TYPE_Q5_K: quantize_q5_K_rows(in, (blk_q5_K *) out, n); break;
         case GGML_TYPE_Q6_K: quantize_q6_K_rows(in, (blk_q6_K *) out, n); break;

@@ -19,7 +19,7 @@
 // the ggml_type values the kernels use (the kernel directory does not see the ggml ABI header: the
 // backend static_asserts each against GGML_TYPE_*). Kernel templates take them as plain ints.
 constexpr int MI_TYPE_F32 = 0, MI_TYPE_F16 = 1, MI_TYPE_Q4_0 = 2, MI_TYPE_Q4_1 = 3, MI_TYPE_Q5_0 = 6, MI_TYPE_Q5_1 = 7,
-              MI_TYPE_Q8_0 = 8, MI_TYPE_Q8_1 = 9, MI_TYPE_Q4_K = 12, MI_TYPE_Q5_K = 13, MI_TYPE_Q6_K = 14, MI_TYPE_Q8_K = 15,
+              MI_TYPE_Q8_0 = 8, MI_TYPE_Q8_1 = 9, MI_TYPE_Q2_K = 10, MI_TYPE_Q3_K = 11, MI_TYPE_Q4_K = 12, MI_TYPE_Q5_K = 13, MI_TYPE_Q6_K = 14, MI_TYPE_Q8_K = 15,
               MI_TYPE_I32 = 26;
 
 // How the activation columns of a mul_mat are quantized: the weight type's vec_dot_type in the
@@ -60,9 +60,12 @@ struct mi_type_info {
 // boxes (profiles/r04p_gemv_sweep.txt, r04r_gemv_sweep.txt): Q4_K depth 3 (4096^2 +2..4 %,
 // 4096 x 11008 +2..4 %), Q5_K depth 2 (+2 %), Q4_0 pairs depth 3 (+1..4 %), Q8_0 depth 1 (+1 %)
 // (Q4_1 / Q5_0 / Q5_1: depth 2 like the other 5- and 6-dword items, not tuned: DESIGN section 14)
+// Q2_K depth 2, Q3_K depth 1 (profiles/q2k_q3k_variant_sweep.txt: no difference beyond the rounds' spread
+// at K = 4096; Q3_K 11008 x 4096 -8 % in tree order and -14 % in the reference order at depth 1)
 //
 // mmv_align: 16-byte rows, except Q6_K, whose 210-byte blocks its loads re-align themselves (rows
-// of an odd superblock count are 2 mod 4: K = 11008 has 9030-byte rows).
+// of an odd superblock count are 2 mod 4: K = 11008 has 9030-byte rows), and likewise Q3_K (110-byte
+// blocks: 2) and Q2_K (84-byte blocks: 4).
 // planes: Q5_K has the plane format (PFmt) and its repack kernel, but no GEMM that reads them.
 constexpr mi_type_info kMiTypes[] = {
     //  type         blck bytes act          has_m  has_qh sub  mmv  align mmqx   mmq    planes copy   get_rows
@@ -73,6 +76,8 @@ constexpr mi_type_info kMiTypes[] = {
     {MI_TYPE_Q5_0,   32,  22,  MI_ACT_Q8_0, false, true,  16,  21,  16,   false, false, false, false, true},
     {MI_TYPE_Q5_1,   32,  24,  MI_ACT_Q8_1, true,  true,  0,   21,  16,   false, false, false, false, true},
     {MI_TYPE_Q8_0,   32,  34,  MI_ACT_Q8_0, false, false, 0,   11,  16,   true,  true,  false, true,  true},
+    {MI_TYPE_Q2_K,   256, 84,  MI_ACT_Q8_K, false, false, 0,   21,  4,    false, false, false, false, true},
+    {MI_TYPE_Q3_K,   256, 110, MI_ACT_Q8_K, false, false, 0,   11,  2,    false, false, false, false, true},
     {MI_TYPE_Q4_K,   256, 144, MI_ACT_Q8_K, false, false, 0,   31,  16,   true,  true,  true,  false, true},
     {MI_TYPE_Q5_K,   256, 176, MI_ACT_Q8_K, false, false, 0,   21,  16,   true,  true,  false, false, true},
     {MI_TYPE_Q6_K,   256, 210, MI_ACT_Q8_K, false, false, 0,   21,  2,    false, false, false, false, true},
@@ -100,6 +105,8 @@ template <class F> void mi_dispatch_type(int type, F && f) {
         case MI_TYPE_Q4_1: f(mi_type_c<MI_TYPE_Q4_1>{}); break;
         case MI_TYPE_Q5_0: f(mi_type_c<MI_TYPE_Q5_0>{}); break;
         case MI_TYPE_Q5_1: f(mi_type_c<MI_TYPE_Q5_1>{}); break;
+        case MI_TYPE_Q2_K: f(mi_type_c<MI_TYPE_Q2_K>{}); break;
+        case MI_TYPE_Q3_K: f(mi_type_c<MI_TYPE_Q3_K>{}); break;
         case MI_TYPE_Q4_K: f(mi_type_c<MI_TYPE_Q4_K>{}); break;
         case MI_TYPE_Q5_K: f(mi_type_c<MI_TYPE_Q5_K>{}); break;
         case MI_TYPE_Q6_K: f(mi_type_c<MI_TYPE_Q6_K>{}); break;

@@ -18,6 +18,8 @@
 //   Q4_K x Q8_K  ggml_vec_dot_q4_K_q8_K  src/ggml-quants.c:7007-7502
 //   Q5_K x Q8_K  ggml_vec_dot_q5_K_q8_K  src/ggml-quants.c:7833-8378
 //   Q6_K x Q8_K  ggml_vec_dot_q6_K_q8_K  src/ggml-quants.c:8730-9310
+//   Q2_K x Q8_K  ggml_vec_dot_q2_K_q8_K  src/ggml-quants.c:5105-5169
+//   Q3_K x Q8_K  ggml_vec_dot_q3_K_q8_K  src/ggml-quants.c:6001-6103
 // (F16 and F32 live in mmv_ordered.hip: bit-exact CPU summation order.)
 
 #include "mi355x_common.h"
@@ -613,6 +615,187 @@ __global__ __launch_bounds__(256) void k_mmv_q6k_ord(const uint8_t * __restrict_
     }
 }
 
+// ---------------------------------------------------------------- Q2_K / Q3_K x Q8_K
+//
+// ggml_vec_dot_q2_K_q8_K (src/ggml-quants.c:5105-5169) and ggml_vec_dot_q3_K_q8_K (:6001-6103), the
+// AVX2 branches. Q2_K (84 B): scales[16] | qs[64] | fp16 d | fp16 dmin, element d (sc & 0xF) q -
+// dmin (sc >> 4) with q in 0..3. Q3_K (110 B): hmask[32] | qs[64] | scales[12] | fp16 d, element
+// d (sc - 32) (q - (hbit ? 0 : 4)) with the 6-bit sc as q3k_scale unpacks it. Both pack the quants
+// alike: byte qs[32h + b] holds at bit 2t element 128h + 32t + b (h = 0..1, t = 0..3, b = 0..31);
+// bit 4h + t of hmask[b] is that element's high bit. Q2_K blocks are 4-byte aligned, Q3_K blocks
+// 2-byte aligned (rows of an odd superblock count are 2 mod 4): aligned dwords (+ v_alignbyte) or
+// narrower loads only, as Q6_K.
+template <int T> struct q23k_fmt {
+    static constexpr bool Q3 = T == MI_TYPE_Q3_K;
+    static constexpr int BS = mi_type(T).bytes;
+    static constexpr int QS = Q3 ? 32 : 16;   // offset of qs
+    static constexpr int SC = Q3 ? 96 : 0;    // offset of scales
+    static constexpr int D = Q3 ? 108 : 80;   // offset of d (Q2_K: dmin follows)
+};
+
+// sub-block t's quants of a dword of qs (and, Q3_K, of the hmask dword of the same bytes, high bit
+// 4h + t) as int8x4: Q2_K q in 0..3; Q3_K (q | hbit << 2) - 4 = q - (hbit ? 0 : 4), no carries
+// between the bytes ((v + 128 - 4) never borrows, the xor takes the 128 back out)
+template <bool Q3>
+__device__ __forceinline__ int q23k_quants(uint32_t qs, uint32_t hm, int h, int t) {
+    const uint32_t q = (qs >> (2 * t)) & 0x03030303u;
+    if constexpr (!Q3) return (int) q;
+    else return (int) (((q | (((hm >> (4 * h + t)) & 0x01010101u) << 2) | 0x80808080u) - 0x04040404u) ^ 0x80808080u);
+}
+
+// Q3_K: sub-block j's scale minus 32 -- low four bits in the nibbles of scales[0..7], upper two in
+// scales[8 + j % 4] at bit 2 (j / 4) (the kmask1 / kmask2 unpack of the reference)
+__device__ __forceinline__ int q3k_scale(const uint8_t * scales, int j) {
+    const int lo = (scales[j & 7] >> (4 * (j >> 3))) & 0xF;
+    return (lo | (((scales[8 + (j & 3)] >> (2 * (j >> 2))) & 3) << 4)) - 32;
+}
+
+// Tree order: Q6_K's item (superblock s, 128-half h, 16-byte range u), item = 4s + 2h + u. It
+// reads qs[32h + 16u ..+15] (and hmask[16u ..+15]): the four 16-element sub-blocks at elements
+// 128h + 32t + 16u, scales index 8h + 2t + u. All integer sums are exact in f32 (an item is at most
+// 4 * 16 * 4 * 128 * 32 = 2^20). Q2_K's mins term needs the 16-element sums of the activations,
+// which act.s32 (sums of 32) does not hold: v_dot4 of the quants in hand against 0x01010101.
+template <int NC, int T, int ID = 0>
+__global__ __launch_bounds__(256) void k_mmv_q23k(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
+    using F = q23k_fmt<T>;
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t) blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+    if (row >= g.N) return;
+    mmv_item<NC, ID> bi;
+    if (!bi.init(g)) return;
+    const uint8_t * wrow = W + bi.wofs + row * g.nb01;
+    const int nsb = (int) (g.K / 256);
+
+    float acc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) acc[c] = 0.0f;
+
+    for (int it = lane; it < 4 * nsb; it += 64) {
+        const int s = it >> 2;
+        const int h = (it >> 1) & 1;
+        const int u = it & 1;
+        const uint8_t * blk = wrow + (size_t) s * F::BS;
+        uint32_t qs[4], hm[4] = {0u, 0u, 0u, 0u};
+        load_qs_unaligned<16>(blk + F::QS + 32 * h + 16 * u, qs);
+        if constexpr (F::Q3) load_qs_unaligned<16>(blk + 16 * u, hm);
+        int q[4][4], sc[4], mn[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) q[t][i] = q23k_quants<F::Q3>(qs[i], hm[i], h, t);
+            if constexpr (F::Q3) {
+                sc[t] = q3k_scale(blk + F::SC, 8 * h + 2 * t + u);
+                mn[t] = 0;
+            } else {
+                const int b = blk[8 * h + 2 * t + u];
+                sc[t] = b & 0xF;
+                mn[t] = b >> 4;
+            }
+        }
+        const float dw = mi_h2f(*(const uint16_t *) (blk + F::D));
+        const float dmw = F::Q3 ? 0.0f : mi_h2f(*(const uint16_t *) (blk + F::D + 2));
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            if (NC > 1 && !bi.has(g, c)) break;
+            const int64_t col = bi.col(c);
+            const int4 * a = (const int4 *) (act.qs + col * g.K + (int64_t) s * 256 + 128 * h + 16 * u);
+            int sumi = 0, summ = 0;
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const int4 av = a[2 * t];
+                int p = mi_dot4(q[t][0], av.x, 0);
+                p = mi_dot4(q[t][1], av.y, p);
+                p = mi_dot4(q[t][2], av.z, p);
+                p = mi_dot4(q[t][3], av.w, p);
+                sumi += sc[t] * p;
+                if constexpr (!F::Q3) {
+                    int b16 = mi_dot4(0x01010101, av.x, 0);
+                    b16 = mi_dot4(0x01010101, av.y, b16);
+                    b16 = mi_dot4(0x01010101, av.z, b16);
+                    b16 = mi_dot4(0x01010101, av.w, b16);
+                    summ += mn[t] * b16;
+                }
+            }
+            acc[c] += act.d[col * nsb + s] * (dw * (float) sumi - dmw * (float) summ);
+        }
+    }
+    mmv_store<NC, ID>(g, dst, row, bi, acc, lane);
+}
+
+// Reference order: both AVX2 dots keep eight int32 lanes per superblock, lane l = sum over the
+// eight 32-element groups g of S[2g + (l >= 4)] * sum_{e = 4l..4l+3} Q[32g + e] * a[32g + e], with
+// (S, Q) = (sc & 0xF, q) for Q2_K and (sc - 32, q - 4 * !hbit) for Q3_K (maddubs pairs -- Q3_K's
+// high-bit part as a second maddubs, subtracted -- then madd_epi16 with the scales: no step
+// saturates), then acc[l] = fma(y.d * fp16(x.d), (float) sumi[l], acc[l]) over the superblocks and
+// hsum_float_8. Q2_K first adds its mins on the same accumulator: acc[l] = fma(-y.d * fp16(x.dmin),
+// (float) (m[2l] * bsums[2l] + m[2l+1] * bsums[2l+1]), acc[l]), m the high nibbles of scales and
+// bsums the 16-element sums of the Q8_K block (here: of the quants, which is what they are).
+// A lane sum is at most 8 * 4 * 4 * 128 * 32 = 2^19 and a mins product below 2^16: exact in f32.
+// Eight lanes are the eight CPU lanes of one row (8 rows per wave), as k_mmv_q6k_ord.
+template <int NC, int T, int ID = 0>
+__global__ __launch_bounds__(256) void k_mmv_q23k_ord(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
+    using F = q23k_fmt<T>;
+    const int l = threadIdx.x & 7;
+    const int64_t row = (int64_t) blockIdx.x * 32 + (threadIdx.x >> 3);
+    const bool live = row < g.N;
+    const int64_t rc = live ? row : g.N - 1;  // (dead groups run a valid row: no early exit before the shuffles)
+    mmv_item<NC, ID> bi;
+    if (!bi.init(g)) return;
+    const uint8_t * wrow = W + bi.wofs + rc * g.nb01;
+    const int nsb = (int) (g.K / 256);
+    const int hi = l >> 2;  // which 16-element half of each 32-group the lane's elements lie in
+
+    float A[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) A[c] = 0.0f;
+
+    for (int s = 0; s < nsb; s++) {
+        const uint8_t * blk = wrow + (size_t) s * F::BS;
+        const float dw = mi_h2f(*(const uint16_t *) (blk + F::D));
+        const float dmw = F::Q3 ? 0.0f : mi_h2f(*(const uint16_t *) (blk + F::D + 2));
+        const uint32_t hm = F::Q3 ? ld32_a2(blk + 4 * l) : 0u;
+        int q[8], sc[8];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const uint32_t qs = ld32_a2(blk + F::QS + 32 * h + 4 * l);
+#pragma unroll
+            for (int t = 0; t < 4; t++) q[4 * h + t] = q23k_quants<F::Q3>(qs, hm, h, t);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) sc[j] = F::Q3 ? q3k_scale(blk + F::SC, 2 * j + hi) : (blk[2 * j + hi] & 0xF);
+        int m0 = 0, m1 = 0;
+        if constexpr (!F::Q3) {
+            m0 = blk[2 * l] >> 4;
+            m1 = blk[2 * l + 1] >> 4;
+        }
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            if (NC > 1 && !bi.has(g, c)) break;
+            const int64_t col = bi.col(c);
+            const int8_t * aq = act.qs + col * g.K + (int64_t) s * 256;
+            const float ya = act.d[col * nsb + s];
+            if constexpr (!F::Q3) {
+                const int4 b0 = *(const int4 *) (aq + 32 * l), b1 = *(const int4 *) (aq + 32 * l + 16);
+                const int s0 = mi_dot4(0x01010101, b0.w, mi_dot4(0x01010101, b0.z, mi_dot4(0x01010101, b0.y, mi_dot4(0x01010101, b0.x, 0))));
+                const int s1 = mi_dot4(0x01010101, b1.w, mi_dot4(0x01010101, b1.z, mi_dot4(0x01010101, b1.y, mi_dot4(0x01010101, b1.x, 0))));
+                A[c] = fmaf(-ya * dmw, (float) (m0 * s0 + m1 * s1), A[c]);  // _mm256_fmadd_ps(dmin, cvt(prod), acc)
+            }
+            int sumi = 0;
+#pragma unroll
+            for (int j = 0; j < 8; j++) sumi += sc[j] * mi_dot4(q[j], *(const int *) (aq + 32 * j + 4 * l), 0);
+            A[c] = fmaf(ya * dw, (float) sumi, A[c]);  // _mm256_fmadd_ps(d, cvt(sumi), acc)
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        // hsum_float_8: ((a0 + a4) + (a2 + a6)) + ((a1 + a5) + (a3 + a7))
+        float z = A[c] + __shfl_xor(A[c], 4, 8);
+        z = z + __shfl_xor(z, 2, 8);
+        z = z + __shfl_xor(z, 1, 8);
+        if (l == 0 && live && bi.has(g, c)) *bi.out(g, dst, row, c) = z;
+    }
+}
+
 mmv_geom make_geom(const mi_mm_desc & m, int NC) {
     mmv_geom g;
     g.K = m.K;
@@ -635,7 +818,7 @@ mmv_geom make_geom(const mi_mm_desc & m, int NC) {
 
 } // namespace
 
-// One launch of weight type T's GEMV (its family by the table: 32-element blocks, Q6_K, Q4_K / Q5_K) in
+// One launch of weight type T's GEMV (its family by the table: 32-element blocks, Q6_K, Q2_K / Q3_K, Q4_K / Q5_K) in
 // tree order (a wave per row) or the reference CPU's order (ORD: 8 rows per wave), NC columns per
 // workgroup. ID as mmv_item; grid_y 0: the column chunks of every (i12, i13) batch.
 template <int T, int NC, int ID, bool ORD>
@@ -651,6 +834,9 @@ static void mmv_launch(const mi_mm_desc & m, const mi_act_q8 & act, unsigned gri
     } else if constexpr (T == MI_TYPE_Q6_K) {
         if constexpr (ORD) hipLaunchKernelGGL((k_mmv_q6k_ord<NC, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
         else hipLaunchKernelGGL((k_mmv_q6k<NC, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
+    } else if constexpr (T == MI_TYPE_Q2_K || T == MI_TYPE_Q3_K) {
+        if constexpr (ORD) hipLaunchKernelGGL((k_mmv_q23k_ord<NC, T, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
+        else hipLaunchKernelGGL((k_mmv_q23k<NC, T, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
     } else {
         if constexpr (ORD) hipLaunchKernelGGL((k_mmv_kq_ord<NC, Q5, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
         else hipLaunchKernelGGL((k_mmv_kq<NC, Q5, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);

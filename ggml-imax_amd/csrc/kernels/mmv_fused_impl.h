@@ -1,6 +1,6 @@
 // mmv_fused_impl.h -- the streaming decode GEMV k_mmv_stream (see mmv_fused.hip for the design),
 // its weight-format policies and launchers. Included by one translation unit per weight format
-// (mmv_fused_q4k.hip, _q5k, _q6k, _q40, _q80, _q41, _q50, _q51) so that the kernel instances compile in parallel; each
+// (mmv_fused_q2k.hip, _q3k, _q4k, _q5k, _q6k, _q40, _q80, _q41, _q50, _q51) so that the kernel instances compile in parallel; each
 // exports one mi_mmv_launch_* entry point that mmv_fused.hip's dispatcher calls.
 #pragma once
 
@@ -1033,6 +1033,270 @@ struct FmtQ6K {
         return z + __shfl_xor(z, 1, 8);
     }
 };
+
+// Q2_K (84 B superblocks: scales[16] | qs[64] | fp16 d | fp16 dmin; element d (sc & 0xF) q -
+// dmin (sc >> 4)) and Q3_K (110 B: hmask[32] | qs[64] | scales[12] | fp16 d; element
+// d (sc - 32) (q - (hbit ? 0 : 4)), sc the 6-bit scale of the kmask1 / kmask2 unpack). Both pack
+// the quants as Q6_K packs its ql halves -- byte qs[32h + b] holds at bit 2t element 128h + 32t + b,
+// and bit 4h + t of hmask[b] is that element's high bit -- so FmtQ6K's item serves both: (superblock
+// s, 128-half h, 16-byte range u), item = 4 s + 2 h + u, reads qs[32h + 16u ..+15] (Q3_K: and
+// hmask[16u ..+15]), i.e. the four 16-element sub-blocks at elements 128h + 32t + 16u (t = 0..3) with
+// scales index 8h + 2t + u. Four items per superblock on adjacent lanes; a K = 4096 row is one item
+// per lane.
+// Loads: Q2_K blocks are 4-byte aligned wherever the row is (84 = 4 * 21), so its seven dwords
+// (four of quants, the eight scale bytes of the 128-half, d | dmin) are read where they lie. Q3_K
+// blocks are 2-byte aligned and rows of an odd superblock count are 2 mod 4 (K = 11008: 4730-byte
+// rows): as FmtQ6K, every load is an aligned dword from two bytes below or at the data, re-aligned
+// with v_alignbyte by the block's own misalignment. The dword that holds d of an aligned block
+// reaches two bytes past the block (the next block, or the buffer's tail slack); nothing reaches
+// further.
+// Q2_K's mins need the 16-element sums of the Q8_K activations, which the activations in LDS do
+// not keep (s32: sums of 32): v_dot4 of the quants in hand against 0x01010101 -- at one column in
+// tree order once per kernel (Act), not per row.
+template <bool Q3>
+struct FmtQ23K {
+    static constexpr bool KL = false;
+    static constexpr int QKA = 256;
+    static constexpr int ITEM = 64;
+    static constexpr int BS = mi_type(Q3 ? MI_TYPE_Q3_K : MI_TYPE_Q2_K).bytes;
+    static constexpr int E = Q3 ? 16 : 20;  // scratch words per superblock in the reference order
+    struct Regs {
+        uint32_t qs[Q3 ? 5 : 4];  // the dwords covering the 16 quant bytes
+        uint32_t hm[Q3 ? 5 : 1];  // Q3_K: ... the 16 hmask bytes
+        uint32_t sc[Q3 ? 4 : 2];  // Q3_K: the 12 scale bytes and d; Q2_K: the eight scales | mins of the 128-half
+        uint32_t dd;              // Q2_K: d | dmin; Q3_K: the block's misalignment, 0 or 2
+    };
+    __device__ static __forceinline__ void load(Regs & r, const uint8_t * row, int item) {
+        const uint32_t s = (uint32_t) item >> 2, h = ((uint32_t) item >> 1) & 1, u = (uint32_t) item & 1;
+        const uint32_t blk = s * BS;
+        if constexpr (Q3) {
+            const uint32_t off = ((uint32_t) (uintptr_t) row + blk) & 2;
+            r.dd = off;
+            const uint8_t * p = row + (int) (blk - off);  // 4-byte aligned (item 0 of a misaligned row: its first dword starts in the row before)
+#pragma unroll
+            for (int i = 0; i < 5; i++) {
+                r.hm[i] = *(const uint32_t *) (p + 16 * u + 4 * i);
+                r.qs[i] = *(const uint32_t *) (p + 32 + 32 * h + 16 * u + 4 * i);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) r.sc[i] = *(const uint32_t *) (p + 96 + 4 * i);  // scales, and d in sc[3]
+        } else {
+            const uint8_t * p = row + blk;
+#pragma unroll
+            for (int i = 0; i < 4; i++) r.qs[i] = *(const uint32_t *) (p + 16 + 32 * h + 16 * u + 4 * i);
+            r.hm[0] = 0u;
+            r.sc[0] = *(const uint32_t *) (p + 8 * h);
+            r.sc[1] = *(const uint32_t *) (p + 8 * h + 4);
+            r.dd = *(const uint32_t *) (p + 80);
+        }
+    }
+    // the item's operands: sub-block t's levels (Q2_K q, Q3_K q - 4 * !hbit) as four int8x4 dwords,
+    // its scale (Q2_K sc & 0xF, Q3_K sc - 32) and min, the block's d and dmin
+    struct Dec {
+        int q[4][4];
+        int sc[4];
+        int mn[Q3 ? 1 : 4];
+        float dw, dmw;
+    };
+    // CENTER (Q3_K): the levels as q - 4 * !hbit in -4..3; else as v = q | hbit << 2 in 0..7, for
+    // callers that take the 4 off on the activations' side, dot(v - 4, a) = dot(v, a) - 4 sum(a)
+    // (nine VALU operations per dword and sub-block become four: the streaming kernel at one column
+    // was bound by them, not by HBM)
+    template <bool CENTER = true>
+    __device__ static __forceinline__ void decode(Dec & d, const Regs & r, int item) {
+        const uint32_t h = ((uint32_t) item >> 1) & 1, u = (uint32_t) item & 1;
+        if constexpr (Q3) {
+            const uint32_t off = r.dd;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const uint32_t qs = __builtin_amdgcn_alignbyte(r.qs[i + 1], r.qs[i], off);
+                const uint32_t hb = (__builtin_amdgcn_alignbyte(r.hm[i + 1], r.hm[i], off) >> (4 * h)) << 2;  // high bit of sub-block t at bit 2 + t
+#pragma unroll
+                for (int t = 0; t < 4; t++) {
+                    const uint32_t v = ((qs >> (2 * t)) & 0x03030303u) | ((hb >> t) & 0x04040404u);
+                    // v - 4 per byte, no carries: (v + 128 - 4) never borrows, the xor takes the 128 back out
+                    d.q[t][i] = CENTER ? (int) (((v | 0x80808080u) - 0x04040404u) ^ 0x80808080u) : (int) v;
+                }
+            }
+            // scales j = 8h + 2t + u: low nibbles in byte 2t + u of aux[0..1] (nibble h), upper two bits in
+            // byte 2 (t & 1) + u of aux[2] at bit 2 (2h + (t >> 1))
+            const uint32_t sh = 8 * u + 4 * h;
+            const uint32_t x0 = __builtin_amdgcn_alignbyte(r.sc[1], r.sc[0], off) >> sh;
+            const uint32_t x1 = __builtin_amdgcn_alignbyte(r.sc[2], r.sc[1], off) >> sh;
+            const uint32_t y = __builtin_amdgcn_alignbyte(r.sc[3], r.sc[2], off) >> sh;
+            d.sc[0] = (int) ((x0 & 0xF) | ((y & 3) << 4)) - 32;
+            d.sc[1] = (int) (((x0 >> 16) & 0xF) | (((y >> 16) & 3) << 4)) - 32;
+            d.sc[2] = (int) ((x1 & 0xF) | (((y >> 2) & 3) << 4)) - 32;
+            d.sc[3] = (int) (((x1 >> 16) & 0xF) | (((y >> 18) & 3) << 4)) - 32;
+            d.mn[0] = 0;
+            d.dw = mi_h2f((uint16_t) ((r.sc[3] >> (8 * off)) & 0xFFFF));
+            d.dmw = 0.0f;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+#pragma unroll
+                for (int t = 0; t < 4; t++) d.q[t][i] = (int) ((r.qs[i] >> (2 * t)) & 0x03030303u);
+            }
+            const uint32_t x0 = r.sc[0] >> (8 * u), x1 = r.sc[1] >> (8 * u);
+            d.sc[0] = (int) (x0 & 0xF);         d.mn[0] = (int) ((x0 >> 4) & 0xF);
+            d.sc[1] = (int) ((x0 >> 16) & 0xF); d.mn[1] = (int) ((x0 >> 20) & 0xF);
+            d.sc[2] = (int) (x1 & 0xF);         d.mn[2] = (int) ((x1 >> 4) & 0xF);
+            d.sc[3] = (int) ((x1 >> 16) & 0xF); d.mn[3] = (int) ((x1 >> 20) & 0xF);
+            d.dw = mi_h2f((uint16_t) (r.dd & 0xFFFF));
+            d.dmw = mi_h2f((uint16_t) (r.dd >> 16));
+        }
+    }
+    // the item's 64 quantized activations of one column: sub-block t = av[4t .. 4t+3]
+    __device__ static __forceinline__ void act16(int (&av)[16], const int8_t * qs, int item) {
+        const int s = item >> 2, h = (item >> 1) & 1, u = item & 1;
+        const int4 * p = (const int4 *) (qs + (int64_t) s * 256 + 128 * h + 16 * u);
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int4 a = p[2 * t];
+            av[4 * t] = a.x; av[4 * t + 1] = a.y; av[4 * t + 2] = a.z; av[4 * t + 3] = a.w;
+        }
+    }
+    // the sum of sub-block t's 16 quants: bsums[8h + 2t + u] of the column's Q8_K block
+    __device__ static __forceinline__ int sum16(const int (&av)[16], int t) {
+        int b = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) b = mi_dot4(0x01010101, av[4 * t + i], b);
+        return b;
+    }
+    // every integer below is exact in f32: an item's sum is at most 4 * 16 * 4 * 128 * 32 = 2^20, its
+    // mins sum at most 4 * 15 * 16 * 128 < 2^17
+    template <bool CENTER = true>
+    __device__ static __forceinline__ float item_dot(const Dec & d, const int (&av)[16], const int (&b16)[4], float ad, float acc) {
+        int sumi = 0, summ = 0;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            int p = Q3 && !CENTER ? -4 * b16[t] : 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) p = mi_dot4(d.q[t][i], av[4 * t + i], p);
+            sumi += __mul24(d.sc[t], p);
+            if constexpr (!Q3) summ += __mul24(d.mn[t], b16[t]);
+        }
+        if constexpr (Q3) return fmaf((float) sumi, d.dw * ad, acc);
+        // explicit fmas (the file contracts freely): the same bits in every kernel that inlines this
+        else return fmaf(ad, fmaf(-d.dmw, (float) summ, d.dw * (float) sumi), acc);
+    }
+    template <int NC>
+    __device__ static __forceinline__ void dot(const Regs & r, int item, const lds_act & a, int64_t K, int ncols, float (&acc)[NC]) {
+        // Q3_K at one column: the 16 sums cost less than centering the 16 dwords of levels
+        constexpr bool CENTER = NC > 1;
+        Dec d;
+        decode<CENTER>(d, r, item);
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            if (NC > 1 && c >= ncols) break;
+            int av[16], b16[4] = {0, 0, 0, 0};
+            act16(av, a.qs + c * K, item);
+            if constexpr (!Q3 || !CENTER) {
+#pragma unroll
+                for (int t = 0; t < 4; t++) b16[t] = sum16(av, t);
+            }
+            acc[c] = item_dot<CENTER>(d, av, b16, a.d[c * (K / 256) + (item >> 2)], acc[c]);
+        }
+    }
+    struct Act {
+        int av[16];
+        int b16[4];
+        float ad;
+    };
+    __device__ static __forceinline__ void act_load(Act & v, int item, const lds_act & a, int64_t) {
+        act16(v.av, a.qs, item);
+#pragma unroll
+        for (int t = 0; t < 4; t++) v.b16[t] = sum16(v.av, t);
+        v.ad = a.d[item >> 2];
+    }
+    __device__ static __forceinline__ float dot_act(const Regs & r, int item, const Act & v, float acc) {
+        Dec d;
+        decode<false>(d, r, item);
+        return item_dot<false>(d, v.av, v.b16, v.ad, acc);
+    }
+
+    // CPU order (ggml_vec_dot_q2_K_q8_K / _q3_K_q8_K, AVX2): eight int32 lanes per superblock, lane l =
+    // sum over the eight 32-groups g of S[2g + (l >= 4)] * sum_{e = 4l..4l+3} Q[32g + e] a[32g + e].
+    // Item (h, u) holds groups g = 4h + t at bytes 16u..16u+15, i.e. CPU lanes 4u + i (its dword i)
+    // with exactly its four scales; the two h items of the quad add up to the lane totals (at most
+    // 2^19). Q2_K's mins lane l is m[2l] bsums[2l] + m[2l+1] bsums[2l+1]: sub-blocks 8h + 2t + u of the
+    // items (h, 0) and (h, 1) with l = 4h + t, which add up over the u pair. Entry of superblock sb
+    // in the scratch, E words: [0..7] the eight sums as floats; Q3_K [12] d = y.d * x.d (FmtKQ's
+    // slot); Q2_K [8..15] the eight mins lanes, [16] d, [17] dmin = -(y.d * x.dmin).
+    template <int NC>
+    __device__ static __forceinline__ void dot_ord(const Regs & r, int item, int slot, const lds_act & a, int64_t K, int ncols,
+                                                   uint32_t * scr, int cs, int) {
+        const int h = (item >> 1) & 1, u = item & 1;
+        constexpr bool CENTER = NC > 1;  // Q3_K at one column: a second v_dot4 against -4 instead of centering
+        Dec d;
+        decode<CENTER>(d, r, item);
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            if (NC > 1 && c >= ncols) break;
+            int av[16];
+            act16(av, a.qs + c * K, item);
+            int v[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                v[i] = 0;
+#pragma unroll
+                for (int t = 0; t < 4; t++) {
+                    const int off4 = Q3 && !CENTER ? mi_dot4((int) 0xFCFCFCFCu, av[4 * t + i], 0) : 0;
+                    v[i] += __mul24(d.sc[t], mi_dot4(d.q[t][i], av[4 * t + i], off4));
+                }
+                v[i] += mi_dpp<MI_DPP_QP_2301>(0, v[i]);  // the other 128-half: lane ^ 2 of the quad
+            }
+            uint32_t * e = scr + c * cs + (slot >> 2) * E;
+            const float yd = a.d[c * (K / 256) + (item >> 2)];
+            if constexpr (!Q3) {
+                int pm[4];
+#pragma unroll
+                for (int t = 0; t < 4; t++) {
+                    pm[t] = __mul24(d.mn[t], sum16(av, t));
+                    pm[t] += mi_dpp<MI_DPP_QP_1032>(0, pm[t]);  // the other 16-byte range: lane ^ 1 of the quad
+                }
+                if (u == 0) {
+                    *(uint4 *) (e + 8 + 4 * h) = make_uint4(__float_as_uint((float) pm[0]), __float_as_uint((float) pm[1]),
+                                                           __float_as_uint((float) pm[2]), __float_as_uint((float) pm[3]));
+                } else if (h == 1) {
+                    *(uint2 *) (e + 16) = make_uint2(__float_as_uint(yd * d.dw), __float_as_uint(-(yd * d.dmw)));
+                }
+            }
+            if (h == 0) {
+                *(uint4 *) (e + 4 * u) = make_uint4(__float_as_uint((float) v[0]), __float_as_uint((float) v[1]),
+                                                   __float_as_uint((float) v[2]), __float_as_uint((float) v[3]));
+            } else if (Q3 && u == 0) {
+                e[12] = __float_as_uint(yd * d.dw);
+            }
+        }
+    }
+    // per superblock: Q2_K acc[l] = fma(dmin, (float) mins[l], acc[l]) first, then for both
+    // acc[l] = fma(d, (float) sumi[l], acc[l]) (_mm256_fmadd_ps)
+    __device__ static __forceinline__ void chain(const uint32_t * scr, int l, int n_items, int, float & A, float &) {
+        const float * e = (const float *) scr;
+        const int nsb = n_items >> 2;
+        for (int sb = 0; sb < nsb; sb++, e += E) {
+            if constexpr (Q3) {
+                A = fmaf(e[12], e[l], A);
+            } else {
+                A = fmaf(e[17], e[8 + l], A);
+                A = fmaf(e[16], e[l], A);
+            }
+        }
+    }
+    static int ord_words(int nitems, int & stride) {
+        stride = 0;
+        return E * (nitems / 4) + 8;
+    }
+    __device__ static __forceinline__ float finish(float A, float) {
+        // hsum_float_8: ((a0 + a4) + (a2 + a6)) + ((a1 + a5) + (a3 + a7))
+        float z = A + __shfl_xor(A, 4, 8);
+        z = z + __shfl_xor(z, 2, 8);
+        return z + __shfl_xor(z, 1, 8);
+    }
+};
+using FmtQ2K = FmtQ23K<false>;
+using FmtQ3K = FmtQ23K<true>;
 
 // a format's weight load (FmtQ0R's needs the row length)
 template <class F>

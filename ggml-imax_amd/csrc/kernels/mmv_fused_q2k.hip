@@ -1,0 +1,7 @@
+// mmv_fused_q2k.hip -- the k_mmv_stream instances of one weight format (mmv_fused_impl.h),
+// compiled as a translation unit of their own so that the formats build in parallel
+#include "mmv_fused_impl.h"
+
+template <> void mi_mmv_launch<MI_TYPE_Q2_K>(const mi_mmv_group & g, int variant, hipStream_t s) {
+    launch_stream_ord<FmtQ2K>(g, variant, s);
+}

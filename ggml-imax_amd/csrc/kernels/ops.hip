@@ -2,7 +2,7 @@
 //
 // All are memory- or launch-bound. Each follows the reference CPU forward's rounding sequence so
 // that results are bit-identical where the CPU order is reproducible:
-//   get_rows   src/ggml.c:12920 (f16) / :13006 (f32) / :12874 (Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q4_K, Q5_K, Q6_K) -- exact
+//   get_rows   src/ggml.c:12920 (f16) / :13006 (f32) / :12874 (Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K .. Q6_K) -- exact
 //   add / mul  src/ggml.c:8568 / :9687 (broadcast src1)      -- exact
 //   scale      src/ggml.c:12637                              -- exact
 //   norm       src/ggml.c:11353-11406 (double sums)          -- sums in double, then the same f32 ops
@@ -186,6 +186,33 @@ __device__ __forceinline__ float dequant_elem(const uint8_t * row, int64_t c) {
         const uint8_t lq = blk[64 * h + 32 * (t & 1) + p];
         const int q = (int) (((t & 2) ? (lq >> 4) : (lq & 0x0F)) | (((blk[128 + 32 * h + p] >> (2 * t)) & 3) << 4)) - 32;
         const int sc = (int8_t) blk[192 + (e >> 4)];
+        return mul_rn(mul_rn(mi_h2f(dh), (float) sc), (float) q);
+    } else if constexpr (TYPE == MI_TYPE_Q2_K) {  // Q2_K (84 B) superblocks: scales[16] qs[64] fp16 d, dmin
+        // dequantize_row_q2_K (:1446-1490): dl * q - ml with dl = d * (sc & 0xF), ml = dmin * (sc >> 4).
+        // The reference build rounds dl * q on its own and contracts the other product,
+        // fnma(dmin, sc >> 4, dl * q); every product here is exact in f32 (an fp16 value times a
+        // 4-bit and a 2-bit integer: 17 bits), so one rounding happens, in the subtraction, whichever
+        // way it is written.
+        const uint8_t * blk = row + (c >> 8) * BS;
+        const int e = (int) (c & 255), h = e >> 7, t = (e >> 5) & 3, p = e & 31;
+        uint16_t dh, mh;
+        __builtin_memcpy(&dh, blk + 80, 2);
+        __builtin_memcpy(&mh, blk + 82, 2);
+        const int sc = blk[e >> 4];
+        const int q = (blk[16 + 32 * h + p] >> (2 * t)) & 3;
+        const float dl = mul_rn(mi_h2f(dh), (float) (sc & 0xF)), ml = mul_rn(mi_h2f(mh), (float) (sc >> 4));
+        return sub_rn(mul_rn(dl, (float) q), ml);
+    } else if constexpr (TYPE == MI_TYPE_Q3_K) {  // Q3_K (110 B) superblocks: hmask[32] qs[64] scales[12] fp16 d
+        // dequantize_row_q3_K (:1880-1928): (d * (sc - 32)) * (q - (hbit ? 0 : 4)), two separately
+        // rounded multiplies (both exact: 11 + 6 + 3 bits)
+        const uint8_t * blk = row + (c >> 8) * BS;
+        const int e = (int) (c & 255), h = e >> 7, t = (e >> 5) & 3, p = e & 31, j = e >> 4;
+        uint16_t dh;
+        __builtin_memcpy(&dh, blk + 108, 2);
+        const uint8_t * scales = blk + 96;
+        const int lo = j < 8 ? scales[j] & 0xF : scales[j - 8] >> 4;
+        const int sc = (lo | (((scales[8 + (j & 3)] >> (2 * (j >> 2))) & 3) << 4)) - 32;
+        const int q = ((blk[32 + 32 * h + p] >> (2 * t)) & 3) - (((blk[p] >> (4 * h + t)) & 1) ? 0 : 4);
         return mul_rn(mul_rn(mi_h2f(dh), (float) sc), (float) q);
     } else {  // Q4_K (144 B) / Q5_K (176 B) superblocks of 256
         constexpr bool Q5 = TYPE == MI_TYPE_Q5_K;
