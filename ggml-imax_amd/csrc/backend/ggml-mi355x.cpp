@@ -45,7 +45,8 @@
 static_assert(MI_TYPE_F32 == GGML_TYPE_F32 && MI_TYPE_F16 == GGML_TYPE_F16 && MI_TYPE_Q4_0 == GGML_TYPE_Q4_0 && MI_TYPE_Q4_1 == GGML_TYPE_Q4_1 &&
               MI_TYPE_Q5_0 == GGML_TYPE_Q5_0 && MI_TYPE_Q5_1 == GGML_TYPE_Q5_1 && MI_TYPE_Q8_0 == GGML_TYPE_Q8_0 && MI_TYPE_Q8_1 == GGML_TYPE_Q8_1 &&
               MI_TYPE_Q4_K == GGML_TYPE_Q4_K && MI_TYPE_Q5_K == GGML_TYPE_Q5_K && MI_TYPE_Q6_K == GGML_TYPE_Q6_K && MI_TYPE_Q8_K == GGML_TYPE_Q8_K &&
-              MI_TYPE_Q2_K == GGML_TYPE_Q2_K && MI_TYPE_Q3_K == GGML_TYPE_Q3_K && MI_TYPE_I32 == GGML_TYPE_I32, "mi355x_types.h names ggml_type values");
+              MI_TYPE_Q2_K == GGML_TYPE_Q2_K && MI_TYPE_Q3_K == GGML_TYPE_Q3_K && MI_TYPE_IQ4_NL == GGML_TYPE_IQ4_NL &&
+              MI_TYPE_IQ4_XS == GGML_TYPE_IQ4_XS && MI_TYPE_I32 == GGML_TYPE_I32, "mi355x_types.h names ggml_type values");
 
 static constexpr size_t kBufferAlign = 256;   // tensor alignment inside device buffers
 static constexpr size_t kBufferSlack = 256;   // tail slack: kernels may over-read < 16 B past a row
@@ -530,6 +531,9 @@ static void scratch_reserve(mi_backend_ctx * ctx, size_t bytes) {
 
 // every row of the weight-type table has a mul_mat
 static bool mm_src0_supported(ggml_type t) { return mi_type(t).type == t; }
+// IQ4_NL rows of an odd block count: the reference's AVX2 ggml_vec_dot_iq4_nl_q8_0 walks the blocks in
+// pairs with no tail and reads past the row, so it defines no result to agree with
+static bool mm_row_supported(const ggml_tensor * a) { return a->type != GGML_TYPE_IQ4_NL || a->ne[0] % 64 == 0; }
 
 static bool is_f32(const ggml_tensor * t) { return t && t->type == GGML_TYPE_F32; }
 static bool is_f16_or_f32(const ggml_tensor * t) { return t && (t->type == GGML_TYPE_F32 || t->type == GGML_TYPE_F16); }
@@ -560,7 +564,7 @@ static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
         case GGML_OP_TRANSPOSE:
             return true;
         case GGML_OP_MUL_MAT: {
-            if (!mm_src0_supported(a->type)) return false;
+            if (!mm_src0_supported(a->type) || !mm_row_supported(a)) return false;
             if (a->nb[0] != ggml_type_size(a->type) || b->nb[0] != ggml_type_size(b->type)) return false;
             // src1 F32, or src1 already of the weight's vec_dot_type, which the reference CPU reads as
             // it lies (ggml.c:11952; F16 x F16, Q4_K/Q5_K/Q6_K x Q8_K, Q4_0/Q5_0/Q8_0 x Q8_0, Q4_1/Q5_1 x Q8_1): the quantized
@@ -573,7 +577,7 @@ static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
             // experts of any mul_mat weight type on this device, F32 activations (quantized or converted
             // here, as the reference does), I32 ids read by the kernels
             const ggml_tensor * ids = op->src[2];
-            if (!mm_src0_supported(a->type) || is_split_tensor(a)) return false;
+            if (!mm_src0_supported(a->type) || !mm_row_supported(a) || is_split_tensor(a)) return false;
             if (a->nb[0] != ggml_type_size(a->type) || b->nb[0] != ggml_type_size(b->type)) return false;
             return b->type == GGML_TYPE_F32 && ids && ids->type == GGML_TYPE_I32;
         }

@@ -240,6 +240,8 @@ enum ggml_type ggml_ftype_to_ggml_type(enum ggml_ftype ftype) {
         case GGML_FTYPE_MOSTLY_Q4_K:  return GGML_TYPE_Q4_K;
         case GGML_FTYPE_MOSTLY_Q5_K:  return GGML_TYPE_Q5_K;
         case GGML_FTYPE_MOSTLY_Q6_K:  return GGML_TYPE_Q6_K;
+        case GGML_FTYPE_MOSTLY_IQ4_NL: return GGML_TYPE_IQ4_NL;
+        case GGML_FTYPE_MOSTLY_IQ4_XS: return GGML_TYPE_IQ4_XS;
         default:                      return GGML_TYPE_COUNT;
     }
 }

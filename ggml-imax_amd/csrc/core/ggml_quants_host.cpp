@@ -1,6 +1,6 @@
 // ggml_quants_host.cpp -- ggml_quantize_chunk (include/ggml/ggml.h:2240-2254) for the weight
-// formats on the hot path: Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K (+ F16 / F32
-// passthrough).
+// formats on the hot path: Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS
+// (+ F16 / F32 passthrough).
 //
 // These produce the bytes the MI355X kernels consume. They must be bit-identical to the
 // reference's imatrix == NULL path (src/ggml.c:21594-21660 -> src/ggml-quants.c reference
@@ -29,6 +29,9 @@ static_assert(sizeof(blk_q6_K) == 210, "blocks");
 struct blk_q2_K { uint8_t scales[16]; uint8_t qs[64]; ggml_fp16_t d, dmin; };
 struct blk_q3_K { uint8_t hmask[32]; uint8_t qs[64]; uint8_t scales[12]; ggml_fp16_t d; };
 static_assert(sizeof(blk_q2_K) == 84 && sizeof(blk_q3_K) == 110, "blocks");
+struct blk_iq4_nl { ggml_fp16_t d; uint8_t qs[16]; };
+struct blk_iq4_xs { ggml_fp16_t d; uint16_t scales_h; uint8_t scales_l[4]; uint8_t qs[128]; };
+static_assert(sizeof(blk_iq4_nl) == 18 && sizeof(blk_iq4_xs) == 136, "blocks");
 struct blk_q4_1 { ggml_fp16_t d, m; uint8_t qs[16]; };
 struct blk_q5_0 { ggml_fp16_t d; uint8_t qh[4]; uint8_t qs[16]; };
 struct blk_q5_1 { ggml_fp16_t d, m; uint8_t qh[4]; uint8_t qs[16]; };
@@ -683,6 +686,115 @@ void quantize_q3_K_rows(const float * x, blk_q3_K * y, int64_t n) {
     }
 }
 
+// ---- IQ4_NL / IQ4_XS: 4-bit indices into a fixed non-linear codebook (src/ggml-quants.c:3321)
+constexpr int8_t kValuesIQ4NL[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
+
+// src/ggml-quants.c:14166-14175 best_index_int8(16, kvalues_iq4nl, x): the index of the level nearest
+// to x, the upper one on a tie
+inline int iq4_best_index(float x) {
+    const int8_t * val = kValuesIQ4NL;
+    if (x <= val[0]) return 0;
+    if (x >= val[15]) return 15;
+    int ml = 0, mu = 15;
+    while (mu - ml > 1) {
+        const int mav = (ml + mu) / 2;
+        if (x < val[mav]) mu = mav; else ml = mav;
+    }
+    return x - val[mu - 1] < val[mu] - x ? mu - 1 : mu;
+}
+
+// src/ggml-quants.c:14192-14246, the scale search of one 32-element block in
+// quantize_row_iq4_nl_impl(quant_weights = NULL, ntry = 7): weights x^2, a first scale -max / -127,
+// then the fifteen candidates id = (itry - 127) / max, itry = -7..7, the best by sumqx^2 / sumq2.
+// Roundings as the reference's x86 build performs them (gcc -O3 -mfma; the same in
+// quantize_row_iq4_nl_impl.constprop, IQ4_NL, and inlined into quantize_iq4_xs): w = x x and w q are
+// rounded products, then sumqx = fma(w q, x, sumqx) and sumq2 = fma(w q, q, sumq2); id x, sumqx sumqx,
+// best sumq2 and d sumqx are plain products. Returns 0 for an all-zero block.
+float iq4_block_scale(const float * xb) {
+    float w[32];
+    float amax = 0, max = 0;
+    for (int j = 0; j < 32; ++j) {
+        w[j] = mul_rn(xb[j], xb[j]);
+        const float ax = fabsf(xb[j]);
+        if (ax > amax) { amax = ax; max = xb[j]; }
+    }
+    if (!amax) return 0.f;
+    auto sums = [&](float id, float & sumqx, float & sumq2) {
+        sumqx = sumq2 = 0;
+        for (int j = 0; j < 32; ++j) {
+            const float q = (float) kValuesIQ4NL[iq4_best_index(mul_rn(id, xb[j]))];
+            const float wq = mul_rn(w[j], q);
+            sumqx = fmaf(wq, xb[j], sumqx);
+            sumq2 = fmaf(wq, q, sumq2);
+        }
+    };
+    float sumqx, sumq2;
+    float d = -max / (float) kValuesIQ4NL[0];
+    sums(1 / d, sumqx, sumq2);
+    d = sumqx / sumq2;
+    float best = mul_rn(d, sumqx);
+    for (int itry = -7; itry <= 7; ++itry) {
+        sums((float) (itry + kValuesIQ4NL[0]) / max, sumqx, sumq2);
+        if (sumq2 > 0 && mul_rn(sumqx, sumqx) > mul_rn(best, sumq2)) {
+            d = sumqx / sumq2;
+            best = mul_rn(d, sumqx);
+        }
+    }
+    return d;
+}
+
+// byte j of a 32-element block: index of element j | index of element 16 + j << 4
+inline void iq4_pack(const uint8_t * L, uint8_t * qs) {
+    for (int j = 0; j < 16; ++j) qs[j] = (uint8_t) (L[j] | (L[16 + j] << 4));
+}
+
+// src/ggml-quants.c:14288-14308 quantize_iq4_nl: d = fp16 of the searched scale (not re-read), the
+// indices from id = 1 / scale (0 for a zero scale: every index 8, the level 1)
+void quantize_iq4_nl_rows(const float * x, blk_iq4_nl * y, int64_t n) {
+    uint8_t L[32];
+    for (int64_t b = 0; b < n / 32; ++b, x += 32) {
+        const float scale = iq4_block_scale(x);
+        y[b].d = ggml_fp32_to_fp16(scale);
+        const float id = scale ? 1 / scale : 0.f;
+        for (int j = 0; j < 32; ++j) L[j] = (uint8_t) iq4_best_index(mul_rn(id, x[j]));
+        iq4_pack(L, y[b].qs);
+    }
+}
+
+// src/ggml-quants.c:14330-14352 quantize_iq4_xs, the second pass of quantize_row_iq4_nl_impl
+// (:14248-14270): d = -max_scale / 32 of the block scale of largest magnitude, the 6-bit
+// l = clamp(nearest_int(id scale), -32, 31) with nearest_int's product contracted into the bias add,
+// the indices from idl = 1 / (d l) with d the f32 value (0 for a zero d l), l + 32 packed: low four
+// bits in the nibbles of scales_l, upper two at bit 2 ib of scales_h. An all-zero superblock has
+// d = -0.0, l = 0: every l + 32 = 32, scales_h 0xAAAA.
+void quantize_iq4_xs_rows(const float * x, blk_iq4_xs * y, int64_t n) {
+    uint8_t L[32];
+    float scales[kQKK / 32];
+    for (int64_t b = 0; b < n / kQKK; ++b, x += kQKK) {
+        float max_scale = 0, amax_scale = 0;
+        for (int ib = 0; ib < kQKK / 32; ++ib) {
+            scales[ib] = iq4_block_scale(x + 32 * ib);
+            const float abs_d = fabsf(scales[ib]);
+            if (abs_d > amax_scale) { amax_scale = abs_d; max_scale = scales[ib]; }
+        }
+        const float d = -max_scale / 32;
+        y[b].d = ggml_fp32_to_fp16(d);
+        y[b].scales_h = 0;
+        const float id = d ? 1 / d : 0.f;
+        for (int ib = 0; ib < kQKK / 32; ++ib) {
+            int l = clampv(rne_int_fma(id, scales[ib]), -32, 31);
+            const float dl = mul_rn(d, (float) l);
+            const float idl = dl ? 1 / dl : 0.f;
+            for (int j = 0; j < 32; ++j) L[j] = (uint8_t) iq4_best_index(mul_rn(idl, x[32 * ib + j]));
+            iq4_pack(L, y[b].qs + 16 * ib);
+            l += 32;
+            if (ib % 2 == 0) y[b].scales_l[ib / 2] = (uint8_t) (l & 0xF);
+            else y[b].scales_l[ib / 2] |= (uint8_t) ((l & 0xF) << 4);
+            y[b].scales_h |= (uint16_t) ((l >> 4) << (2 * ib));
+        }
+    }
+}
+
 } // namespace
 
 extern "C" {
@@ -716,6 +828,8 @@ size_t ggml_quantize_chunk(enum ggml_type type, const float * src, void * dst, i
         case GGML_TYPE_Q4_K: quantize_q4_K_rows(in, (blk_q4_K *) out, n); break;
         case GGML_TYPE_Q5_K: quantize_q5_K_rows(in, (blk_q5_K *) out, n); break;
         case GGML_TYPE_Q6_K: quantize_q6_K_rows(in, (blk_q6_K *) out, n); break;
+        case GGML_TYPE_IQ4_NL: quantize_iq4_nl_rows(in, (blk_iq4_nl *) out, n); break;
+        case GGML_TYPE_IQ4_XS: quantize_iq4_xs_rows(in, (blk_iq4_xs *) out, n); break;
         case GGML_TYPE_F16: ggml_fp32_to_fp16_row(in, (ggml_fp16_t *) out, n); break;
         case GGML_TYPE_F32: memcpy(out, in, (size_t) n * sizeof(float)); break;
         default: GGML_ASSERT(!"ggml_quantize_chunk: type not supported by this runtime");

@@ -69,6 +69,33 @@ __device__ __forceinline__ float mi_wave_max(float v) {
 
 __device__ __forceinline__ int mi_dot4(int a, int b, int c) { return __builtin_amdgcn_sdot4(a, b, c, false); }
 
+// ---- the IQ4_NL / IQ4_XS codebook (kvalues_iq4nl, src/ggml-quants.c:3321): -127, -104, -83, -65,
+// -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113 as int8, entry i in byte i % 4 of dword i / 4
+constexpr int8_t kMiIQ4NL[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
+constexpr uint32_t kMiIQ4NL0 = 0xBFAD9881u, kMiIQ4NL1 = 0xF6EADDCFu, kMiIQ4NL2 = 0x26190D01u, kMiIQ4NL3 = 0x71594535u;
+// Four 4-bit indices, one per byte of q (upper nibbles clear), to their four int8 levels: v_perm_b32
+// picks byte sel of the eight bytes {S0, S1} (0..3: S1, 4..7: S0). One lookup of idx & 7 in entries
+// 0..7, one in entries 8..15, and a third perm that takes byte i of the second where bit 3 of
+// index i is set (selector i + 4), else of the first (selector i).
+// (q: the indices in the low nibbles of the bytes; whatever the upper nibbles hold is masked off.
+// The selector (q >> 1 & 0x04040404) | 0x03020100 is one v_and_or_b32 with its constants in
+// registers -- VOP3 takes no literals on gfx9, and left to itself the compiler emits an and and an or
+// with a literal each.)
+__device__ __forceinline__ int mi_iq4nl_levels(uint32_t q) {
+    const uint32_t i7 = q & 0x07070707u;
+    const uint32_t lo = __builtin_amdgcn_perm(kMiIQ4NL1, kMiIQ4NL0, i7);
+    const uint32_t hi = __builtin_amdgcn_perm(kMiIQ4NL3, kMiIQ4NL2, i7);
+    uint32_t sel;
+    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(sel) : "v"(q >> 1), "s"(0x04040404u), "v"(0x03020100u));
+    return (int) __builtin_amdgcn_perm(hi, lo, sel);
+}
+// the eight indices of a dword of quants: the low nibbles' levels (elements j) and the high
+// nibbles' (elements j + 16 of the 32-element block)
+__device__ __forceinline__ void mi_iq4nl_levels8(uint32_t qs, int & lo, int & hi) {
+    lo = mi_iq4nl_levels(qs);
+    hi = mi_iq4nl_levels(qs >> 4);
+}
+
 // ---- DPP wave reductions (gfx9 family: quad_perm, row_half_mirror, row_mirror, row_bcast15/31).
 // The total lands in lane 63 and is broadcast with v_readlane into an SGPR, so the result is
 // wave-uniform. The whole wave must be active (call from wave-uniform control flow).

@@ -207,7 +207,7 @@ extern thread_local int tl_mi_graph_order;
 inline int mi_mmv_order() { return g_mi_tuning.mmv_order >= 0 ? g_mi_tuning.mmv_order : tl_mi_graph_order; }
 size_t mi_mmv_fused_lds_bytes(int type, int64_t K, int64_t ncols);
 void mi_mul_mat_q_fused(mi_mmv_group & g, hipStream_t s);
-// its per-format launchers, specialized in mmv_fused_q2k.hip, _q3k, _q4k, _q5k, _q6k, _q40, _q80, _q41, _q50, _q51 (one
+// its per-format launchers, specialized in mmv_fused_q2k.hip, _q3k, _q4k, _q5k, _q6k, _q40, _q80, _q41, _q50, _q51, _iq4nl, _iq4xs (one
 // translation unit each, so that the formats build in parallel)
 template <int T> void mi_mmv_launch(const mi_mmv_group & g, int variant, hipStream_t s);
 // Batched (prefill) mul_mat on MFMA: 2-D weights [K, N] of type Q4_0/Q8_0/Q4_K/Q5_K/F16,

@@ -20,7 +20,7 @@
 // backend static_asserts each against GGML_TYPE_*). Kernel templates take them as plain ints.
 constexpr int MI_TYPE_F32 = 0, MI_TYPE_F16 = 1, MI_TYPE_Q4_0 = 2, MI_TYPE_Q4_1 = 3, MI_TYPE_Q5_0 = 6, MI_TYPE_Q5_1 = 7,
               MI_TYPE_Q8_0 = 8, MI_TYPE_Q8_1 = 9, MI_TYPE_Q2_K = 10, MI_TYPE_Q3_K = 11, MI_TYPE_Q4_K = 12, MI_TYPE_Q5_K = 13, MI_TYPE_Q6_K = 14, MI_TYPE_Q8_K = 15,
-              MI_TYPE_I32 = 26;
+              MI_TYPE_IQ4_NL = 20, MI_TYPE_IQ4_XS = 23, MI_TYPE_I32 = 26;
 
 // How the activation columns of a mul_mat are quantized: the weight type's vec_dot_type in the
 // reference (src/ggml.c type_traits). MI_ACT_NONE: F32 weights read src1 as it lies.
@@ -42,6 +42,7 @@ struct mi_type_info {
     bool has_m;        // fp16 m after d; dots with Q8_1
     bool has_qh;       // a fifth-bit plane qh[4] before the quants
     int sub;           // subtracted from every level
+    bool lut;          // the 4-bit levels index the IQ4 codebook (kvalues_iq4nl) instead of counting
     // routes
     int mmv_variant;   // streaming decode GEMV (mi_mul_mat_q_fused): its default mmv_variant, 0: no such kernel
     int mmv_align;     // ... and the weight row alignment it needs (the tensor base: 16)
@@ -62,27 +63,31 @@ struct mi_type_info {
 // (Q4_1 / Q5_0 / Q5_1: depth 2 like the other 5- and 6-dword items, not tuned: DESIGN section 14)
 // Q2_K depth 2, Q3_K depth 1 (profiles/q2k_q3k_variant_sweep.txt: no difference beyond the rounds' spread
 // at K = 4096; Q3_K 11008 x 4096 -8 % in tree order and -14 % in the reference order at depth 1)
+// IQ4_NL / IQ4_XS depth 2 (profiles/iq4_variant_sweep.txt: depths 1 to 3 alike within the rounds' spread)
 //
 // mmv_align: 16-byte rows, except Q6_K, whose 210-byte blocks its loads re-align themselves (rows
 // of an odd superblock count are 2 mod 4: K = 11008 has 9030-byte rows), and likewise Q3_K (110-byte
-// blocks: 2) and Q2_K (84-byte blocks: 4).
+// blocks: 2) and Q2_K (84-byte blocks: 4). IQ4_XS reads 8-byte words of its 136-byte blocks (rows of an
+// odd superblock count are 8 mod 16: K = 11008 has 5848-byte rows): 8.
 // planes: Q5_K has the plane format (PFmt) and its repack kernel, but no GEMM that reads them.
 constexpr mi_type_info kMiTypes[] = {
-    //  type         blck bytes act          has_m  has_qh sub  mmv  align mmqx   mmq    planes copy   get_rows
-    {MI_TYPE_F32,    1,   4,   MI_ACT_NONE, false, false, 0,   0,   16,   false, false, false, false, true},
-    {MI_TYPE_F16,    1,   2,   MI_ACT_F16,  false, false, 0,   0,   16,   false, true,  false, false, true},
-    {MI_TYPE_Q4_0,   32,  18,  MI_ACT_Q8_0, false, false, 8,   32,  16,   true,  true,  false, true,  true},
-    {MI_TYPE_Q4_1,   32,  20,  MI_ACT_Q8_1, true,  false, 0,   21,  16,   false, false, false, false, true},
-    {MI_TYPE_Q5_0,   32,  22,  MI_ACT_Q8_0, false, true,  16,  21,  16,   false, false, false, false, true},
-    {MI_TYPE_Q5_1,   32,  24,  MI_ACT_Q8_1, true,  true,  0,   21,  16,   false, false, false, false, true},
-    {MI_TYPE_Q8_0,   32,  34,  MI_ACT_Q8_0, false, false, 0,   11,  16,   true,  true,  false, true,  true},
-    {MI_TYPE_Q2_K,   256, 84,  MI_ACT_Q8_K, false, false, 0,   21,  4,    false, false, false, false, true},
-    {MI_TYPE_Q3_K,   256, 110, MI_ACT_Q8_K, false, false, 0,   11,  2,    false, false, false, false, true},
-    {MI_TYPE_Q4_K,   256, 144, MI_ACT_Q8_K, false, false, 0,   31,  16,   true,  true,  true,  false, true},
-    {MI_TYPE_Q5_K,   256, 176, MI_ACT_Q8_K, false, false, 0,   21,  16,   true,  true,  false, false, true},
-    {MI_TYPE_Q6_K,   256, 210, MI_ACT_Q8_K, false, false, 0,   21,  2,    false, false, false, false, true},
+    //  type         blck bytes act          has_m  has_qh sub  lut    mmv  align mmqx   mmq    planes copy   get_rows
+    {MI_TYPE_F32,    1,   4,   MI_ACT_NONE, false, false, 0,   false, 0,   16,   false, false, false, false, true},
+    {MI_TYPE_F16,    1,   2,   MI_ACT_F16,  false, false, 0,   false, 0,   16,   false, true,  false, false, true},
+    {MI_TYPE_Q4_0,   32,  18,  MI_ACT_Q8_0, false, false, 8,   false, 32,  16,   true,  true,  false, true,  true},
+    {MI_TYPE_Q4_1,   32,  20,  MI_ACT_Q8_1, true,  false, 0,   false, 21,  16,   false, false, false, false, true},
+    {MI_TYPE_Q5_0,   32,  22,  MI_ACT_Q8_0, false, true,  16,  false, 21,  16,   false, false, false, false, true},
+    {MI_TYPE_Q5_1,   32,  24,  MI_ACT_Q8_1, true,  true,  0,   false, 21,  16,   false, false, false, false, true},
+    {MI_TYPE_Q8_0,   32,  34,  MI_ACT_Q8_0, false, false, 0,   false, 11,  16,   true,  true,  false, true,  true},
+    {MI_TYPE_Q2_K,   256, 84,  MI_ACT_Q8_K, false, false, 0,   false, 21,  4,    false, false, false, false, true},
+    {MI_TYPE_Q3_K,   256, 110, MI_ACT_Q8_K, false, false, 0,   false, 11,  2,    false, false, false, false, true},
+    {MI_TYPE_Q4_K,   256, 144, MI_ACT_Q8_K, false, false, 0,   false, 31,  16,   true,  true,  true,  false, true},
+    {MI_TYPE_Q5_K,   256, 176, MI_ACT_Q8_K, false, false, 0,   false, 21,  16,   true,  true,  false, false, true},
+    {MI_TYPE_Q6_K,   256, 210, MI_ACT_Q8_K, false, false, 0,   false, 21,  2,    false, false, false, false, true},
+    {MI_TYPE_IQ4_NL, 32,  18,  MI_ACT_Q8_0, false, false, 0,   true,  21,  16,   false, false, false, false, true},
+    {MI_TYPE_IQ4_XS, 256, 136, MI_ACT_Q8_K, false, false, 0,   true,  21,  8,    false, false, false, false, true},
 };
-constexpr mi_type_info kMiNoType = {-1, 1, 0, MI_ACT_NONE, false, false, 0, 0, 16, false, false, false, false, false};
+constexpr mi_type_info kMiNoType = {-1, 1, 0, MI_ACT_NONE, false, false, 0, false, 0, 16, false, false, false, false, false};
 
 // the row of `type` (kMiNoType: none): a compile-time constant in kernels, a lookup on the host
 constexpr mi_type_info mi_type(int type) {
@@ -110,6 +115,8 @@ template <class F> void mi_dispatch_type(int type, F && f) {
         case MI_TYPE_Q4_K: f(mi_type_c<MI_TYPE_Q4_K>{}); break;
         case MI_TYPE_Q5_K: f(mi_type_c<MI_TYPE_Q5_K>{}); break;
         case MI_TYPE_Q6_K: f(mi_type_c<MI_TYPE_Q6_K>{}); break;
+        case MI_TYPE_IQ4_NL: f(mi_type_c<MI_TYPE_IQ4_NL>{}); break;
+        case MI_TYPE_IQ4_XS: f(mi_type_c<MI_TYPE_IQ4_XS>{}); break;
         case MI_TYPE_F16: f(mi_type_c<MI_TYPE_F16>{}); break;
         case MI_TYPE_F32: f(mi_type_c<MI_TYPE_F32>{}); break;
         default: MI_ASSERT(!"weight type outside the table");

@@ -20,6 +20,8 @@
 //   Q6_K x Q8_K  ggml_vec_dot_q6_K_q8_K  src/ggml-quants.c:8730-9310
 //   Q2_K x Q8_K  ggml_vec_dot_q2_K_q8_K  src/ggml-quants.c:5105-5169
 //   Q3_K x Q8_K  ggml_vec_dot_q3_K_q8_K  src/ggml-quants.c:6001-6103
+//   IQ4_NL x Q8_0 ggml_vec_dot_iq4_nl_q8_0 src/ggml-quants.c:11733-11815
+//   IQ4_XS x Q8_K ggml_vec_dot_iq4_xs_q8_K src/ggml-quants.c:11873-11967
 // (F16 and F32 live in mmv_ordered.hip: bit-exact CPU summation order.)
 
 #include "mi355x_common.h"
@@ -210,6 +212,8 @@ __global__ __launch_bounds__(256) void k_mmv_kq(const uint8_t * __restrict__ W, 
 // qs[j - 16]; bit j of the little-endian qh is the fifth bit of element j.
 // Values: Q4_0 (q - 8) d, Q5_0 (q - 16) d, Q4_1 / Q5_1 q d + m. Q4_1 / Q5_1 dot with Q8_1
 // activations, whose per-block s = fp16(d * sum(qs)) lies as fp16 bits in act.s32.
+// IQ4_NL (18 B: fp16 d, qs[16]) has Q4_0's geometry; its nibbles index the codebook kvalues_iq4nl
+// (LUT), value d kvalues[q], nothing subtracted.
 template <int T> struct q32_fmt {
     static constexpr bool Q8 = T == MI_TYPE_Q8_0;
     static constexpr bool HAS_M = mi_type(T).has_m;    // fp16 m after d, Q8_1 activations
@@ -218,6 +222,7 @@ template <int T> struct q32_fmt {
     static constexpr int QH = HAS_M ? 4 : 2;          // offset of qh
     static constexpr int QS = (HAS_M ? 4 : 2) + (HAS_QH ? 4 : 0);  // offset of the quants
     static constexpr int SUB = mi_type(T).sub;  // subtracted from every level
+    static constexpr bool LUT = mi_type(T).lut;  // the nibbles index the IQ4 codebook
 };
 
 // four fifth bits (bits 0..3 of x) to bit 4 of four bytes: bit b of x * 0x00204081 lands at b, b + 7,
@@ -269,8 +274,12 @@ __global__ __launch_bounds__(256) void k_mmv_q0(const uint8_t * __restrict__ W, 
             load_qs_unaligned<16>(blk + F::QS, t);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                wq[i] = (int) (t[i] & 0x0F0F0F0Fu);          // elements 4i..4i+3
-                wq[i + 4] = (int) ((t[i] >> 4) & 0x0F0F0F0Fu);  // elements 16+4i..
+                if constexpr (F::LUT) {
+                    mi_iq4nl_levels8(t[i], wq[i], wq[i + 4]);
+                } else {
+                    wq[i] = (int) (t[i] & 0x0F0F0F0Fu);          // elements 4i..4i+3
+                    wq[i + 4] = (int) ((t[i] >> 4) & 0x0F0F0F0Fu);  // elements 16+4i..
+                }
             }
             if constexpr (F::HAS_QH) {
                 uint32_t qh[1];
@@ -319,6 +328,10 @@ __global__ __launch_bounds__(256) void k_mmv_q0(const uint8_t * __restrict__ W, 
 // levels in the lanes and one scalar chain summs += fp16(x.m) * fp16(y.s) over the blocks in order
 // (the product of two fp16 values is exact in f32, so a contracted fma gives the same bits); the
 // result is hsum_float_8(acc) + summs.
+// IQ4_NL (ggml_vec_dot_iq4_nl_q8_0 :11781-11815) looks the nibbles up in the codebook and keeps two
+// accumulators: accum1 runs the chain over the even blocks, accum2 over the odd ones, and the result
+// is hsum_float_8(accum1 + accum2). It walks the blocks in pairs, so the backend takes even block
+// counts only.
 template <int NC, int T, int ID = 0>
 __global__ __launch_bounds__(256) void k_mmv_q0_ord(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
     using F = q32_fmt<T>;
@@ -350,6 +363,7 @@ __global__ __launch_bounds__(256) void k_mmv_q0_ord(const uint8_t * __restrict__
         const uint32_t * qp = (const uint32_t *) (qa & ~(uintptr_t) 3);
         uint32_t q = __builtin_amdgcn_alignbyte(qp[1], qp[0], (uint32_t) (qa & 3));
         if constexpr (!Q8) q = (l < 4 ? q : q >> 4) & 0x0F0F0F0Fu;
+        if constexpr (F::LUT) q = (uint32_t) mi_iq4nl_levels(q);
         float mw = 0.0f;
         if constexpr (F::HAS_M) mw = mi_h2f((uint16_t) ((blk & 2) ? *(const uint32_t *) (blk + 2) & 0xFFFF : dw0 >> 16));
         if constexpr (F::HAS_QH) {
@@ -366,14 +380,16 @@ __global__ __launch_bounds__(256) void k_mmv_q0_ord(const uint8_t * __restrict__
             // Q4_0: (q - 8) . y, exact (0xF8 = -8 per byte); Q5_0: (q - 16) . y (0xF0)
             constexpr int kSub = (int) (F::SUB == 16 ? 0xF0F0F0F0u : 0xF8F8F8F8u);
             const int sumi = F::SUB == 0 ? mi_dot4((int) q, av, 0) : mi_dot4((int) q, av, mi_dot4(kSub, av, 0));
-            A[c] = fmaf(dw * act.d[col * nb + b], (float) sumi, A[c]);  // _mm256_fmadd_ps, exact int -> float
+            if (F::LUT && (b & 1)) M[c] = fmaf(dw * act.d[col * nb + b], (float) sumi, M[c]);  // accum2: the odd blocks
+            else A[c] = fmaf(dw * act.d[col * nb + b], (float) sumi, A[c]);  // _mm256_fmadd_ps, exact int -> float
             if constexpr (F::HAS_M) M[c] = M[c] + mw * mi_h2f((uint16_t) act.s32[col * nb + b]);  // summs += x.m * y.s (exact product)
         }
     }
 #pragma unroll
     for (int c = 0; c < NC; c++) {
         // hsum_float_8: ((a0 + a4) + (a2 + a6)) + ((a1 + a5) + (a3 + a7))
-        float z = A[c] + __shfl_xor(A[c], 4, 8);
+        const float a = F::LUT ? A[c] + M[c] : A[c];  // IQ4_NL: _mm256_add_ps(accum1, accum2)
+        float z = a + __shfl_xor(a, 4, 8);
         z = z + __shfl_xor(z, 2, 8);
         z = z + __shfl_xor(z, 1, 8);
         if constexpr (F::HAS_M) z = z + M[c];
@@ -796,6 +812,121 @@ __global__ __launch_bounds__(256) void k_mmv_q23k_ord(const uint8_t * __restrict
     }
 }
 
+// ---------------------------------------------------------------- IQ4_XS x Q8_K
+//
+// ggml_vec_dot_iq4_xs_q8_K (src/ggml-quants.c:11873-11967). IQ4_XS (136 B): fp16 d | u16 scales_h |
+// scales_l[4] | qs[128]; sub-block ib (32 elements, quants qs[16 ib ..], element j < 16 the low
+// nibble of byte j, element 16 + j its high nibble) has the 6-bit scale ls = (nibble ib of scales_l)
+// | (bits 2 ib .. of scales_h) << 4 and the value d (ls - 32) kvalues_iq4nl[q]. Blocks are whole
+// dwords (136 = 4 * 34) of rows that start on one.
+__device__ __forceinline__ int iq4xs_scale(uint32_t sl, uint32_t sh, int ib) {
+    return (int) (((sl >> (4 * ib)) & 0xF) | (((sh >> (2 * ib)) & 3) << 4)) - 32;
+}
+
+// Tree order: item (superblock s, quarter u) = 4 s + u: the sub-blocks 2u and 2u + 1, 32 bytes of
+// quants, looked up once and used for every column. A sub-block's sum is below 32 * 127 * 127 * 32 <
+// 2^24: exact in f32.
+template <int NC, int ID = 0>
+__global__ __launch_bounds__(256) void k_mmv_iq4xs(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
+    constexpr int BS = mi_type(MI_TYPE_IQ4_XS).bytes;
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t) blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+    if (row >= g.N) return;
+    mmv_item<NC, ID> bi;
+    if (!bi.init(g)) return;
+    const uint8_t * wrow = W + bi.wofs + row * g.nb01;
+    const int nsb = (int) (g.K / 256);
+
+    float acc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) acc[c] = 0.0f;
+
+    for (int it = lane; it < 4 * nsb; it += 64) {
+        const int s = it >> 2, u = it & 3;
+        const uint32_t * blk = (const uint32_t *) (wrow + (size_t) s * BS);
+        const uint32_t h0 = blk[0], sl = blk[1];
+        const float dw = mi_h2f((uint16_t) (h0 & 0xFFFF));
+        const int ls0 = iq4xs_scale(sl, h0 >> 16, 2 * u), ls1 = iq4xs_scale(sl, h0 >> 16, 2 * u + 1);
+        int lv[16];  // [0..7] sub-block 2u (elements 4i.. in lv[i]), [8..15] sub-block 2u + 1
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            mi_iq4nl_levels8(blk[2 + 8 * u + i], lv[i], lv[4 + i]);
+            mi_iq4nl_levels8(blk[6 + 8 * u + i], lv[8 + i], lv[12 + i]);
+        }
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            if (NC > 1 && !bi.has(g, c)) break;
+            const int64_t col = bi.col(c);
+            const int4 * a = (const int4 *) (act.qs + col * g.K + (int64_t) s * 256 + 64 * u);
+            const int4 a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
+            const int av[16] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w, a3.x, a3.y, a3.z, a3.w};
+            int p0 = 0, p1 = 0;
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                p0 = mi_dot4(lv[i], av[i], p0);
+                p1 = mi_dot4(lv[8 + i], av[8 + i], p1);
+            }
+            acc[c] += (dw * act.d[col * nsb + s]) * ((float) (ls0 * p0) + (float) (ls1 * p1));
+        }
+    }
+    mmv_store<NC, ID>(g, dst, row, bi, acc, lane);
+}
+
+// Reference order, the AVX2 branch: per superblock eight int32 lanes, lane l = sum over the eight
+// sub-blocks ib of (ls_ib - 32) * sum_{e = 4l..4l+3} v[32 ib + e] a[32 ib + e] (mul_add_epi8 pairs,
+// at most 2 * 127 * 127: no saturation; madd_epi16 with the scale) -- for l < 4 the low nibbles of
+// bytes 4l.. of the sub-block, for l >= 4 the high nibbles of bytes 4(l - 4).. -- then
+// acc[l] = fma(fp16(x.d) * y.d, (float) sumi[l], acc[l]) over the superblocks and hsum_float_8. A lane
+// sum is below 8 * 4 * 127 * 127 * 32 < 2^24: exact in f32. Eight lanes are the eight CPU lanes of
+// one row (8 rows per wave), as k_mmv_q6k_ord.
+template <int NC, int ID = 0>
+__global__ __launch_bounds__(256) void k_mmv_iq4xs_ord(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
+    constexpr int BS = mi_type(MI_TYPE_IQ4_XS).bytes;
+    const int l = threadIdx.x & 7;
+    const int64_t row = (int64_t) blockIdx.x * 32 + (threadIdx.x >> 3);
+    const bool live = row < g.N;
+    const int64_t rc = live ? row : g.N - 1;  // (dead groups run a valid row: no early exit before the shuffles)
+    mmv_item<NC, ID> bi;
+    if (!bi.init(g)) return;
+    const uint8_t * wrow = W + bi.wofs + rc * g.nb01;
+    const int nsb = (int) (g.K / 256);
+
+    float A[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) A[c] = 0.0f;
+
+    for (int s = 0; s < nsb; s++) {
+        const uint32_t * blk = (const uint32_t *) (wrow + (size_t) s * BS);
+        const uint32_t h0 = blk[0], sl = blk[1];
+        const float dw = mi_h2f((uint16_t) (h0 & 0xFFFF));
+        int lv[8], sc[8];
+#pragma unroll
+        for (int ib = 0; ib < 8; ib++) {
+            const uint32_t q = blk[2 + 4 * ib + (l & 3)];
+            lv[ib] = mi_iq4nl_levels((l < 4 ? q : q >> 4) & 0x0F0F0F0Fu);
+            sc[ib] = iq4xs_scale(sl, h0 >> 16, ib);
+        }
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            if (NC > 1 && !bi.has(g, c)) break;
+            const int64_t col = bi.col(c);
+            const int8_t * aq = act.qs + col * g.K + (int64_t) s * 256;
+            int sumi = 0;
+#pragma unroll
+            for (int ib = 0; ib < 8; ib++) sumi += sc[ib] * mi_dot4(lv[ib], *(const int *) (aq + 32 * ib + 4 * l), 0);
+            A[c] = fmaf(dw * act.d[col * nsb + s], (float) sumi, A[c]);  // _mm256_fmadd_ps(d, cvt(sumi), accum)
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        // hsum_float_8: ((a0 + a4) + (a2 + a6)) + ((a1 + a5) + (a3 + a7))
+        float z = A[c] + __shfl_xor(A[c], 4, 8);
+        z = z + __shfl_xor(z, 2, 8);
+        z = z + __shfl_xor(z, 1, 8);
+        if (l == 0 && live && bi.has(g, c)) *bi.out(g, dst, row, c) = z;
+    }
+}
+
 mmv_geom make_geom(const mi_mm_desc & m, int NC) {
     mmv_geom g;
     g.K = m.K;
@@ -818,7 +949,7 @@ mmv_geom make_geom(const mi_mm_desc & m, int NC) {
 
 } // namespace
 
-// One launch of weight type T's GEMV (its family by the table: 32-element blocks, Q6_K, Q2_K / Q3_K, Q4_K / Q5_K) in
+// One launch of weight type T's GEMV (its family by the table: 32-element blocks, Q6_K, Q2_K / Q3_K, IQ4_XS, Q4_K / Q5_K) in
 // tree order (a wave per row) or the reference CPU's order (ORD: 8 rows per wave), NC columns per
 // workgroup. ID as mmv_item; grid_y 0: the column chunks of every (i12, i13) batch.
 template <int T, int NC, int ID, bool ORD>
@@ -837,6 +968,9 @@ static void mmv_launch(const mi_mm_desc & m, const mi_act_q8 & act, unsigned gri
     } else if constexpr (T == MI_TYPE_Q2_K || T == MI_TYPE_Q3_K) {
         if constexpr (ORD) hipLaunchKernelGGL((k_mmv_q23k_ord<NC, T, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
         else hipLaunchKernelGGL((k_mmv_q23k<NC, T, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
+    } else if constexpr (T == MI_TYPE_IQ4_XS) {
+        if constexpr (ORD) hipLaunchKernelGGL((k_mmv_iq4xs_ord<NC, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
+        else hipLaunchKernelGGL((k_mmv_iq4xs<NC, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
     } else {
         if constexpr (ORD) hipLaunchKernelGGL((k_mmv_kq_ord<NC, Q5, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
         else hipLaunchKernelGGL((k_mmv_kq<NC, Q5, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);

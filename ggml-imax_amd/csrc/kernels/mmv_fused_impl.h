@@ -1,6 +1,6 @@
 // mmv_fused_impl.h -- the streaming decode GEMV k_mmv_stream (see mmv_fused.hip for the design),
 // its weight-format policies and launchers. Included by one translation unit per weight format
-// (mmv_fused_q2k.hip, _q3k, _q4k, _q5k, _q6k, _q40, _q80, _q41, _q50, _q51) so that the kernel instances compile in parallel; each
+// (mmv_fused_q2k.hip, _q3k, _q4k, _q5k, _q6k, _q40, _q80, _q41, _q50, _q51, _iq4nl, _iq4xs) so that the kernel instances compile in parallel; each
 // exports one mi_mmv_launch_* entry point that mmv_fused.hip's dispatcher calls.
 #pragma once
 
@@ -386,8 +386,12 @@ struct FmtKQ {
 
 // Q4_0 (18 B) / Q8_0 (34 B) blocks: 2-byte aligned. Load the dwords covering the quants
 // (aligned down) and re-align with v_alignbyte; d is a separate 2-byte load.
-template <bool Q8>
+// LUT: IQ4_NL, Q4_0's block with the nibbles as indices into the codebook kvalues_iq4nl -- the same
+// loads; the levels come from mi_iq4nl_levels (three v_perm_b32 per four), once per block and
+// reused for every column, and nothing is subtracted. Its reference order keeps two accumulators.
+template <bool Q8, bool LUT = false>
 struct FmtQ0 {
+    static_assert(!(Q8 && LUT), "the codebook indexes nibbles");
     static constexpr bool KL = false;
     static constexpr int QKA = 32;
     static constexpr int ITEM = 32;
@@ -411,23 +415,36 @@ struct FmtQ0 {
     template <int NC>
     __device__ static __forceinline__ void dot(const Regs & r, int item, const lds_act & a, int64_t K, int ncols, float (&acc)[NC]) {
         // d = bytes off..off+1 of w[0]; the quants start at byte off + 2
-        uint32_t t[NQ];
+        uint32_t t[NL];
 #pragma unroll
         for (int i = 0; i < NQ; i++) t[i] = r.off ? r.w[i + 1] : __builtin_amdgcn_alignbyte(r.w[i + 1], r.w[i], 2);
         const uint32_t dbits = (r.off ? r.w[0] >> 16 : r.w[0]) & 0xFFFF;
         const float dw = mi_h2f((uint16_t) dbits);
+        if constexpr (LUT) levels(t);
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             if (NC > 1 && c >= ncols) break;
             const int4 * p = (const int4 *) (a.qs + c * K + (int64_t) item * 32);
             const int4 a0 = p[0], a1 = p[1];
             const int av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-            acc[c] = block_dot(t, dw, av, Q8 ? 0 : (int) a.s32[c * (K / 32) + item], a.d[c * (K / 32) + item], acc[c]);
+            acc[c] = block_dot(t, dw, av, Q8 || LUT ? 0 : (int) a.s32[c * (K / 32) + item], a.d[c * (K / 32) + item], acc[c]);
         }
     }
-    __device__ static __forceinline__ float block_dot(const uint32_t (&t)[NQ], float dw, const int (&av)[8], int s32, float da, float acc) {
+    // LUT: the four quant dwords t[0..3] to the block's eight dwords of int8 levels, t[l] = elements
+    // 4l..4l+3 (the reference's lane l)
+    static constexpr int NL = LUT ? 8 : NQ;
+    __device__ static __forceinline__ void levels(uint32_t (&t)[NL]) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            int lo, hi;
+            mi_iq4nl_levels8(t[i], lo, hi);
+            t[i] = (uint32_t) lo;
+            t[i + 4] = (uint32_t) hi;
+        }
+    }
+    __device__ static __forceinline__ float block_dot(const uint32_t (&t)[NL], float dw, const int (&av)[8], int s32, float da, float acc) {
         int sumi = 0;
-        if constexpr (Q8) {
+        if constexpr (Q8 || LUT) {
 #pragma unroll
             for (int i = 0; i < 8; i++) sumi = mi_dot4((int) t[i], av[i], sumi);
         } else {
@@ -451,28 +468,33 @@ struct FmtQ0 {
         const int av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
 #pragma unroll
         for (int i = 0; i < 8; i++) v.av[i] = av[i];
-        v.s32 = Q8 ? 0 : (int) a.s32[item];
+        v.s32 = Q8 || LUT ? 0 : (int) a.s32[item];
         v.da = a.d[item];
     }
     __device__ static __forceinline__ float dot_act(const Regs & r, int, const Act & v, float acc) {
-        uint32_t t[NQ];
+        uint32_t t[NL];
 #pragma unroll
         for (int i = 0; i < NQ; i++) t[i] = r.off ? r.w[i + 1] : __builtin_amdgcn_alignbyte(r.w[i + 1], r.w[i], 2);
         const uint32_t dbits = (r.off ? r.w[0] >> 16 : r.w[0]) & 0xFFFF;
+        if constexpr (LUT) levels(t);
         return block_dot(t, mi_h2f((uint16_t) dbits), v.av, v.s32, v.da, acc);
     }
 
     // CPU order: the reference's eight int32 lanes l of mul_sum_i8_pairs_float -- elements 4l..4l+3
     // (Q4_0: low nibbles for l < 4, high nibbles of bytes 4(l-4).. for l >= 4, minus 8) -- and
     // d = x.d * y.d, stored transposed: scratch [l][slot] (row stride 68 words), d at [8][slot].
+    // IQ4_NL (ggml_vec_dot_iq4_nl_q8_0, AVX2): the same lanes of codebook levels, nothing subtracted;
+    // the chain then runs the even blocks into accum1 (A) and the odd ones into accum2 (M), and the
+    // lanes are added before hsum_float_8.
     template <int NC>
     __device__ static __forceinline__ void dot_ord(const Regs & r, int item, int slot, const lds_act & a, int64_t K, int ncols,
                                                    uint32_t * scr, int cs, int S) {
-        uint32_t t[NQ];
+        uint32_t t[NL];
 #pragma unroll
         for (int i = 0; i < NQ; i++) t[i] = r.off ? r.w[i + 1] : __builtin_amdgcn_alignbyte(r.w[i + 1], r.w[i], 2);
         const uint32_t dbits = (r.off ? r.w[0] >> 16 : r.w[0]) & 0xFFFF;
         const float dw = mi_h2f((uint16_t) dbits);
+        if constexpr (LUT) levels(t);
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             if (NC > 1 && c >= ncols) break;
@@ -483,7 +505,7 @@ struct FmtQ0 {
 #pragma unroll
             for (int l = 0; l < 8; l++) {
                 int q;
-                if constexpr (Q8) {
+                if constexpr (Q8 || LUT) {
                     q = mi_dot4((int) t[l], av[l], 0);
                 } else {
                     const uint32_t nib = l < 4 ? (t[l] & 0x0F0F0F0Fu) : ((t[l - 4] >> 4) & 0x0F0F0F0Fu);
@@ -500,6 +522,22 @@ struct FmtQ0 {
         const float * q = (const float *) scr + l * S;
         const float * d = (const float *) scr + 8 * S;
         int i = 0;
+        if constexpr (LUT) {
+            // (every chunk of a row starts at an even block: the scratch slot's parity is the block's)
+            for (; i + 4 <= n_items; i += 4) {
+                const float4 qq = *(const float4 *) (q + i);
+                const float4 dd = *(const float4 *) (d + i);
+                A = fmaf(dd.x, qq.x, A);
+                M = fmaf(dd.y, qq.y, M);
+                A = fmaf(dd.z, qq.z, A);
+                M = fmaf(dd.w, qq.w, M);
+            }
+            for (; i < n_items; i++) {
+                if (i & 1) M = fmaf(d[i], q[i], M);
+                else A = fmaf(d[i], q[i], A);
+            }
+            return;
+        }
         for (; i + 4 <= n_items; i += 4) {
             const float4 qq = *(const float4 *) (q + i);
             const float4 dd = *(const float4 *) (d + i);
@@ -518,13 +556,15 @@ struct FmtQ0 {
         stride = S;
         return 9 * S;
     }
-    __device__ static __forceinline__ float finish(float A, float) {
+    __device__ static __forceinline__ float finish(float A, float M) {
+        if constexpr (LUT) A = A + M;  // _mm256_add_ps(accum1, accum2)
         // hsum_float_8: ((a0 + a4) + (a2 + a6)) + ((a1 + a5) + (a3 + a7))
         float z = A + __shfl_xor(A, 4, 8);
         z = z + __shfl_xor(z, 2, 8);
         return z + __shfl_xor(z, 1, 8);
     }
 };
+using FmtIQ4NL = FmtQ0<false, true>;
 
 // Q4_1 (20 B: fp16 d, m, qs[16]), Q5_0 (22 B: fp16 d, qh[4], qs[16]) and Q5_1 (24 B:
 // fp16 d, m, qh[4], qs[16]) blocks of 32. Element j < 16 is the low nibble of qs[j], element j >= 16
@@ -1297,6 +1337,153 @@ struct FmtQ23K {
 };
 using FmtQ2K = FmtQ23K<false>;
 using FmtQ3K = FmtQ23K<true>;
+
+// IQ4_XS (136 B superblocks: fp16 d | u16 scales_h | scales_l[4] | qs[128]; sub-block ib of 32
+// elements has its quants at qs[16 ib ..], element j < 16 the low nibble of byte j and element 16 + j
+// its high nibble, both indices into kvalues_iq4nl, and the 6-bit scale ls = nibble ib of scales_l |
+// bits 2 ib.. of scales_h << 4; element value d (ls - 32) kvalues[q]). Item (superblock s, quarter u),
+// item = 4 s + u: the 8-byte header and qs[32u .. 32u + 31], i.e. the sub-blocks 2u and 2u + 1 and 64
+// activations. Four items per superblock on adjacent lanes; a K = 4096 row is one item per lane.
+// Loads: blocks are 8-byte aligned wherever the row lies (136 = 8 * 17; rows of an odd superblock
+// count are 8 mod 16, K = 11008: 5848 bytes), so the item is five aligned 8-byte words of its own
+// block: nothing is read outside the block.
+// The levels are looked up once per item (mi_iq4nl_levels) and used for every column.
+struct FmtIQ4XS {
+    static constexpr bool KL = false;
+    static constexpr int QKA = 256;
+    static constexpr int ITEM = 64;
+    static constexpr int BS = mi_type(MI_TYPE_IQ4_XS).bytes;
+    static constexpr int E = 16;  // scratch words per superblock in the reference order
+    struct Regs {
+        uint2 hdr;   // d | scales_h << 16, scales_l
+        uint2 q[4];  // the 32 quant bytes
+    };
+    __device__ static __forceinline__ void load(Regs & r, const uint8_t * row, int item) {
+        const uint32_t s = (uint32_t) item >> 2, u = (uint32_t) item & 3;
+        const uint8_t * p = row + s * BS;
+        r.hdr = *(const uint2 *) p;
+#pragma unroll
+        for (int i = 0; i < 4; i++) r.q[i] = *(const uint2 *) (p + 8 + 32 * u + 8 * i);
+    }
+    // the item's operands: lv[0..7] the levels of sub-block 2u (lv[l]: its elements 4l..4l+3, the
+    // reference's lane l), lv[8..15] those of sub-block 2u + 1, their scales minus 32, the block's d
+    struct Dec {
+        int lv[16];
+        int ls0, ls1;
+        float dw;
+    };
+    __device__ static __forceinline__ void decode(Dec & d, const Regs & r, int item) {
+        const uint32_t u = (uint32_t) item & 3;
+        const uint32_t sh = r.hdr.x >> (16 + 4 * u), sl = r.hdr.y >> (8 * u);
+        d.dw = mi_h2f((uint16_t) (r.hdr.x & 0xFFFF));
+        d.ls0 = (int) ((sl & 0xF) | ((sh & 3) << 4)) - 32;
+        d.ls1 = (int) (((sl >> 4) & 0xF) | (((sh >> 2) & 3) << 4)) - 32;
+        const uint32_t q[8] = {r.q[0].x, r.q[0].y, r.q[1].x, r.q[1].y, r.q[2].x, r.q[2].y, r.q[3].x, r.q[3].y};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            mi_iq4nl_levels8(q[i], d.lv[i], d.lv[4 + i]);
+            mi_iq4nl_levels8(q[4 + i], d.lv[8 + i], d.lv[12 + i]);
+        }
+    }
+    // the item's 64 quantized activations of one column
+    __device__ static __forceinline__ void act16(int (&av)[16], const int8_t * qs, int item) {
+        const int4 * p = (const int4 *) (qs + (int64_t) (item >> 2) * 256 + 64 * (item & 3));
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int4 a = p[t];
+            av[4 * t] = a.x; av[4 * t + 1] = a.y; av[4 * t + 2] = a.z; av[4 * t + 3] = a.w;
+        }
+    }
+    // a sub-block's scaled sum is below 32 * 127 * 127 * 32 < 2^24: exact in f32
+    __device__ static __forceinline__ float item_dot(const Dec & d, const int (&av)[16], float ad, float acc) {
+        int p0 = 0, p1 = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            p0 = mi_dot4(d.lv[i], av[i], p0);
+            p1 = mi_dot4(d.lv[8 + i], av[8 + i], p1);
+        }
+        // explicit fmas (the file contracts freely): the same bits in every kernel that inlines this
+        const float dd = d.dw * ad;
+        return fmaf((float) (d.ls1 * p1), dd, fmaf((float) (d.ls0 * p0), dd, acc));
+    }
+    template <int NC>
+    __device__ static __forceinline__ void dot(const Regs & r, int item, const lds_act & a, int64_t K, int ncols, float (&acc)[NC]) {
+        Dec d;
+        decode(d, r, item);
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            if (NC > 1 && c >= ncols) break;
+            int av[16];
+            act16(av, a.qs + c * K, item);
+            acc[c] = item_dot(d, av, a.d[c * (K / 256) + (item >> 2)], acc[c]);
+        }
+    }
+    struct Act {
+        int av[16];
+        float ad;
+    };
+    __device__ static __forceinline__ void act_load(Act & v, int item, const lds_act & a, int64_t) {
+        act16(v.av, a.qs, item);
+        v.ad = a.d[item >> 2];
+    }
+    __device__ static __forceinline__ float dot_act(const Regs & r, int item, const Act & v, float acc) {
+        Dec d;
+        decode(d, r, item);
+        return item_dot(d, v.av, v.ad, acc);
+    }
+
+    // CPU order (ggml_vec_dot_iq4_xs_q8_K, AVX2): eight int32 lanes per superblock, lane l = sum over
+    // the eight sub-blocks ib of (ls_ib - 32) * sum_{e = 4l..4l+3} v[32 ib + e] a[32 ib + e], then
+    // acc[l] = fma(fp16(x.d) * y.d, (float) sumi[l], acc[l]) over the superblocks and hsum_float_8.
+    // Item u holds the sub-blocks 2u and 2u + 1 whole, i.e. its share of all eight lanes; the four
+    // items of the quad add up to the lane totals (below 8 * 4 * 127 * 127 * 32 < 2^24: exact as
+    // floats). Entry of superblock sb in the scratch, E words: [0..7] the sums, [12] d (FmtKQ's slot).
+    template <int NC>
+    __device__ static __forceinline__ void dot_ord(const Regs & r, int item, int slot, const lds_act & a, int64_t K, int ncols,
+                                                   uint32_t * scr, int cs, int) {
+        const int u = item & 3;
+        Dec d;
+        decode(d, r, item);
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            if (NC > 1 && c >= ncols) break;
+            int av[16];
+            act16(av, a.qs + c * K, item);
+            int v[8];
+#pragma unroll
+            for (int l = 0; l < 8; l++) {
+                v[l] = d.ls0 * mi_dot4(d.lv[l], av[l], 0) + d.ls1 * mi_dot4(d.lv[8 + l], av[8 + l], 0);
+                v[l] += mi_dpp<MI_DPP_QP_1032>(0, v[l]);  // the quad's other three items (rows are whole
+                v[l] += mi_dpp<MI_DPP_QP_2301>(0, v[l]);  // superblocks: a quad is active as one)
+            }
+            uint32_t * e = scr + c * cs + (slot >> 2) * E;
+            if (u == 0) {
+                *(uint4 *) e = make_uint4(__float_as_uint((float) v[0]), __float_as_uint((float) v[1]),
+                                          __float_as_uint((float) v[2]), __float_as_uint((float) v[3]));
+            } else if (u == 1) {
+                *(uint4 *) (e + 4) = make_uint4(__float_as_uint((float) v[4]), __float_as_uint((float) v[5]),
+                                                __float_as_uint((float) v[6]), __float_as_uint((float) v[7]));
+            } else if (u == 2) {
+                e[12] = __float_as_uint(d.dw * a.d[c * (K / 256) + (item >> 2)]);
+            }
+        }
+    }
+    __device__ static __forceinline__ void chain(const uint32_t * scr, int l, int n_items, int, float & A, float &) {
+        const float * e = (const float *) scr;
+        const int nsb = n_items >> 2;
+        for (int sb = 0; sb < nsb; sb++, e += E) A = fmaf(e[12], e[l], A);
+    }
+    static int ord_words(int nitems, int & stride) {
+        stride = 0;
+        return E * (nitems / 4) + 8;
+    }
+    __device__ static __forceinline__ float finish(float A, float) {
+        // hsum_float_8: ((a0 + a4) + (a2 + a6)) + ((a1 + a5) + (a3 + a7))
+        float z = A + __shfl_xor(A, 4, 8);
+        z = z + __shfl_xor(z, 2, 8);
+        return z + __shfl_xor(z, 1, 8);
+    }
+};
 
 // a format's weight load (FmtQ0R's needs the row length)
 template <class F>

@@ -2,7 +2,7 @@
 //
 // All are memory- or launch-bound. Each follows the reference CPU forward's rounding sequence so
 // that results are bit-identical where the CPU order is reproducible:
-//   get_rows   src/ggml.c:12920 (f16) / :13006 (f32) / :12874 (Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K .. Q6_K) -- exact
+//   get_rows   src/ggml.c:12920 (f16) / :13006 (f32) / :12874 (Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K .. Q6_K, IQ4_NL, IQ4_XS) -- exact
 //   add / mul  src/ggml.c:8568 / :9687 (broadcast src1)      -- exact
 //   scale      src/ggml.c:12637                              -- exact
 //   norm       src/ggml.c:11353-11406 (double sums)          -- sums in double, then the same f32 ops
@@ -157,6 +157,26 @@ __device__ __forceinline__ float dequant_elem(const uint8_t * row, int64_t c) {
         } else {
             return (float) (int8_t) blk[2 + j] * d;
         }
+    } else if constexpr (TYPE == MI_TYPE_IQ4_NL) {  // IQ4_NL (18 B) blocks of 32: fp16 d, qs[16] of codebook indices
+        // dequantize_row_iq4_nl (:3323-3339): d * kvalues_iq4nl[index], one multiply
+        const uint8_t * blk = row + (c >> 5) * BS;
+        const int j = (int) (c & 31);
+        uint16_t dh;
+        __builtin_memcpy(&dh, blk, 2);
+        const uint8_t b = blk[2 + (j & 15)];
+        return mul_rn(mi_h2f(dh), (float) kMiIQ4NL[j < 16 ? (b & 0x0F) : (b >> 4)]);
+    } else if constexpr (TYPE == MI_TYPE_IQ4_XS) {  // IQ4_XS (136 B) superblocks: fp16 d, u16 scales_h, scales_l[4], qs[128]
+        // dequantize_row_iq4_xs (:3341-3366): (d * (ls - 32)) * kvalues_iq4nl[index], two separately
+        // rounded multiplies; the signs of zeros included (an all-zero superblock has d = -0.0 and
+        // ls = 32: every element -0.0 * 0 * 1 = -0.0)
+        const uint8_t * blk = row + (c >> 8) * BS;
+        const int e = (int) (c & 255), ib = e >> 5, j = e & 31;
+        uint16_t dh, sh;
+        __builtin_memcpy(&dh, blk, 2);
+        __builtin_memcpy(&sh, blk + 2, 2);
+        const int ls = ((blk[4 + (ib >> 1)] >> (4 * (ib & 1))) & 0xF) | (((sh >> (2 * ib)) & 3) << 4);
+        const uint8_t b = blk[8 + 16 * ib + (j & 15)];
+        return mul_rn(mul_rn(mi_h2f(dh), (float) (ls - 32)), (float) kMiIQ4NL[j < 16 ? (b & 0x0F) : (b >> 4)]);
     } else if constexpr (I.blck == 32) {
         // Q4_1 (20 B: fp16 d, m, qs[16]) / Q5_0 (22 B: fp16 d, qh[4], qs[16]) / Q5_1 (24 B: fp16 d, m,
         // qh[4], qs[16]) blocks of 32: dequantize_row_q4_1 / _q5_0 / _q5_1 (src/ggml-quants.c:1000-1072),

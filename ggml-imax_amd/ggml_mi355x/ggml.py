@@ -29,11 +29,13 @@ GGML_TYPE_F32, GGML_TYPE_F16, GGML_TYPE_Q4_0, GGML_TYPE_Q8_0 = 0, 1, 2, 8
 GGML_TYPE_Q4_K, GGML_TYPE_Q5_K, GGML_TYPE_Q8_K, GGML_TYPE_I32 = 12, 13, 15, 26
 GGML_TYPE_Q6_K = 14
 GGML_TYPE_Q2_K, GGML_TYPE_Q3_K = 10, 11
+GGML_TYPE_IQ4_NL, GGML_TYPE_IQ4_XS = 20, 23
 GGML_TYPE_Q4_1, GGML_TYPE_Q5_0, GGML_TYPE_Q5_1, GGML_TYPE_Q8_1 = 3, 6, 7, 9
 TYPE_BY_NAME = {"f32": 0, "f16": 1, "q4_0": 2, "q4_1": 3, "q5_0": 6, "q5_1": 7, "q8_0": 8, "q8_1": 9, "q2_K": 10, "q3_K": 11,
-                "q4_K": 12, "q5_K": 13, "q6_K": 14, "i32": 26}
+                "q4_K": 12, "q5_K": 13, "q6_K": 14, "iq4_nl": 20, "iq4_xs": 23, "i32": 26}
 BLOCK = {0: (1, 4), 1: (1, 2), 2: (32, 18), 3: (32, 20), 6: (32, 22), 7: (32, 24), 8: (32, 34), 9: (32, 36), 10: (256, 84),
-         11: (256, 110), 12: (256, 144), 13: (256, 176), 14: (256, 210), 26: (1, 4)}
+         11: (256, 110), 12: (256, 144), 13: (256, 176), 14: (256, 210), 20: (32, 18), 23: (256, 136),
+         26: (1, 4)}
 
 GGML_OP_MUL_MAT = 23
 GGML_OP_FLASH_ATTN_EXT = 56
@@ -139,6 +141,9 @@ _SIGS = {
     "ggml_build_forward_expand": ([POINTER(ggml_cgraph), T], None),
     "ggml_graph_print": ([POINTER(ggml_cgraph)], None),
     "ggml_quantize_chunk": ([c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p], c_size_t),
+    "ggml_quantize_requires_imatrix": ([c_int], c_bool),
+    "ggml_is_quantized": ([c_int], c_bool),
+    "ggml_ftype_to_ggml_type": ([c_int], c_int),
     "ggml_fp32_to_fp16": ([c_float], ctypes.c_uint16),
     "ggml_fp16_to_fp32": ([ctypes.c_uint16], c_float),
     # GGUF (include/ggml/ggml.h:2247-2380)
