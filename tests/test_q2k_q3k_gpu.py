@@ -5,553 +5,112 @@ and GGUF loading.
 
 The reference is the reference CPU backend itself (oracle/_ref/libggml_ref.so, loaded isolated
 beside the runtime) on identical inputs, or the committed fixtures tests/golden/q2k_*, q3k_* where
-those suffice. All the assertions are path-agnostic: they hold whichever kernel serves a shape.
+those suffice. The bodies are the check_* functions of tests/weight_types.py, run on the table's
+Q2_K and Q3_K rows.
 """
-import ctypes
-import functools
-import json
 import os
-import subprocess
 
-os.environ.setdefault("GGML_MI355X_SPLIT_SLOTS", "3")  # read once, at the first split buffer type (as tests/test_split_gpu.py)
-
-import numpy as np
 import pytest
 
-from conftest import GOLDEN, REPO, golden_blob
-from ggml_mi355x import ggml as G
-from ggml_mi355x import gguf
-from ggml_mi355x import gpt2
-from ggml_mi355x import synth
+import weight_types as W
+from weight_types import REF_GPT2, REF_QUANTIZE, needs_ref
+from weight_types import backend, ref, rt, tiny_models  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-REF = os.path.join(REPO, "oracle", "_ref")
-REF_LIB = os.path.join(REF, "libggml_ref.so")
-REF_GPT2 = os.path.join(REF, "libgpt2_ref.so")
-REF_QUANTIZE = os.path.join(REF, "gpt-2-quantize")
-needs_ref = pytest.mark.skipif(not os.path.exists(REF_LIB), reason="reference lib not built (make -C oracle ref)")
-Q2_K, Q3_K, Q8_K = 10, 11, 15
-TAG = {Q2_K: "q2k", Q3_K: "q3k"}
-FTYPE = {Q2_K: "q2_k", Q3_K: "q3_k"}
-both_types = pytest.mark.parametrize("T", [Q2_K, Q3_K], ids=lambda t: TAG[t])
-TREE_TOL = 1e-5  # integer block sums are exact: only the f32 combination order differs
+ROWS = W.rows("q2k_q3k")
+both_types = pytest.mark.parametrize("wt", ROWS, ids=lambda wt: wt.tag)
 
-with open(os.path.join(GOLDEN, "q2k_q3k.json")) as _f:
-    MANIFEST = json.load(_f)
-
-
-@pytest.fixture(scope="module")
-def rt():
-    return G.runtime()
-
-
-@pytest.fixture(scope="module")
-def backend(rt):
-    b = G.mi355x_backend(rt, 0)
-    yield b
-    rt.ggml_backend_free(b)
-
-
-@pytest.fixture(scope="module")
-def ref():
-    lib = G.Lib([REF_LIB], isolated=True)
-    cpu = lib.ggml_backend_cpu_init()
-    yield lib, cpu
-    lib.ggml_backend_free(cpu)
-
-
-def rel_err(y, r):
-    return float(np.abs(y.astype(np.float64) - r).max() / max(np.abs(r).max(), 1e-30))
-
-
-def same_bits(y, r):
-    return np.array_equal(y.view(np.uint32), r.view(np.uint32))
-
-
-def in_order(rt, order, fn):
-    assert rt.ggml_backend_mi355x_set_tuning(b"mmv_order", order)
-    try:
-        return fn()
-    finally:
-        rt.ggml_backend_mi355x_set_tuning(b"mmv_order", -1)
-
-
-@functools.lru_cache(maxsize=None)
-def weights(T, K, N, seed):
-    """Seeded rows of type T from the runtime's quantizer (tests/test_q2k_q3k.py pins it to the reference's bytes)."""
-    rt = G.runtime()
-    w = np.random.default_rng(seed).standard_normal(K * N).astype(np.float32)
-    out = np.empty(G.row_size(T, K) * N, np.uint8)
-    assert rt.ggml_quantize_chunk(T, w.ctypes.data, out.ctypes.data, 0, N, K, None) == out.nbytes
-    out.setflags(write=False)
-    return out
-
-
-# ------------------------------------------------------------------ GET_ROWS
 
 @both_types
 @pytest.mark.parametrize("which", ["w", "edge"])
-def test_get_rows_matches_golden_dequantization(rt, backend, T, which):
-    """Row indices out of order and repeated, f32 dst: dequantize_row_q2_K's / _q3_K's bits."""
-    K, N = MANIFEST[which]["K"], MANIFEST[which]["N"]
-    wq = golden_blob(f"{TAG[T]}_{which}.wq.bin")
-    want = golden_blob(f"{TAG[T]}_{which}.wdq.f32", np.float32).reshape(N, K)
-    idx = np.array([N - 1, 0, 2, 2, 1, N - 1, 3, 0, N - 2], np.int32)
+def test_get_rows_matches_golden_dequantization(rt, backend, wt, which):
+    W.check_get_rows_matches_golden_dequantization(rt, backend, wt, which)
 
-    def build(c):
-        w = rt.ggml_new_tensor_2d(c, T, K, N)
-        i = rt.ggml_new_tensor_1d(c, G.GGML_TYPE_I32, len(idx))
-        return [(w, wq), (i, idx)], rt.ggml_get_rows(c, w, i)
-
-    y = G.graph_once(rt, backend, build).reshape(len(idx), K)
-    assert same_bits(y, want[idx]), float(np.abs(y - want[idx]).max())
-
-
-# ------------------------------------------------------------------ MUL_MAT
 
 @both_types
-def test_mul_mat_matches_golden_output(rt, backend, T):
-    """The committed reference-CPU output (B = 3): identical bits in order 1, 1e-5 in tree order."""
-    c = MANIFEST["w"]
-    K, N, B = c["K"], c["N"], c["B"]
-    wq = golden_blob(f"{TAG[T]}_w.wq.bin")
-    x = synth.uniform(c["xseed"], K * B)
-    want = golden_blob(f"{TAG[T]}_w.y.f32", np.float32)
-    y1 = in_order(rt, 1, lambda: G.mul_mat_once(rt, backend, T, wq, K, N, x, B))
-    y0 = in_order(rt, 0, lambda: G.mul_mat_once(rt, backend, T, wq, K, N, x, B))
-    print(f"golden {TAG[T]} B={B}: order 1 rel err {rel_err(y1, want):.2e}, tree order {rel_err(y0, want):.2e}")
-    assert same_bits(y1, want), rel_err(y1, want)
-    assert rel_err(y0, want) <= TREE_TOL
-
-
-# rows that are 2 mod 4 (Q3_K) or 4-byte-only aligned (Q2_K) with the odd superblock counts 1, 3, 11;
-# under one / exactly one / one and a half items per lane of a wave (K 2048 / 4096 / 6144), N not a
-# multiple of 4 or of the rows per workgroup, 1..8 columns in one launch, the 4-column split,
-# 8-column chunks with a ragged tail
-SHAPES = [(256, 5), (768, 67), (2048, 67), (2816, 33), (4096, 67), (6144, 9)]
-COLS = [1, 2, 3, 5, 8, 9, 17]
-
-
-@functools.lru_cache(maxsize=None)
-def _ref_mul_mat(T, K, N, B):
-    lib = G.Lib([REF_LIB], isolated=True)
-    cpu = lib.ggml_backend_cpu_init()
-    try:
-        y = G.mul_mat_once(lib, cpu, T, weights(T, K, N, 100 + K + N), K, N, synth.uniform(200 + K + B, K * B), B)
-    finally:
-        lib.ggml_backend_free(cpu)
-    y.setflags(write=False)
-    return y
+def test_mul_mat_matches_golden_output(rt, backend, wt):
+    W.check_mul_mat_matches_golden_output(rt, backend, wt)
 
 
 @needs_ref
 @both_types
-@pytest.mark.parametrize("K,N", SHAPES)
-def test_mul_mat_reference_order_bit_identical(rt, backend, T, K, N):
-    wq = weights(T, K, N, 100 + K + N)
-    for B in COLS:
-        x = synth.uniform(200 + K + B, K * B)
-        y = in_order(rt, 1, lambda: G.mul_mat_once(rt, backend, T, wq, K, N, x, B))
-        yr = _ref_mul_mat(T, K, N, B)
-        assert same_bits(y, yr), (B, float(np.mean(y.view(np.uint32) == yr.view(np.uint32))), rel_err(y, yr))
+@pytest.mark.parametrize("K,N", ROWS[0].shapes)
+def test_mul_mat_reference_order_bit_identical(rt, backend, wt, K, N):
+    W.check_mul_mat_reference_order_bit_identical(rt, backend, wt, (K, N))
 
 
 @needs_ref
 @both_types
-@pytest.mark.parametrize("K,N", SHAPES)
-def test_mul_mat_tree_order(rt, backend, T, K, N):
-    wq = weights(T, K, N, 100 + K + N)
-    for B in COLS:
-        x = synth.uniform(200 + K + B, K * B)
-        y = in_order(rt, 0, lambda: G.mul_mat_once(rt, backend, T, wq, K, N, x, B))
-        err = rel_err(y, _ref_mul_mat(T, K, N, B))
-        print(f"tree order {TAG[T]} K={K} N={N} B={B}: rel err {err:.2e}")
-        assert err <= TREE_TOL, (B, err)
+@pytest.mark.parametrize("K,N", ROWS[0].shapes)
+def test_mul_mat_tree_order(rt, backend, wt, K, N):
+    W.check_mul_mat_tree_order(rt, backend, wt, (K, N))
 
 
 @needs_ref
 @both_types
-def test_mul_mat_llama_ffn_down_rows(rt, backend, ref, T):
-    """K = 11008 (LLaMA-7B's ffn_down): 43 superblocks, 3612-byte (Q2_K: 4 mod 16) and 4730-byte
-    (Q3_K: every other row starts 2 mod 4) rows, 172 items per row, more than two per lane. Decode
-    and prompt column counts."""
-    lib, cpu = ref
-    K, N = 11008, 10
-    wq = weights(T, K, N, 801)
-    for B in (1, 3, 8, 9):
-        x = synth.uniform(802 + B, K * B)
-        yr = G.mul_mat_once(lib, cpu, T, wq, K, N, x, B)
-        y1 = in_order(rt, 1, lambda: G.mul_mat_once(rt, backend, T, wq, K, N, x, B))
-        y0 = in_order(rt, 0, lambda: G.mul_mat_once(rt, backend, T, wq, K, N, x, B))
-        assert same_bits(y1, yr), (B, rel_err(y1, yr))
-        assert rel_err(y0, yr) <= TREE_TOL, (B, rel_err(y0, yr))
-
-
-def _mul_mat_general(lib, backend, T, wq, w_ne, x, x_ne, permute_x):
-    """W [K, N, ne02, 1] x X [K, ne11, ne12, 1] with broadcasting; permute_x: X stored as
-    [K, ne12, ne11] and permuted, so that src1's columns are strided."""
-    ovh = lib.ggml_tensor_overhead() * 16 + lib.ggml_graph_overhead()
-    with G.Context(lib, ovh, no_alloc=True) as c:
-        w = lib.ggml_new_tensor_4d(c.ctx, T, *w_ne)
-        if permute_x:
-            xs = lib.ggml_new_tensor_4d(c.ctx, G.GGML_TYPE_F32, x_ne[0], x_ne[2], x_ne[1], x_ne[3])
-            xt = lib.ggml_permute(c.ctx, xs, 0, 2, 1, 3)
-        else:
-            xs = xt = lib.ggml_new_tensor_4d(c.ctx, G.GGML_TYPE_F32, *x_ne)
-        y = lib.ggml_mul_mat(c.ctx, w, xt)
-        g = lib.ggml_new_graph(c.ctx)
-        lib.ggml_build_forward_expand(g, y)
-        buf = lib.ggml_backend_alloc_ctx_tensors(c.ctx, backend)
-        try:
-            G.tensor_set(lib, w, wq)
-            G.tensor_set(lib, xs, x)
-            assert lib.ggml_backend_graph_compute(backend, g) == 0
-            return G.tensor_get(lib, y)
-        finally:
-            lib.ggml_backend_buffer_free(buf)
+def test_mul_mat_llama_ffn_down_rows(rt, backend, ref, wt):
+    W.check_mul_mat_llama_ffn_down_rows(rt, backend, ref, wt)
 
 
 @needs_ref
 @both_types
 @pytest.mark.parametrize("ne11", [1, 3, 9])
-def test_weight_batch_and_strided_src1(rt, backend, ref, T, ne11):
-    """A 3-D weight batch (ne02 = 2) broadcast over ne12 = 4, contiguous and strided src1."""
-    lib, cpu = ref
-    K, N, ne02, ne12 = 768, 40, 2, 4  # three superblocks: Q3_K rows 2 mod 4
-    w_ne, x_ne = (K, N, ne02, 1), (K, ne11, ne12, 1)
-    wq = weights(T, K, N * ne02, 301)
-    x = synth.uniform(302 + ne11, K * ne11 * ne12)
-    for permute in (False, True):
-        yr = _mul_mat_general(lib, cpu, T, wq, w_ne, x, x_ne, permute)
-        y1 = in_order(rt, 1, lambda: _mul_mat_general(rt, backend, T, wq, w_ne, x, x_ne, permute))
-        y0 = in_order(rt, 0, lambda: _mul_mat_general(rt, backend, T, wq, w_ne, x, x_ne, permute))
-        assert same_bits(y1, yr), (permute, rel_err(y1, yr))
-        assert rel_err(y0, yr) <= TREE_TOL, (permute, rel_err(y0, yr))
-
-
-def _cpy_q8k_then_mul_mat(lib, backend, T, wq, K, N, x, B):
-    """X (f32) -> CPY to Q8_K rows -> MUL_MAT(W, Xq) as one graph: src1 already of the vec_dot type."""
-    overhead = lib.ggml_tensor_overhead() * 8 + lib.ggml_graph_overhead()
-    with G.Context(lib, overhead, no_alloc=True) as c:
-        w = lib.ggml_new_tensor_2d(c.ctx, T, K, N)
-        xt = lib.ggml_new_tensor_2d(c.ctx, G.GGML_TYPE_F32, K, B)
-        xq = lib.ggml_cpy(c.ctx, xt, lib.ggml_new_tensor_2d(c.ctx, Q8_K, K, B))
-        y = lib.ggml_mul_mat(c.ctx, w, xq)
-        g = lib.ggml_new_graph(c.ctx)
-        lib.ggml_build_forward_expand(g, y)
-        buf = lib.ggml_backend_alloc_ctx_tensors(c.ctx, backend)
-        assert buf
-        try:
-            G.tensor_set(lib, w, wq)
-            G.tensor_set(lib, xt, x)
-            assert lib.ggml_backend_graph_compute(backend, g) == G.GGML_STATUS_SUCCESS
-            return G.tensor_get(lib, y)
-        finally:
-            lib.ggml_backend_buffer_free(buf)
+def test_weight_batch_and_strided_src1(rt, backend, ref, wt, ne11):
+    W.check_weight_batch_and_strided_src1(rt, backend, ref, wt, ne11)
 
 
 @needs_ref
 @both_types
-@pytest.mark.parametrize("B", [4, 20])
-def test_prequantized_q8k_src1(rt, backend, ref, T, B):
-    lib, cpu = ref
-    K, N = 1024, 48
-    wq = weights(T, K, N, 401)
-    x = synth.uniform(402 + B, K * B)
-    yr = _cpy_q8k_then_mul_mat(lib, cpu, T, wq, K, N, x, B)
-    y1 = in_order(rt, 1, lambda: _cpy_q8k_then_mul_mat(rt, backend, T, wq, K, N, x, B))
-    y0 = in_order(rt, 0, lambda: _cpy_q8k_then_mul_mat(rt, backend, T, wq, K, N, x, B))
-    yf = in_order(rt, 1, lambda: G.mul_mat_once(rt, backend, T, wq, K, N, x, B))
-    assert same_bits(y1, yr), rel_err(y1, yr)
-    assert rel_err(y0, yr) <= TREE_TOL, rel_err(y0, yr)
-    assert same_bits(y1, yf), rel_err(y1, yf)  # the same quants either way: the F32-src1 path's bits
-
-
-def _three_mul_mats(lib, backend, T, wqs, K, N, xs):
-    """Three independent same-shape mul_mats (B = 1) in one graph."""
-    overhead = lib.ggml_tensor_overhead() * 16 + lib.ggml_graph_overhead()
-    with G.Context(lib, overhead, no_alloc=True) as c:
-        ws = [lib.ggml_new_tensor_2d(c.ctx, T, K, N) for _ in wqs]
-        xts = [lib.ggml_new_tensor_2d(c.ctx, G.GGML_TYPE_F32, K, 1) for _ in xs]
-        ys = [lib.ggml_mul_mat(c.ctx, w, x) for w, x in zip(ws, xts)]
-        g = lib.ggml_new_graph(c.ctx)
-        for y in ys:
-            lib.ggml_build_forward_expand(g, y)
-        buf = lib.ggml_backend_alloc_ctx_tensors(c.ctx, backend)
-        assert buf
-        try:
-            for t, a in list(zip(ws, wqs)) + list(zip(xts, xs)):
-                G.tensor_set(lib, t, a)
-            assert lib.ggml_backend_graph_compute(backend, g) == G.GGML_STATUS_SUCCESS
-            return [G.tensor_get(lib, y) for y in ys]
-        finally:
-            lib.ggml_backend_buffer_free(buf)
+@pytest.mark.parametrize("B", ROWS[0].prequant_B)
+def test_prequantized_q8k_src1(rt, backend, ref, wt, B):
+    W.check_prequantized_src1(rt, backend, ref, wt, B)
 
 
 @needs_ref
 @both_types
-def test_three_independent_mul_mats_in_one_graph(rt, backend, ref, T):
-    lib, cpu = ref
-    K, N = 4096, 64
-    wqs = [weights(T, K, N, 500 + i) for i in range(3)]
-    xs = [synth.uniform(510 + i, K) for i in range(3)]
-    yr = _three_mul_mats(lib, cpu, T, wqs, K, N, xs)
-    y1 = in_order(rt, 1, lambda: _three_mul_mats(rt, backend, T, wqs, K, N, xs))
-    y0 = in_order(rt, 0, lambda: _three_mul_mats(rt, backend, T, wqs, K, N, xs))
-    for i in range(3):
-        assert same_bits(y1[i], yr[i]), (i, rel_err(y1[i], yr[i]))
-        assert rel_err(y0[i], yr[i]) <= TREE_TOL, (i, rel_err(y0[i], yr[i]))
-
-
-def _block(T, fill, d=1.0):
-    """A block whose quant, high-bit and scale bytes are all `fill` (0x00 or 0xFF): Q2_K every scale
-    and min 0 / 15 and every q 0 / 3; Q3_K every sc - 32 = -32 / 31 and every q - 4 * !hbit = -4 / 3."""
-    if T == Q2_K:
-        b = np.full(84, fill, np.uint8)
-        b[80:82] = np.array([d], np.float16).view(np.uint8)
-        b[82:84] = np.array([d], np.float16).view(np.uint8)
-    else:
-        b = np.full(110, fill, np.uint8)
-        b[108:110] = np.array([d], np.float16).view(np.uint8)
-    return b
+def test_three_independent_mul_mats_in_one_graph(rt, backend, ref, wt):
+    W.check_three_independent_mul_mats_in_one_graph(rt, backend, ref, wt)
 
 
 @needs_ref
 @both_types
-def test_extreme_integers(rt, backend, ref, T):
-    """Hand-made blocks at the ends of the integer range against columns whose Q8_K quants are all
-    of the largest magnitude: a constant column quantizes to -128 throughout (through an F32 src1
-    and through src1 pre-quantized by CPY F32 -> Q8_K alike), one of alternating signs to +-127.
-    Q3_K with every sc - 32 = -32 and every q - 4 = -4 then reaches the lane sum 8 * 4 * 4 * 128 * 32 =
-    2^19 and the superblock sum 2^22; Q2_K with every scale and min 15 and every q = 3 reaches its
-    largest lane sum and the mins product 2 * 15 * 16 * 128. Identical bits in the reference order.
-    K = 512, N = 8, B = 2."""
-    lib, cpu = ref
-    lo, hi = _block(T, 0x00), _block(T, 0xFF)
-    pairs = [(lo, lo), (hi, hi), (lo, hi), (hi, lo)]
-    wq = np.concatenate([np.concatenate(p) for p in pairs + pairs[::-1]])
-    K, N, B = 512, 8, 2
-    assert wq.size == N * G.row_size(T, K)
-    for x in (np.concatenate([np.full(K, 0.5, np.float32), np.full(K, -2.0, np.float32)]),
-              np.concatenate([np.tile(np.array([3.0, -3.0], np.float32), K // 2), np.full(K, 1e-3, np.float32)])):
-        yr = G.mul_mat_once(lib, cpu, T, wq, K, N, x, B)
-        assert np.abs(yr).max() > 1.0  # the sums did not cancel
-        y1 = in_order(rt, 1, lambda: G.mul_mat_once(rt, backend, T, wq, K, N, x, B))
-        y0 = in_order(rt, 0, lambda: G.mul_mat_once(rt, backend, T, wq, K, N, x, B))
-        assert same_bits(y1, yr), (y1, yr)
-        assert rel_err(y0, yr) <= TREE_TOL, rel_err(y0, yr)
-        yq = _cpy_q8k_then_mul_mat(lib, cpu, T, wq, K, N, x, B)
-        yq1 = in_order(rt, 1, lambda: _cpy_q8k_then_mul_mat(rt, backend, T, wq, K, N, x, B))
-        assert same_bits(yq1, yq), (yq1, yq)
+def test_extreme_integers(rt, backend, ref, wt):
+    W.check_extreme_integers(rt, backend, ref, wt)
 
 
 @needs_ref
 @both_types
-@pytest.mark.parametrize("B", [1, 3])
-def test_default_order_of_a_quantized_chain(rt, backend, ref, T, B):
-    """W1 . x -> RMSNorm -> W2 with the default settings (mmv_order -1): the second mul_mat consumes
-    computed activations, so the graph runs in the reference order -- the reference CPU's bits."""
-    lib, cpu = ref
-    K, N1, N2 = 1024, 768, 37
-    w1, w2 = weights(T, K, N1, 601), weights(T, N1, N2, 602)
-    x = synth.uniform(603 + B, K * B)
-
-    def build(L, c):
-        a = L.ggml_new_tensor_2d(c, T, K, N1)
-        b = L.ggml_new_tensor_2d(c, T, N1, N2)
-        xt = L.ggml_new_tensor_2d(c, G.GGML_TYPE_F32, K, B)
-        h = L.ggml_rms_norm(c, L.ggml_mul_mat(c, a, xt), 1e-5)
-        return [(a, w1), (b, w2), (xt, x)], L.ggml_mul_mat(c, b, h)
-
-    y = G.graph_once(rt, backend, lambda c: build(rt, c))
-    yr = G.graph_once(lib, cpu, lambda c: build(lib, c))
-    assert same_bits(y, yr), rel_err(y, yr)
-
-
-# ------------------------------------------------------------------ MUL_MAT_ID
-
-def _mul_mat_id(L, be, T, w, K, n, n_as, n_ids, n_tokens, x, ids):
-    def build(c):
-        a = L.ggml_new_tensor_3d(c, T, K, n, n_as)
-        b = L.ggml_new_tensor_3d(c, G.GGML_TYPE_F32, K, 1, n_tokens)
-        full = L.ggml_new_tensor_2d(c, G.GGML_TYPE_I32, n_as, n_tokens)
-        top = L.ggml_view_2d(c, full, n_ids, n_tokens, full.contents.nb[1], 0)
-        return [(a, w), (b, x), (full, ids)], L.ggml_mul_mat_id(c, a, b, top)
-    return G.graph_once(L, be, build)
+@pytest.mark.parametrize("B", ROWS[0].chain_B)
+def test_default_order_of_a_quantized_chain(rt, backend, ref, wt, B):
+    W.check_default_order_of_a_quantized_chain(rt, backend, ref, wt, B)
 
 
 @needs_ref
 @both_types
-@pytest.mark.parametrize("n_tokens", [1, 12])
-def test_mul_mat_id_top2_of_4_experts(rt, backend, ref, T, n_tokens):
-    """4 experts, the first two ids of every token's row (a strided view), src1 broadcast over the
-    ids: decode and a 12-token prompt against the reference CPU's MUL_MAT_ID."""
-    lib, cpu = ref
-    K, n, n_as, n_ids = 768, 100, 4, 2
-    w = weights(T, K, n * n_as, 901)
-    x = synth.uniform(902 + n_tokens, K * n_tokens)
-    rng = np.random.default_rng(903 + n_tokens)
-    ids = np.stack([rng.permutation(n_as) for _ in range(n_tokens)]).astype(np.int32)
-    yr = _mul_mat_id(lib, cpu, T, w, K, n, n_as, n_ids, n_tokens, x, ids)
-    y1 = in_order(rt, 1, lambda: _mul_mat_id(rt, backend, T, w, K, n, n_as, n_ids, n_tokens, x, ids))
-    y0 = in_order(rt, 0, lambda: _mul_mat_id(rt, backend, T, w, K, n, n_as, n_ids, n_tokens, x, ids))
-    assert yr.shape == (n * n_ids * n_tokens,) and np.abs(yr).max() > 0
-    assert same_bits(y1, yr), rel_err(y1, yr)
-    assert rel_err(y0, yr) <= TREE_TOL, rel_err(y0, yr)
-
-
-# ------------------------------------------------------------------ GPT-2 end to end
-
-TINY = dict(n_embd=256, n_head=4, n_layer=2, n_vocab=512, n_ctx=64)
-
-
-@pytest.fixture(scope="module")
-def tiny_models(tmp_path_factory):
-    d = tmp_path_factory.mktemp("q2k_q3k_gpt2")
-    f16 = gpt2.write_synthetic_model(str(d / "tiny-f16.bin"), **TINY)
-    return f16, {T: gpt2.quantize_model(G.runtime(), f16, str(d / f"tiny-{FTYPE[T]}.bin"), FTYPE[T]) for T in (Q2_K, Q3_K)}
+@pytest.mark.parametrize("n_tokens", ROWS[0].id_tokens)
+def test_mul_mat_id_top2_of_4_experts(rt, backend, ref, wt, n_tokens):
+    W.check_mul_mat_id_top2_of_4_experts(rt, backend, ref, wt, n_tokens)
 
 
 @pytest.mark.skipif(not os.path.exists(REF_QUANTIZE), reason="make -C oracle gpt2")
 @both_types
-def test_quantized_model_file_matches_reference_program(tiny_models, tmp_path, T):
-    import filecmp
-    f16, ours = tiny_models
-    out = str(tmp_path / f"ref-{FTYPE[T]}.bin")
-    p = subprocess.run([REF_QUANTIZE, f16, out, FTYPE[T]], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, p.stderr[-2000:]
-    assert os.path.getsize(ours[T]) == os.path.getsize(out)
-    assert filecmp.cmp(ours[T], out, shallow=False)
-
-
-def _both_models(path, n_batch):
-    lib = G.runtime()
-    be = G.mi355x_backend(lib)
-    ours = gpt2.Model(lib, path, be, n_batch=n_batch)
-    ref = G.Lib([REF_LIB, REF_GPT2], isolated=True)
-    rbe = ref.ggml_backend_cpu_init()
-    ref.ggml_backend_cpu_set_n_threads(rbe, 4)
-    rm = gpt2.Model(ref, path, rbe, n_batch=n_batch)
-
-    def free():
-        ours.free()
-        rm.free()
-        lib.ggml_backend_free(be)
-        ref.ggml_backend_free(rbe)
-    return ours, rm, free
-
-
-TOKENS = [(37 * i * i + 11 * i + 5) % 511 for i in range(20)]
+def test_quantized_model_file_matches_reference_program(tiny_models, tmp_path, wt):
+    W.check_quantized_model_file_matches_reference_program(tiny_models, tmp_path, wt)
 
 
 @pytest.mark.skipif(not os.path.exists(REF_GPT2), reason="make -C oracle gpt2")
 @both_types
-@pytest.mark.parametrize("mode", ["decode", "prompt20", "batches_of_8"])
-def test_gpt2_logits_bit_identical_to_reference_cpu(tiny_models, T, mode):
-    """A tiny GPT-2 of the type (its get_rows embedding, its MUL_MAT for every projection and the
-    lm_head), default settings: teacher-forced decode over 12 tokens, a 20-token prompt in one batch
-    (the chunked > 8 column path) and a prompt in batches of 8 -- the reference CPU's logits, bit for bit."""
-    n_batch = 20 if mode == "prompt20" else 8
-    ours, rm, free = _both_models(tiny_models[1][T], n_batch)
-    try:
-        assert ours.hp.ftype % 1000 == T
-        if mode == "decode":
-            steps = [[t] for t in TOKENS[:12]]
-        elif mode == "prompt20":
-            steps = [TOKENS]
-        else:
-            steps = [TOKENS[0:8], TOKENS[8:16], TOKENS[16:20]]
-        n_past = 0
-        for chunk in steps:
-            a = ours.eval(n_past, chunk, all_logits=True)
-            b = rm.eval(n_past, chunk, all_logits=True)
-            assert np.isfinite(b).all() and np.abs(b).max() > 0
-            assert same_bits(a, b), (mode, n_past, float(np.mean(a == b)), rel_err(a, b))
-            n_past += len(chunk)
-    finally:
-        free()
-
-
-# ------------------------------------------------------------------ split buffers, GGUF
-
-def _split_buft(rt, props):
-    arr = (ctypes.c_float * 16)(*([float(p) for p in props] + [0.0] * (16 - len(props))))
-    return rt.ggml_backend_mi355x_split_buffer_type(ctypes.cast(arr, ctypes.c_void_p))
+@pytest.mark.parametrize("mode", ROWS[0].gpt2_modes)
+def test_gpt2_logits_bit_identical_to_reference_cpu(tiny_models, wt, mode):
+    W.check_gpt2_logits_bit_identical_to_reference_cpu(tiny_models, wt, mode)
 
 
 @both_types
-@pytest.mark.parametrize("B", [1, 12])
-def test_split_buffer_weights(rt, backend, T, B):
-    """Rows divided over the slots of a split buffer (slots beyond the device count are virtual
-    slots on device 0, each with its own allocation, stream and copies): each slice runs through the
-    same mul_mat as the unsplit weight: the unsplit result's bits in the reference order, within
-    1e-5 of it in tree order."""
-    K, N = 768, 333  # 252- / 330-byte rows: Q3_K slices start 2 mod 4
-    wq = weights(T, K, N, 701)
-    x = synth.uniform(702 + B, K * B)
-    buft = _split_buft(rt, [1, 1, 0])
-    for order in (1, 0):
-        def run_split():
-            cw = G.Context(rt, rt.ggml_tensor_overhead() * 4, no_alloc=True)
-            cx = G.Context(rt, rt.ggml_tensor_overhead() * 8 + rt.ggml_graph_overhead(), no_alloc=True)
-            try:
-                w = rt.ggml_new_tensor_2d(cw.ctx, T, K, N)
-                wbuf = rt.ggml_backend_alloc_ctx_tensors_from_buft(cw.ctx, buft)
-                assert wbuf and rt.ggml_backend_buffer_name(wbuf) == b"MI355X_Split"
-                xt = rt.ggml_new_tensor_2d(cx.ctx, G.GGML_TYPE_F32, K, B)
-                y = rt.ggml_mul_mat(cx.ctx, w, xt)
-                g = rt.ggml_new_graph(cx.ctx)
-                rt.ggml_build_forward_expand(g, y)
-                xbuf = rt.ggml_backend_alloc_ctx_tensors(cx.ctx, backend)
-                try:
-                    G.tensor_set(rt, w, wq)
-                    back = np.empty_like(wq)
-                    rt.ggml_backend_tensor_get(w, back.ctypes.data, 0, back.nbytes)
-                    assert np.array_equal(back, wq), "split set/get round trip"
-                    G.tensor_set(rt, xt, x)
-                    assert rt.ggml_backend_graph_compute(backend, g) == G.GGML_STATUS_SUCCESS
-                    return G.tensor_get(rt, y)
-                finally:
-                    rt.ggml_backend_buffer_free(xbuf)
-                    rt.ggml_backend_buffer_free(wbuf)
-            finally:
-                cx.free()
-                cw.free()
-
-        ys = in_order(rt, order, run_split)
-        yu = in_order(rt, order, lambda: G.mul_mat_once(rt, backend, T, wq, K, N, x, B))
-        if order:
-            assert same_bits(ys, yu), rel_err(ys, yu)
-        else:
-            assert rel_err(ys, yu) <= TREE_TOL, rel_err(ys, yu)
+@pytest.mark.parametrize("B", ROWS[0].split_B)
+def test_split_buffer_weights(rt, backend, wt, B):
+    W.check_split_buffer_weights(rt, backend, wt, B)
 
 
 def test_gguf_q2k_q3k_weights_on_mi355x(rt, backend, tmp_path):
-    """A GGUF file with a tensor of each type -> MI355X buffer (gguf.Model): the bytes arrive and
-    MUL_MAT returns the golden outputs."""
-    c = MANIFEST["w"]
-    K, N, B = c["K"], c["N"], c["B"]
-    wqs = {T: golden_blob(f"{TAG[T]}_w.wq.bin") for T in (Q2_K, Q3_K)}
-    path = str(tmp_path / "q2k_q3k.gguf")
-    gguf.write(rt, path, [("general.architecture", "str", "test")],
-               [("pad", G.GGML_TYPE_F32, [3], np.zeros(3, np.float32)), ("w2", Q2_K, [K, N], wqs[Q2_K]),
-                ("w3", Q3_K, [K, N], wqs[Q3_K])])
-    m = gguf.Model(rt, path, backend)
-    try:
-        x = synth.uniform(c["xseed"], K * B)
-        for T, name in ((Q2_K, "w2"), (Q3_K, "w3")):
-            w = m.tensors[name]
-            assert w.contents.type == T
-            back = np.empty(rt.ggml_nbytes(w), np.uint8)
-            rt.ggml_backend_tensor_get(w, back.ctypes.data, 0, back.nbytes)
-            assert np.array_equal(back, wqs[T])
-
-            def build(ctx):
-                xt = rt.ggml_new_tensor_2d(ctx, G.GGML_TYPE_F32, K, B)
-                return [(xt, x)], rt.ggml_mul_mat(ctx, w, xt)
-
-            y = in_order(rt, 1, lambda: G.graph_once(rt, backend, build))
-            assert same_bits(y, golden_blob(f"{TAG[T]}_w.y.f32", np.float32)), name
-    finally:
-        m.free()
+    W.check_gguf_weights_on_mi355x(rt, backend, tmp_path, "q2k_q3k")

@@ -1,16 +1,22 @@
-"""Decode GEMV time of Q2_K and Q3_K beside the unchanged Q4_K and Q6_K kernels (B = 1, grouped
-graphs of R rotated weights, > 320 MiB per step so that no weight byte comes from the 256 MiB
-last-level cache), HIP events around graph-plan steps, for 4096x4096, 4096x11008 and 11008x4096 in
-tree order (mmv_order 0) and in the reference CPU's order (mmv_order 1).
+"""Decode GEMV time of quantized weight types side by side (B = 1, grouped graphs of R rotated
+weights, > 320 MiB per step so that no weight byte comes from the 256 MiB last-level cache), HIP
+events around graph-plan steps, for 4096x4096, 4096x11008 and 11008x4096 in tree order (mmv_order 0)
+and in the reference CPU's order (mmv_order 1).
 
 The types of one shape and order are measured in alternated rounds (round 1: every type, round 2:
 every type, ...), so that a drift of the box hits them alike; a line gives the median round, the
 spread of the rounds (min .. max) and the GB/s of algorithmic bytes at the median.
 
-  python tools/q2k_q3k_gemv.py                              kept as profiles/q2k_q3k_gemv.txt
-  GGML_MI355X_NO_FUSED_MMV=1 python tools/q2k_q3k_gemv.py   the generic kernels (mmv.hip) serve every
-                                                            mul_mat: profiles/q2k_q3k_gemv_generic.txt
-  python tools/q2k_q3k_gemv.py q3_K q4_K                    the named types only
+  python tools/type_gemv.py                         Q2_K, Q3_K, Q4_K, Q6_K, IQ4_NL, IQ4_XS and Q4_0
+  python tools/type_gemv.py q2_K q3_K q4_K q6_K     kept as profiles/q2k_q3k_gemv.txt
+  python tools/type_gemv.py iq4_nl iq4_xs q4_0 q4_K kept as profiles/iq4_gemv.txt
+  GGML_MI355X_NO_FUSED_MMV=1 python tools/type_gemv.py ...
+                                                    the generic kernels (mmv.hip) serve every mul_mat:
+                                                    profiles/q2k_q3k_gemv_generic.txt, iq4_gemv_generic.txt
+
+The type column is as wide as the longest name asked for, so the lines match the kept profiles.
+tools/q6k_gemv.py stays beside this script: it times one type at a time with bench.MulMatWorkload
+and prints the fastest of three rounds as ms/step, other columns than these.
 """
 import os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +30,8 @@ import torch  # noqa: E402
 SHAPES = ((4096, 4096), (4096, 11008), (11008, 4096))
 ROUNDS, ITERS = 5, 10
 by_lower = {k.lower(): k for k in G.TYPE_BY_NAME}
-names = [by_lower[a.lower()] for a in sys.argv[1:]] or ["q2_K", "q3_K", "q4_K", "q6_K"]
+names = [by_lower[a.lower()] for a in sys.argv[1:]] or ["q2_K", "q3_K", "q4_K", "q6_K", "iq4_nl", "iq4_xs", "q4_0"]
+width = max(map(len, names))
 
 
 class Rotated:
@@ -63,7 +70,7 @@ lib = G.runtime()
 be = G.mi355x_backend(lib, 0)
 sp = lib.ggml_backend_mi355x_get_stream(be)
 print(f"# {ROUNDS} alternated rounds of {ITERS} steps per line; us per mul_mat: median (min .. max of the rounds)")
-print("type  K x N (B = 1)    rotated  MiB/step  order           us/mul_mat median (min .. max)    GB/s (algorithmic bytes)", flush=True)
+print(f"{'type':{width}s}  K x N (B = 1)    rotated  MiB/step  order           us/mul_mat median (min .. max)    GB/s (algorithmic bytes)", flush=True)
 for k, n in SHAPES:
     wl = {}
     try:
@@ -85,7 +92,7 @@ for k, n in SHAPES:
                 v = sorted(us[tname])
                 med = v[len(v) // 2]
                 gbs = bench.unit_bytes(tt, k, n, 1) / (med * 1e-6) / 1e9
-                print(f"{tname}  {k:5d} x {n:5d}    {r:7d}  {r * G.row_size(tt, k) * n / 2**20:8.1f}  {oname:14s}  "
+                print(f"{tname:{width}s}  {k:5d} x {n:5d}    {r:7d}  {r * G.row_size(tt, k) * n / 2**20:8.1f}  {oname:14s}  "
                       f"{med:8.3f} ({v[0]:7.3f} .. {v[-1]:7.3f})         {gbs:7.1f}", flush=True)
     finally:
         lib.ggml_backend_mi355x_set_tuning(b"mmv_order", -1)
