@@ -597,6 +597,35 @@ static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
             if (op_param_f(op, 1) > 0.0f && !mask) return false;
             return !is_split_tensor(a) && !is_split_tensor(b) && !is_split_tensor(v) && !(mask && is_split_tensor(mask));
         }
+        case GGML_OP_SSM_CONV: {
+            // F32 state / x / weights and an I32 sq the kernel reads, with the strides the reference forward
+            // asserts (src/ggml.c:16331-16338): contiguous state rows, contiguous weights, x rows of any stride
+            const ggml_tensor * c = op->src[2];
+            const ggml_tensor * sq = op->src[3];
+            if (!a || !b || !c || !sq || !is_f32(a) || !is_f32(b) || !is_f32(c) || !is_f32(op) || sq->type != GGML_TYPE_I32) return false;
+            if (!mi_ssm_conv_width_ok(c->ne[0]) || !ggml_is_3d(a) || !ggml_is_matrix(b) || !ggml_is_matrix(c) || !ggml_is_matrix(sq)) return false;
+            if (a->ne[0] != c->ne[0] - 1 || a->ne[1] != c->ne[1] || b->ne[0] != c->ne[1] || sq->ne[0] != a->ne[2] || sq->ne[1] != b->ne[1]) return false;
+            if (a->nb[0] != sizeof(float) || a->nb[1] != (size_t) a->ne[0] * sizeof(float) || b->nb[0] != sizeof(float) ||
+                !ggml_is_contiguous(c) || sq->nb[0] != sizeof(int32_t) || !ggml_is_contiguous(op))
+                return false;
+            if (ggml_nelements(op) != b->ne[0] * b->ne[1] + c->ne[0] * c->ne[1] * a->ne[2]) return false;
+            return !is_split_tensor(a) && !is_split_tensor(b) && !is_split_tensor(c) && !is_split_tensor(sq);
+        }
+        case GGML_OP_SSM_SCAN: {
+            // F32 everywhere and an I32 sq; the strides of src/ggml.c:16460-16472: contiguous s and x, unit
+            // element stride in dt / A / B / C (B and C are views of wider rows in a model graph)
+            for (int i = 0; i < 7; i++) {
+                const ggml_tensor * t = op->src[i];
+                if (!t || t->type != (i == 6 ? GGML_TYPE_I32 : GGML_TYPE_F32) || t->nb[0] != 4 || is_split_tensor(t)) return false;
+            }
+            const ggml_tensor * dt = op->src[2], * A = op->src[3], * B = op->src[4], * C = op->src[5], * sq = op->src[6];
+            if (!is_f32(op) || !ggml_is_contiguous(op) || !ggml_is_contiguous(a) || !ggml_is_contiguous(b) || !ggml_is_3d(a)) return false;
+            if (!ggml_is_matrix(b) || !ggml_is_matrix(dt) || !ggml_is_matrix(A) || !ggml_is_matrix(B) || !ggml_is_matrix(C) || !ggml_is_matrix(sq)) return false;
+            const int64_t d_state = a->ne[0], d_inner = a->ne[1], n_t = b->ne[1];
+            if (d_state < 1 || b->ne[0] != d_inner || !ggml_are_same_shape(b, dt) || A->ne[0] != d_state || A->ne[1] != d_inner) return false;
+            if (B->ne[0] != d_state || B->ne[1] != n_t || C->ne[0] != d_state || C->ne[1] != n_t || sq->ne[0] != a->ne[2] || sq->ne[1] != n_t) return false;
+            return ggml_nelements(op) == ggml_nelements(b) + ggml_nelements(a);
+        }
         case GGML_OP_ADD:
         case GGML_OP_SUB:
         case GGML_OP_MUL:
@@ -1368,6 +1397,14 @@ static void op_companion(mi_backend_ctx * ctx, ggml_tensor * node) {
         case GGML_OP_SUM_ROWS: mi_op_sum_rows(desc(node), desc(a), st); break;
         case GGML_OP_ARGSORT:
             mi_op_argsort(desc(node), desc(a), ((const int32_t *) node->op_params)[0] == (int32_t) GGML_SORT_ORDER_DESC, st);
+            break;
+        case GGML_OP_SSM_CONV:
+            // (ssm.hip) sq = src[3] is read by the kernel: a replayed capture follows new ids
+            mi_op_ssm_conv(desc(node), desc(a), desc(b), desc(node->src[2]), desc(node->src[3]), st);
+            break;
+        case GGML_OP_SSM_SCAN:
+            mi_op_ssm_scan(desc(node), desc(a), desc(b), desc(node->src[2]), desc(node->src[3]), desc(node->src[4]), desc(node->src[5]),
+                           desc(node->src[6]), st);
             break;
         case GGML_OP_CPY:
         case GGML_OP_DUP:

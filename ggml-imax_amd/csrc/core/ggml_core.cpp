@@ -556,6 +556,70 @@ void ggml_flash_attn_ext_set_prec(struct ggml_tensor * a, enum ggml_prec prec) {
     a->op_params[2] = (int32_t) prec;
 }
 
+// src/ggml.c:6663-6704 ggml_ssm_conv: s [d_conv - 1, d_inner, n_kv], x [d_inner, n_tokens], c [d_conv, d_inner],
+// sq i32 [n_kv, n_tokens] -> dst f32, 1-D: the outputs [d_inner, n_tokens], then the new states
+// [d_conv, d_inner, n_kv] (one column wider than s)
+struct ggml_tensor * ggml_ssm_conv(struct ggml_context * ctx, struct ggml_tensor * s, struct ggml_tensor * x,
+                                   struct ggml_tensor * c, struct ggml_tensor * sq) {
+    GGML_ASSERT(ggml_is_3d(s));
+    GGML_ASSERT(ggml_is_matrix(x));
+    GGML_ASSERT(ggml_is_matrix(c));
+    GGML_ASSERT(ggml_is_matrix(sq));
+    GGML_ASSERT(sq->type == GGML_TYPE_I32);
+    const int64_t d_conv = c->ne[0];
+    const int64_t d_inner = c->ne[1];
+    const int64_t n_tokens = x->ne[1];
+    const int64_t n_kv = s->ne[2];
+    GGML_ASSERT(s->ne[0] == d_conv - 1);
+    GGML_ASSERT(s->ne[1] == d_inner);
+    GGML_ASSERT(x->ne[0] == d_inner);
+    GGML_ASSERT(sq->ne[0] == n_kv);
+    GGML_ASSERT(sq->ne[1] == n_tokens);
+    ggml_tensor * r = ggml_new_tensor_1d(ctx, GGML_TYPE_F32, d_inner * n_tokens + d_conv * d_inner * n_kv);
+    r->op = GGML_OP_SSM_CONV;
+    r->src[0] = s;
+    r->src[1] = x;
+    r->src[2] = c;
+    r->src[3] = sq;
+    return r;
+}
+
+// src/ggml.c:6708-6761 ggml_ssm_scan: s [d_state, d_inner, n_kv], x / dt [d_inner, n_tokens], A [d_state, d_inner],
+// B / C [d_state, n_tokens] (rows of any stride), sq i32 [n_kv, n_tokens] -> dst f32, 1-D: y [d_inner, n_tokens],
+// then the new states [d_state, d_inner, n_kv]
+struct ggml_tensor * ggml_ssm_scan(struct ggml_context * ctx, struct ggml_tensor * s, struct ggml_tensor * x,
+                                   struct ggml_tensor * dt, struct ggml_tensor * A, struct ggml_tensor * B,
+                                   struct ggml_tensor * C, struct ggml_tensor * sq) {
+    GGML_ASSERT(ggml_is_contiguous(s));
+    GGML_ASSERT(ggml_is_contiguous(x));
+    GGML_ASSERT(ggml_is_contiguous(dt));
+    GGML_ASSERT(ggml_is_contiguous(A));
+    GGML_ASSERT(sq->type == GGML_TYPE_I32);
+    GGML_ASSERT(B->nb[0] == ggml_type_size(B->type));
+    GGML_ASSERT(C->nb[0] == ggml_type_size(C->type));
+    GGML_ASSERT(ggml_are_same_shape(x, dt));
+    const int64_t d_state = s->ne[0];
+    const int64_t d_inner = s->ne[1];
+    const int64_t n_tokens = x->ne[1];
+    GGML_ASSERT(x->ne[0] == d_inner);
+    GGML_ASSERT(A->ne[0] == d_state);
+    GGML_ASSERT(A->ne[1] == d_inner);
+    GGML_ASSERT(B->ne[0] == d_state);
+    GGML_ASSERT(B->ne[1] == n_tokens);
+    GGML_ASSERT(C->ne[0] == d_state);
+    GGML_ASSERT(C->ne[1] == n_tokens);
+    ggml_tensor * r = ggml_new_tensor_1d(ctx, GGML_TYPE_F32, ggml_nelements(x) + ggml_nelements(s));
+    r->op = GGML_OP_SSM_SCAN;
+    r->src[0] = s;
+    r->src[1] = x;
+    r->src[2] = dt;
+    r->src[3] = A;
+    r->src[4] = B;
+    r->src[5] = C;
+    r->src[6] = sq;
+    return r;
+}
+
 static ggml_tensor * unary_like(ggml_context * ctx, ggml_tensor * a, ggml_op op, bool inplace) {
     ggml_tensor * r = inplace ? ggml_view_tensor(ctx, a) : ggml_dup_tensor(ctx, a);
     r->op = op;

@@ -366,6 +366,20 @@ struct mi_router_desc {
 };
 void mi_router_fused(const mi_router_desc & r, const uint16_t * exp_table, hipStream_t s);
 
+// ---- GGML_OP_SSM_CONV / GGML_OP_SSM_SCAN (ssm.hip; src/ggml.c:16311-16543) ----
+// All f32 but sq (i32 [n_kv, n_tokens], read by the kernels: a token whose sq[0] is outside [0, n_kv) is
+// skipped). d is 1-D: the outputs [d_inner, n_tokens], then the new states of every sequence. One launch each.
+// conv: s [d_conv - 1, d_inner, n_kv] (rows contiguous), x [d_inner, n_tokens] (nb0 == 4), c [d_conv, d_inner]
+// contiguous, d_conv in 2..8; the states in d are d_conv wide
+bool mi_ssm_conv_width_ok(int64_t d_conv);
+void mi_op_ssm_conv(const mi_tensor_desc & d, const mi_tensor_desc & s, const mi_tensor_desc & x, const mi_tensor_desc & c,
+                    const mi_tensor_desc & sq, hipStream_t st);
+// scan: s [d_state, d_inner, n_kv] and x [d_inner, n_tokens] contiguous; dt like x, A [d_state, d_inner] and
+// B / C [d_state, n_tokens] with nb0 == 4 and any row stride; any d_state >= 1 (16: the fast kernel)
+void mi_op_ssm_scan(const mi_tensor_desc & d, const mi_tensor_desc & s, const mi_tensor_desc & x, const mi_tensor_desc & dt,
+                    const mi_tensor_desc & A, const mi_tensor_desc & B, const mi_tensor_desc & C, const mi_tensor_desc & sq,
+                    hipStream_t st);
+
 // ---- GGML_OP_FLASH_ATTN_EXT (flash_attn.hip; src/ggml.c:15572-15751) ----
 // q f32 [D, N, nh, ne3] (nb0 == 4), k / v f16 [D, kv, nh_k / nh_v, ne3_k / ne3_v] (nb0 == 2), mask f16
 // rows of nbm1 bytes or null, dst f32 [D, nh, N, ne3] contiguous.

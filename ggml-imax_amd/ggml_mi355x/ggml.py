@@ -39,6 +39,7 @@ BLOCK = {0: (1, 4), 1: (1, 2), 2: (32, 18), 3: (32, 20), 6: (32, 22), 7: (32, 24
 
 GGML_OP_MUL_MAT = 23
 GGML_OP_FLASH_ATTN_EXT = 56
+GGML_OP_SSM_CONV, GGML_OP_SSM_SCAN = 59, 60
 GGML_KQ_MASK_PAD = 32  # rows of a flash-attention mask are padded to this
 GGML_PREC_DEFAULT, GGML_PREC_F32 = 0, 1
 GGML_STATUS_SUCCESS = 0
@@ -107,6 +108,8 @@ _SIGS = {
     "ggml_mul_mat_id": ([c_void_p, T, T, T], T),
     "ggml_flash_attn_ext": ([c_void_p, T, T, T, T, c_float, c_float], T),
     "ggml_flash_attn_ext_set_prec": ([T, c_int], None),
+    "ggml_ssm_conv": ([c_void_p, T, T, T, T], T),
+    "ggml_ssm_scan": ([c_void_p, T, T, T, T, T, T, T], T),
     "ggml_add": ([c_void_p, T, T], T),
     "ggml_mul": ([c_void_p, T, T], T),
     "ggml_sub": ([c_void_p, T, T], T),

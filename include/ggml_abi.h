@@ -316,6 +316,11 @@ GGML_API void ggml_mul_mat_set_prec(struct ggml_tensor * a, enum ggml_prec prec)
 GGML_API struct ggml_tensor * ggml_flash_attn_ext(struct ggml_context * ctx, struct ggml_tensor * q, struct ggml_tensor * k,
                                                   struct ggml_tensor * v, struct ggml_tensor * mask, float scale, float max_bias);
 GGML_API void ggml_flash_attn_ext_set_prec(struct ggml_tensor * a, enum ggml_prec prec);
+GGML_API struct ggml_tensor * ggml_ssm_conv(struct ggml_context * ctx, struct ggml_tensor * s, struct ggml_tensor * x,
+                                            struct ggml_tensor * c, struct ggml_tensor * sq);
+GGML_API struct ggml_tensor * ggml_ssm_scan(struct ggml_context * ctx, struct ggml_tensor * s, struct ggml_tensor * x,
+                                            struct ggml_tensor * dt, struct ggml_tensor * A, struct ggml_tensor * B,
+                                            struct ggml_tensor * C, struct ggml_tensor * sq);
 GGML_API struct ggml_tensor * ggml_dup(struct ggml_context * ctx, struct ggml_tensor * a);
 GGML_API struct ggml_tensor * ggml_add(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);
 GGML_API struct ggml_tensor * ggml_add_inplace(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);
