@@ -2092,6 +2092,10 @@ static void plan_attention(const ggml_cgraph * g, const mi_uses & u, std::vector
         bool all = true;
         for (int a : absorbed_ids) all &= a >= 0;
         if (!all) MI_ATTN_SKIP("check 15")
+        // the block writes M alone: a tensor the graph's user asked to keep must be computed by its own node
+        bool kept = (kqv->flags | P2->flags) & GGML_TENSOR_FLAG_OUTPUT;
+        for (const ggml_tensor * t : {vt, qc, Qp, kq, sc, dm, sm}) kept |= (t->flags & GGML_TENSOR_FLAG_OUTPUT) != 0;
+        if (kept) MI_ATTN_SKIP("check 15o")
         // the fused kernel writes M while other workgroups still read Q, K, V
         const char * mlo = (const char *) M->data;
         const char * mhi = mlo + ggml_nbytes(M);
