@@ -761,13 +761,15 @@ struct ggml_tensor * ggml_get_rows(struct ggml_context * ctx, struct ggml_tensor
 
 // src/ggml.c:5960 ggml_rope_impl: op_params = {n_past(0), n_dims, mode, n_ctx, n_orig_ctx,
 // freq_base, freq_scale, ext_factor, attn_factor, beta_fast, beta_slow, xpos_base, xpos_down}
-struct ggml_tensor * ggml_rope(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, int n_dims, int mode, int n_ctx) {
-    GGML_ASSERT(ggml_is_vector(b) && b->type == GGML_TYPE_I32 && a->ne[2] == b->ne[0]);
-    GGML_ASSERT((mode & 1) == 0 && "mode & 1 == 1 is no longer supported");
+static struct ggml_tensor * rope_impl(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, int n_dims, int mode, int n_ctx,
+                                      int n_orig_ctx, float freq_base, float freq_scale, float ext_factor, float attn_factor,
+                                      float beta_fast, float beta_slow) {
+    GGML_ASSERT(ggml_is_vector(b));
+    GGML_ASSERT(b->type == GGML_TYPE_I32);
+    GGML_ASSERT(a->ne[2] == b->ne[0]);
     ggml_tensor * r = ggml_dup_tensor(ctx, a);
-    int32_t params[13] = {0, n_dims, mode, n_ctx, 0};
-    const float freq_base = 10000.0f, freq_scale = 1.0f, ext_factor = 0.0f, attn_factor = 1.0f;
-    const float beta_fast = 32.0f, beta_slow = 1.0f, xpos_base = 0.0f;
+    int32_t params[13] = {0, n_dims, mode, n_ctx, n_orig_ctx};
+    const float xpos_base = 0.0f;
     const bool xpos_down = false;
     memcpy(params + 5, &freq_base, sizeof(float));
     memcpy(params + 6, &freq_scale, sizeof(float));
@@ -782,6 +784,18 @@ struct ggml_tensor * ggml_rope(struct ggml_context * ctx, struct ggml_tensor * a
     r->src[0] = a;
     r->src[1] = b;
     return r;
+}
+
+struct ggml_tensor * ggml_rope(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, int n_dims, int mode, int n_ctx) {
+    GGML_ASSERT((mode & 1) == 0 && "mode & 1 == 1 is no longer supported");
+    return rope_impl(ctx, a, b, n_dims, mode, n_ctx, 0, 10000.0f, 1.0f, 0.0f, 1.0f, 32.0f, 1.0f);
+}
+
+// src/ggml.c:5846 ggml_rope_custom: every parameter of ggml_rope_impl but the xPos pair
+struct ggml_tensor * ggml_rope_custom(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, int n_dims, int mode, int n_ctx,
+                                      int n_orig_ctx, float freq_base, float freq_scale, float ext_factor, float attn_factor,
+                                      float beta_fast, float beta_slow) {
+    return rope_impl(ctx, a, b, n_dims, mode, n_ctx, n_orig_ctx, freq_base, freq_scale, ext_factor, attn_factor, beta_fast, beta_slow);
 }
 
 // src/ggml.c:5220 ggml_cpy: result is a view of b

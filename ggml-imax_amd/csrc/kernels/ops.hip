@@ -430,13 +430,14 @@ __global__ __launch_bounds__(256) void k_soft_max(mi_tensor_desc d, mi_tensor_de
 // One thread per rotated pair. cos/sin come from the backend's host-built table (tab: the
 // reference's own running product theta *= theta_scale and the host libm's sincosf, so bit for bit
 // the reference CPU's values) for positions 0 <= p < tab_p; otherwise theta follows the same
-// running product on the device (each thread replays k multiplications) and cos/sin are rounded
-// from double (a correctly rounded libm: within an ulp of the host's). The pair is combined with
+// running product on the device (each thread replays k multiplications), the YaRN mix uses the
+// host table's fma so that theta is the same float, and cos/sin are rounded from double (a
+// correctly rounded libm: within an ulp of the host's). The pair is combined with
 // the fmas the reference's -mfma build emits (checked against its outputs): mode 0 fma(x0, cos,
 // -(x1 sin)) / fma(x1, cos, x0 sin), NeoX fma(x0, cos, -(x1 sin)) / fma(x0, sin, x1 cos).
 struct mi_rope_params {
     int n_dims, mode;
-    float freq_scale, ext_factor, attn_factor, theta_scale, inv_ndims, corr0, corr1;
+    float freq_scale, ext_factor, mscale, theta_scale, inv_ndims, corr0, corr1;  // mscale: rope_yarn's, computed on the host
     const float2 * tab;  // [tab_p][pairs] {cos, sin}, or null
     int tab_p;
 };
@@ -444,15 +445,15 @@ struct mi_rope_params {
 __device__ __forceinline__ void rope_yarn_dev(float theta_extrap, const mi_rope_params & r, int64_t i0, float & c, float & s) {
     const float theta_interp = mul_rn(r.freq_scale, theta_extrap);
     float theta = theta_interp;
-    float mscale = r.attn_factor;
     if (r.ext_factor != 0.0f) {
+        // the fma of the reference's -mfma build, as the host table's rope_yarn_host: separately rounded
+        // products put theta an ulp off, which at a theta in the hundreds is far more than an ulp of cos / sin
         const float y = ((float) (i0 / 2) - r.corr0) / fmaxf(0.001f, r.corr1 - r.corr0);
         const float ramp_mix = (1.0f - fminf(1.0f, fmaxf(0.0f, y))) * r.ext_factor;
-        theta = add_rn(mul_rn(theta_interp, 1.0f - ramp_mix), mul_rn(theta_extrap, ramp_mix));
-        mscale *= 1.0f + 0.1f * (float) log(1.0 / (double) r.freq_scale);
+        theta = __fmaf_rn(theta_interp, 1.0f - ramp_mix, mul_rn(theta_extrap, ramp_mix));
     }
-    c = mul_rn((float) cos((double) theta), mscale);
-    s = mul_rn((float) sin((double) theta), mscale);
+    c = mul_rn((float) cos((double) theta), r.mscale);
+    s = mul_rn((float) sin((double) theta), r.mscale);
 }
 
 __global__ __launch_bounds__(256) void k_rope(mi_tensor_desc d, mi_tensor_desc a, const int32_t * pos, mi_rope_params r) {
@@ -594,7 +595,8 @@ void mi_op_rope(const mi_tensor_desc & d, const mi_tensor_desc & a, const int32_
     r.mode = mode;
     r.freq_scale = freq_scale;
     r.ext_factor = ext_factor;
-    r.attn_factor = attn_factor;
+    // rope_yarn's magnitude with the host's logf and the reference build's fma, as rope_yarn_host computes it
+    r.mscale = ext_factor != 0.0f ? attn_factor * fmaf(logf(1.0f / freq_scale), 0.1f, 1.0f) : attn_factor;
     r.theta_scale = powf(freq_base, -2.0f / n_dims);
     r.inv_ndims = -1.f / n_dims;
     r.corr0 = corr0;

@@ -127,6 +127,7 @@ _SIGS = {
     "ggml_diag_mask_inf": ([c_void_p, T, c_int], T),
     "ggml_get_rows": ([c_void_p, T, T], T),
     "ggml_rope": ([c_void_p, T, T, c_int, c_int, c_int], T),
+    "ggml_rope_custom": ([c_void_p, T, T, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float], T),
     "ggml_cpy": ([c_void_p, T, T], T),
     "ggml_cont": ([c_void_p, T], T),
     "ggml_transpose": ([c_void_p, T], T),

@@ -134,9 +134,16 @@ def _graph_signature(lib):
         out = lib.ggml_gelu(ctx, lib.ggml_cont(ctx, lib.ggml_transpose(ctx, kq)))
         x4 = lib.ggml_new_tensor_2d(ctx, 0, 256, 2)
         out2 = lib.ggml_mul_mat(ctx, w, x4)
+        # ggml_rope_custom: every op_param of ggml_rope_impl, on a view of wider rows and with n_dims < ne0
+        x3 = lib.ggml_new_tensor_3d(ctx, 0, 32, n_head, n_tok)
+        pos = lib.ggml_new_tensor_1d(ctx, 26, n_tok)
+        xv = lib.ggml_view_3d(ctx, x3, 16, n_head, n_tok, x3.contents.nb[1], x3.contents.nb[2], 0)
+        out3 = lib.ggml_rope_custom(ctx, xv, pos, 8, 2, 4096, 2048, 500000.0, 0.25, 1.0, 0.8, 24.0, 2.0)
+        out3 = lib.ggml_rope_custom(ctx, out3, pos, 16, 0, 0, 0, 10000.0, 1.0, 0.0, 1.0, 32.0, 1.0)
         gr = lib.ggml_new_graph(ctx)
         lib.ggml_build_forward_expand(gr, out)
         lib.ggml_build_forward_expand(gr, out2)
+        lib.ggml_build_forward_expand(gr, out3)
         gg = gr.contents
         sig = []
         for i in range(gg.n_nodes):
