@@ -46,7 +46,7 @@ static_assert(MI_TYPE_F32 == GGML_TYPE_F32 && MI_TYPE_F16 == GGML_TYPE_F16 && MI
               MI_TYPE_Q5_0 == GGML_TYPE_Q5_0 && MI_TYPE_Q5_1 == GGML_TYPE_Q5_1 && MI_TYPE_Q8_0 == GGML_TYPE_Q8_0 && MI_TYPE_Q8_1 == GGML_TYPE_Q8_1 &&
               MI_TYPE_Q4_K == GGML_TYPE_Q4_K && MI_TYPE_Q5_K == GGML_TYPE_Q5_K && MI_TYPE_Q6_K == GGML_TYPE_Q6_K && MI_TYPE_Q8_K == GGML_TYPE_Q8_K &&
               MI_TYPE_Q2_K == GGML_TYPE_Q2_K && MI_TYPE_Q3_K == GGML_TYPE_Q3_K && MI_TYPE_IQ4_NL == GGML_TYPE_IQ4_NL &&
-              MI_TYPE_IQ4_XS == GGML_TYPE_IQ4_XS && MI_TYPE_I32 == GGML_TYPE_I32, "mi355x_types.h names ggml_type values");
+              MI_TYPE_IQ4_XS == GGML_TYPE_IQ4_XS && MI_TYPE_I32 == GGML_TYPE_I32 && MI_TYPE_BF16 == GGML_TYPE_BF16, "mi355x_types.h names ggml_type values");
 
 static constexpr size_t kBufferAlign = 256;   // tensor alignment inside device buffers
 static constexpr size_t kBufferSlack = 256;   // tail slack: kernels may over-read < 16 B past a row
@@ -537,11 +537,13 @@ static bool mm_row_supported(const ggml_tensor * a) { return a->type != GGML_TYP
 
 static bool is_f32(const ggml_tensor * t) { return t && t->type == GGML_TYPE_F32; }
 static bool is_f16_or_f32(const ggml_tensor * t) { return t && (t->type == GGML_TYPE_F32 || t->type == GGML_TYPE_F16); }
+// the dense element types CPY / DUP / CONT convert between (the element-wise ops take F32 / F16 only)
+static bool is_dense(const ggml_tensor * t) { return is_f16_or_f32(t) || (t && t->type == GGML_TYPE_BF16); }
 
 // the quantized vec_dot_type a src1 may already have for weight type t (GGML_TYPE_COUNT: none)
 static ggml_type q8_src1_type(ggml_type t) {
     const mi_act_quant q = mi_type(t).act;
-    return q == MI_ACT_NONE || q == MI_ACT_F16 ? GGML_TYPE_COUNT : (ggml_type) mi_act_type(q);
+    return q == MI_ACT_NONE || q == MI_ACT_F16 || q == MI_ACT_BF16 ? GGML_TYPE_COUNT : (ggml_type) mi_act_type(q);
 }
 
 // the q8 quantization whose rows have type t (MI_ACT_NONE: t is no such type)
@@ -567,10 +569,10 @@ static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
             if (!mm_src0_supported(a->type) || !mm_row_supported(a)) return false;
             if (a->nb[0] != ggml_type_size(a->type) || b->nb[0] != ggml_type_size(b->type)) return false;
             // src1 F32, or src1 already of the weight's vec_dot_type, which the reference CPU reads as
-            // it lies (ggml.c:11952; F16 x F16, Q4_K/Q5_K/Q6_K x Q8_K, Q4_0/Q5_0/Q8_0 x Q8_0, Q4_1/Q5_1 x Q8_1): the quantized
+            // it lies (ggml.c:11952; F16 x F16, BF16 x BF16, Q4_K/Q5_K/Q6_K x Q8_K, Q4_0/Q5_0/Q8_0 x Q8_0, Q4_1/Q5_1 x Q8_1): the quantized
             // ones with whole superblocks, on the device's own weights
-            // (the split-buffer path converts an F32 src1 on the main device: F16 src1 only unsplit)
-            if (b->type == GGML_TYPE_F32 || (b->type == GGML_TYPE_F16 && a->type == GGML_TYPE_F16 && !is_split_tensor(a))) return true;
+            // (the split-buffer path converts an F32 src1 on the main device: F16 / BF16 src1 only unsplit)
+            if (b->type == GGML_TYPE_F32 || ((b->type == GGML_TYPE_F16 || b->type == GGML_TYPE_BF16) && a->type == b->type && !is_split_tensor(a))) return true;
             return b->type == q8_src1_type(a->type) && a->ne[0] % 256 == 0 && !is_split_tensor(a);
         }
         case GGML_OP_MUL_MAT_ID: {
@@ -668,7 +670,8 @@ static bool mi_supports_op(ggml_backend_t, const ggml_tensor * op) {
             if (is_f32(a) && q8_quant_of(op->type) != MI_ACT_NONE)
                 return ggml_are_same_shape(a, op) && a->nb[0] == sizeof(float) && op->nb[0] == ggml_type_size(op->type) &&
                        op->ne[0] % mi_act_block(q8_quant_of(op->type)) == 0;
-            return is_f16_or_f32(a) && is_f16_or_f32(op);
+            // F32 / F16 / BF16 in any pairing (to BF16: ggml_fp32_to_bf16's bits, F16 through f32)
+            return is_dense(a) && is_dense(op);
         case GGML_OP_ROPE: {
             const int32_t * pp = (const int32_t *) op->op_params;
             const int mode = pp[2];
@@ -690,10 +693,10 @@ static bool mi_offload_op(ggml_backend_t, const ggml_tensor * op) {
 // GGML_OP_MUL_MAT
 // ---------------------------------------------------------------------------------------------
 
-// the activations of weight type t as its GEMV reads them: q8 SoA, or f16 rows
+// the activations of weight type t as its GEMV reads them: q8 SoA, or f16 / bf16 rows
 static mi_act_format act_format_of(ggml_type t) {
     const mi_act_quant q = mi_type(t).act;
-    return {q, q == MI_ACT_F16 ? MI_LAYOUT_ROWS : MI_LAYOUT_SOA};
+    return {q, q == MI_ACT_F16 || q == MI_ACT_BF16 ? MI_LAYOUT_ROWS : MI_LAYOUT_SOA};
 }
 
 static mi_act_mmx mmx_carve(mi_act_quant q, void * base, int64_t K, int64_t ncols) {
@@ -776,6 +779,10 @@ static void * get_activations(mi_backend_ctx * ctx, const ggml_tensor * src1, mi
         if (f.quant == MI_ACT_Q8_K) mi_quantize_q8_K(x, K, act, ctx->stream);
         else if (f.quant == MI_ACT_Q8_1) mi_quantize_q8_1(x, K, act, ctx->stream);
         else mi_quantize_q8_0(x, K, act, ctx->stream);
+    } else if (f.quant == MI_ACT_BF16) {
+        // bf16 rows (ggml_fp32_to_bf16_row's bits; a BF16 src1 is copied as it lies): never the f16 converter
+        MI_ASSERT(f.layout == MI_LAYOUT_ROWS);
+        mi_convert_bf16(x, K, (uint16_t *) dev, (int) src1->type, ctx->stream);
     } else if (f.quant == MI_ACT_F16) {
         mi_convert_f16(x, K, (uint16_t *) dev, ctx->stream, blocked, src1->type == GGML_TYPE_F16);
     } else {
@@ -902,7 +909,7 @@ static mi_mm_desc mm_desc(const ggml_tensor * src0, const void * W, int64_t N, c
 // (op_mul_mat_split) each device's row slice.
 static void mul_mat_run(mi_backend_ctx * ctx, const ggml_tensor * src0, const void * W, int64_t N, const ggml_tensor * src1,
                         float * out, size_t nb1, size_t nb2, size_t nb3) {
-    MI_ASSERT(src1->type == GGML_TYPE_F32 || (src1->type == GGML_TYPE_F16 && src0->type == GGML_TYPE_F16) ||
+    MI_ASSERT(src1->type == GGML_TYPE_F32 || ((src1->type == GGML_TYPE_F16 || src1->type == GGML_TYPE_BF16) && src0->type == src1->type) ||
               src1->type == q8_src1_type(src0->type));
     MI_ASSERT(src0->nb[0] == ggml_type_size(src0->type));
     MI_ASSERT(src1->nb[0] == ggml_type_size(src1->type));
@@ -928,7 +935,10 @@ static void mul_mat_run(mi_backend_ctx * ctx, const ggml_tensor * src0, const vo
                 break;
             case MI_LAYOUT_ROWS:
             case MI_LAYOUT_BLOCKED:
-                if (f.quant == MI_ACT_F16 && f.layout == MI_LAYOUT_BLOCKED && mi_mmf16p_supported(m.K, m.N, m.nb01, ncols, m.nb1)) {
+                if (f.quant == MI_ACT_BF16) {
+                    // BF16 weights: their own kernels at any column count and shape (mm_bf16.hip)
+                    mi_mul_mat_bf16(m, xh, ctx->stream);
+                } else if (f.quant == MI_ACT_F16 && f.layout == MI_LAYOUT_BLOCKED && mi_mmf16p_supported(m.K, m.N, m.nb01, ncols, m.nb1)) {
                     // F16 weights, a short prompt: 32 x 32 tiles with the K split over each tile's 4 waves
                     mi_mul_mat_f16p(m.W, m.nb01, m.K, m.N, xh, ncols, m.dst, m.nb1, ctx->stream);
                 } else if (f.quant != MI_ACT_F16 || f.layout == MI_LAYOUT_BLOCKED || mm_batched(m, src1)) {
@@ -1054,6 +1064,8 @@ static void op_mul_mat_id(mi_backend_ctx * ctx, ggml_tensor * dst) {
         void * xa = get_activations(ctx, b, f, K);
         if (f.quant == MI_ACT_F16) {
             mi_mul_mat_f16(m, (const uint16_t *) xa, ctx->stream);
+        } else if (f.quant == MI_ACT_BF16) {
+            mi_mul_mat_bf16(m, (const uint16_t *) xa, ctx->stream);
         } else {
             if (grouped) {
                 const int64_t pairs = n_ids * n_tokens;
@@ -1526,7 +1538,7 @@ static size_t graph_scratch_bytes(const ggml_cgraph * cgraph) {
         const ggml_tensor * b = n->src[1];
         const int64_t ncols = b->ne[1] * b->ne[2] * b->ne[3];
         total += (act_bytes(f, b->ne[0], ncols) + kBufferAlign - 1) & ~(kBufferAlign - 1);
-        if (ncols > 8 && f.quant != MI_ACT_Q8_1) {
+        if (ncols > 8 && f.quant != MI_ACT_Q8_1 && f.quant != MI_ACT_BF16) {
             const size_t big = std::max(act_bytes({f.quant, MI_LAYOUT_ROWS}, b->ne[0], ncols),
                                         f.quant != MI_ACT_F16 ? act_bytes({f.quant, MI_LAYOUT_MFMA}, b->ne[0], ncols) : 0);
             total += (big + kBufferAlign - 1) & ~(kBufferAlign - 1);
@@ -2920,6 +2932,9 @@ static enum ggml_status mi_graph_plan_compute(ggml_backend_t backend, ggml_backe
 // reference order, bit-identical either way -- and in a full graph as input.
 static bool sched_split_view(const ggml_cgraph * g) { return g->size == 0 && g->visited_hash_table.size == 0; }
 
+// BF16 weights count as F16 does (ggml_is_quantized is false for both): rounding an activation to bf16 turns a
+// 1-ulp f32 difference into another value only where it crosses a rounding tie, about once in 2^16 values,
+// against every value near a boundary for round(x / d) -- DESIGN section 22 has the measured deviation.
 static int graph_decode_order(const ggml_cgraph * g) {
     const bool view = sched_split_view(g);
     for (int i = 0; i < g->n_nodes; i++) {

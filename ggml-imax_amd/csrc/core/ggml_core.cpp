@@ -160,6 +160,34 @@ void ggml_fp32_to_fp16_row(const float * x, ggml_fp16_t * y, int64_t n) {
     for (int64_t i = 0; i < n; i++) y[i] = ggml_fp32_to_fp16(x[i]);
 }
 
+// bf16 (ggml-impl.h:59-92): the upper half of an f32. To bf16: a NaN keeps its upper half and is made
+// quiet, an f32 with a zero exponent field (zero or subnormal) becomes a signed zero, everything else
+// rounds to nearest even (0x7f7fffff carries into inf)
+float ggml_bf16_to_fp32(ggml_bf16_t h) {
+    const uint32_t x = (uint32_t) h.bits << 16;
+    float f;
+    memcpy(&f, &x, 4);
+    return f;
+}
+
+ggml_bf16_t ggml_fp32_to_bf16(float f) {
+    uint32_t x;
+    memcpy(&x, &f, 4);
+    ggml_bf16_t h;
+    if ((x & 0x7fffffffu) > 0x7f800000u) h.bits = (uint16_t) ((x >> 16) | 64u);
+    else if (!(x & 0x7f800000u)) h.bits = (uint16_t) ((x & 0x80000000u) >> 16);
+    else h.bits = (uint16_t) ((x + (0x7fffu + ((x >> 16) & 1u))) >> 16);
+    return h;
+}
+
+void ggml_bf16_to_fp32_row(const ggml_bf16_t * x, float * y, int64_t n) {
+    for (int64_t i = 0; i < n; i++) y[i] = ggml_bf16_to_fp32(x[i]);
+}
+
+void ggml_fp32_to_bf16_row(const float * x, ggml_bf16_t * y, int64_t n) {
+    for (int64_t i = 0; i < n; i++) y[i] = ggml_fp32_to_bf16(x[i]);
+}
+
 bool ggml_guid_matches(ggml_guid_t a, ggml_guid_t b) { return memcmp(a, b, sizeof(ggml_guid)) == 0; }
 
 static int64_t g_t0_us;

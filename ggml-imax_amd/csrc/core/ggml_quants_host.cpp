@@ -814,7 +814,7 @@ size_t ggml_quantize_chunk(enum ggml_type type, const float * src, void * dst, i
     const size_t row_size = ggml_row_size(type, n_per_row);
     char * out = (char *) dst + (start / n_per_row) * row_size;
     const float * in = src + start;
-    if (imatrix != NULL && type != GGML_TYPE_Q8_0 && type != GGML_TYPE_F16 && type != GGML_TYPE_F32) {
+    if (imatrix != NULL && type != GGML_TYPE_Q8_0 && type != GGML_TYPE_F16 && type != GGML_TYPE_BF16 && type != GGML_TYPE_F32) {
         GGML_ASSERT(!"importance-matrix quantization is not supported by this runtime");
     }
     switch (type) {
@@ -831,6 +831,7 @@ size_t ggml_quantize_chunk(enum ggml_type type, const float * src, void * dst, i
         case GGML_TYPE_IQ4_NL: quantize_iq4_nl_rows(in, (blk_iq4_nl *) out, n); break;
         case GGML_TYPE_IQ4_XS: quantize_iq4_xs_rows(in, (blk_iq4_xs *) out, n); break;
         case GGML_TYPE_F16: ggml_fp32_to_fp16_row(in, (ggml_fp16_t *) out, n); break;
+        case GGML_TYPE_BF16: ggml_fp32_to_bf16_row(in, (ggml_bf16_t *) out, n); break;
         case GGML_TYPE_F32: memcpy(out, in, (size_t) n * sizeof(float)); break;
         default: GGML_ASSERT(!"ggml_quantize_chunk: type not supported by this runtime");
     }

@@ -40,6 +40,18 @@ __device__ __forceinline__ uint16_t mi_f2h(float f) {
     return h;
 }
 
+// bf16: the upper half of an f32 (exact). To bf16 by ggml_fp32_to_bf16's rules (src/ggml-impl.h:75-92), in
+// integer arithmetic: a NaN keeps its upper half and is made quiet, an f32 with a zero exponent field
+// becomes a signed zero, everything else rounds to nearest even (v_cvt_pk_bf16_f32 keeps subnormals
+// and treats NaN payloads differently: not used)
+__device__ __forceinline__ float mi_bf2f(uint16_t b) { return __uint_as_float((uint32_t) b << 16); }
+__device__ __forceinline__ uint16_t mi_f2bf(float f) {
+    const uint32_t x = __float_as_uint(f);
+    if ((x & 0x7fffffffu) > 0x7f800000u) return (uint16_t) ((x >> 16) | 64u);
+    if (!(x & 0x7f800000u)) return (uint16_t) ((x & 0x80000000u) >> 16);
+    return (uint16_t) ((x + (0x7fffu + ((x >> 16) & 1u))) >> 16);
+}
+
 // f16(a * b) with the product rounded to f32 first, then to f16, as the CPU's F16C code rounds it. The
 // empty asm keeps the compiler from folding the multiply into the conversion (a mixed-precision
 // v_fma_mixlo_f16 rounds the exact product once: a different f16 about once in 2^13 products).

@@ -485,5 +485,11 @@ void mi_sum_parts(float * out, const float * parts, int nparts, int64_t n, hipSt
 
 // f16 weights x f16-rounded activations
 void mi_mul_mat_f16(const mi_mm_desc & m, const uint16_t * xh, hipStream_t s);
+// bf16 weights x bf16 activations (mm_bf16.hip). mi_convert_bf16: src1 columns of src_type MI_TYPE_F32 /
+// MI_TYPE_F16 (rounded with ggml_fp32_to_bf16's bits) or MI_TYPE_BF16 (copied) -> bf16 rows [ncols][K].
+// mi_mul_mat_bf16: xb those rows; any K, row alignment, column count, weight batch and MUL_MAT_ID;
+// mmv_order 1: ggml_vec_dot_bf16's bits
+void mi_convert_bf16(const mi_src_cols & x, int64_t K, uint16_t * out, int src_type, hipStream_t s);
+void mi_mul_mat_bf16(const mi_mm_desc & m, const uint16_t * xb, hipStream_t s);
 // f32 x f32, both operands arbitrarily strided (src1 described by x, src0 by m.nb0x)
 void mi_mul_mat_f32(const mi_mm_desc & m, const mi_src_cols & x, hipStream_t s);

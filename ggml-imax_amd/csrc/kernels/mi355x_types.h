@@ -20,17 +20,18 @@
 // backend static_asserts each against GGML_TYPE_*). Kernel templates take them as plain ints.
 constexpr int MI_TYPE_F32 = 0, MI_TYPE_F16 = 1, MI_TYPE_Q4_0 = 2, MI_TYPE_Q4_1 = 3, MI_TYPE_Q5_0 = 6, MI_TYPE_Q5_1 = 7,
               MI_TYPE_Q8_0 = 8, MI_TYPE_Q8_1 = 9, MI_TYPE_Q2_K = 10, MI_TYPE_Q3_K = 11, MI_TYPE_Q4_K = 12, MI_TYPE_Q5_K = 13, MI_TYPE_Q6_K = 14, MI_TYPE_Q8_K = 15,
-              MI_TYPE_IQ4_NL = 20, MI_TYPE_IQ4_XS = 23, MI_TYPE_I32 = 26;
+              MI_TYPE_IQ4_NL = 20, MI_TYPE_IQ4_XS = 23, MI_TYPE_I32 = 26, MI_TYPE_BF16 = 30;
 
 // How the activation columns of a mul_mat are quantized: the weight type's vec_dot_type in the
-// reference (src/ggml.c type_traits). MI_ACT_NONE: F32 weights read src1 as it lies.
-enum mi_act_quant : int { MI_ACT_NONE, MI_ACT_Q8_0, MI_ACT_Q8_1, MI_ACT_Q8_K, MI_ACT_F16 };
+// reference (src/ggml.c type_traits). MI_ACT_NONE: F32 weights read src1 as it lies. MI_ACT_F16 /
+// MI_ACT_BF16: dense 2-byte elements (ggml_fp32_to_fp16_row / ggml_fp32_to_bf16_row), no blocks.
+enum mi_act_quant : int { MI_ACT_NONE, MI_ACT_Q8_0, MI_ACT_Q8_1, MI_ACT_Q8_K, MI_ACT_F16, MI_ACT_BF16 };
 constexpr int mi_act_block(mi_act_quant q) { return q == MI_ACT_Q8_K ? 256 : 32; }  // elements per q8 block
 constexpr int mi_act_block_bytes(mi_act_quant q) {  // bytes per block of its rows in the reference layout (block_q8_0 / _q8_1 / _q8_K)
     return q == MI_ACT_Q8_K ? 292 : q == MI_ACT_Q8_1 ? 36 : q == MI_ACT_Q8_0 ? 34 : 2;
 }
 constexpr int mi_act_type(mi_act_quant q) {  // its ggml_type (-1: none)
-    return q == MI_ACT_Q8_0 ? MI_TYPE_Q8_0 : q == MI_ACT_Q8_1 ? MI_TYPE_Q8_1 : q == MI_ACT_Q8_K ? MI_TYPE_Q8_K : q == MI_ACT_F16 ? MI_TYPE_F16 : -1;
+    return q == MI_ACT_Q8_0 ? MI_TYPE_Q8_0 : q == MI_ACT_Q8_1 ? MI_TYPE_Q8_1 : q == MI_ACT_Q8_K ? MI_TYPE_Q8_K : q == MI_ACT_F16 ? MI_TYPE_F16 : q == MI_ACT_BF16 ? MI_TYPE_BF16 : -1;
 }
 
 struct mi_type_info {
@@ -74,6 +75,9 @@ constexpr mi_type_info kMiTypes[] = {
     //  type         blck bytes act          has_m  has_qh sub  lut    mmv  align mmqx   mmq    planes copy   get_rows
     {MI_TYPE_F32,    1,   4,   MI_ACT_NONE, false, false, 0,   false, 0,   16,   false, false, false, false, true},
     {MI_TYPE_F16,    1,   2,   MI_ACT_F16,  false, false, 0,   false, 0,   16,   false, true,  false, false, true},
+    // (BF16: its own kernels, mm_bf16.hip. Never the f16-operand GEMM of mmq.hip or mi_convert_f16: bf16's
+    // exponent range does not fit f16. Rows of an odd K are 2-byte aligned: its launchers pick the path.)
+    {MI_TYPE_BF16,   1,   2,   MI_ACT_BF16, false, false, 0,   false, 0,   2,    false, false, false, false, true},
     {MI_TYPE_Q4_0,   32,  18,  MI_ACT_Q8_0, false, false, 8,   false, 32,  16,   true,  true,  false, true,  true},
     {MI_TYPE_Q4_1,   32,  20,  MI_ACT_Q8_1, true,  false, 0,   false, 21,  16,   false, false, false, false, true},
     {MI_TYPE_Q5_0,   32,  22,  MI_ACT_Q8_0, false, true,  16,  false, 21,  16,   false, false, false, false, true},
@@ -118,6 +122,7 @@ template <class F> void mi_dispatch_type(int type, F && f) {
         case MI_TYPE_IQ4_NL: f(mi_type_c<MI_TYPE_IQ4_NL>{}); break;
         case MI_TYPE_IQ4_XS: f(mi_type_c<MI_TYPE_IQ4_XS>{}); break;
         case MI_TYPE_F16: f(mi_type_c<MI_TYPE_F16>{}); break;
+        case MI_TYPE_BF16: f(mi_type_c<MI_TYPE_BF16>{}); break;
         case MI_TYPE_F32: f(mi_type_c<MI_TYPE_F32>{}); break;
         default: MI_ASSERT(!"weight type outside the table");
     }

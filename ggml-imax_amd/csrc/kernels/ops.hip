@@ -2,7 +2,7 @@
 //
 // All are memory- or launch-bound. Each follows the reference CPU forward's rounding sequence so
 // that results are bit-identical where the CPU order is reproducible:
-//   get_rows   src/ggml.c:12920 (f16) / :13006 (f32) / :12874 (Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K .. Q6_K, IQ4_NL, IQ4_XS) -- exact
+//   get_rows   src/ggml.c:12920 (f16) / :12963 (bf16) / :13006 (f32) / :12874 (Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K .. Q6_K, IQ4_NL, IQ4_XS) -- exact
 //   add / mul  src/ggml.c:8568 / :9687 (broadcast src1)      -- exact
 //   scale      src/ggml.c:12637                              -- exact
 //   norm       src/ggml.c:11353-11406 (double sums)          -- sums in double, then the same f32 ops
@@ -13,7 +13,8 @@
 //              reference's ggml_init, src/ggml.c:2884-2898)
 //   rope       src/ggml.c:13719-13948 (modes 0 and 2)
 //   cpy/cont/dup src/ggml.c:8062, :12818 -- element i of src (row-major logical order) to
-//              element i of dst, with f32/f16 conversion (RNE)
+//              element i of dst, with f32/f16 conversion (RNE) or f32/bf16 (ggml_fp32_to_bf16: RNE, NaNs made
+//              quiet, subnormals flushed; f16 -> bf16 through f32)
 
 #include "mi355x_common.h"
 #include "mi355x_kernels.h"
@@ -39,11 +40,13 @@ __device__ __forceinline__ size_t off4(const size_t * nb, int64_t i0, int64_t i1
 }
 
 __device__ __forceinline__ float ld_f(const char * p, int type) {
+    if (type == MI_TYPE_BF16) return mi_bf2f(*(const uint16_t *) p);
     return type == MI_TYPE_F16 ? mi_h2f(*(const uint16_t *) p) : *(const float *) p;
 }
 
 __device__ __forceinline__ void st_f(char * p, int type, float v) {
     if (type == MI_TYPE_F16) *(uint16_t *) p = mi_f2h(v);
+    else if (type == MI_TYPE_BF16) *(uint16_t *) p = mi_f2bf(v);  // ggml_fp32_to_bf16's bits
     else *(float *) p = v;
 }
 
@@ -96,7 +99,7 @@ __global__ __launch_bounds__(256) void k_cpy(mi_tensor_desc d, mi_tensor_desc a,
         unflatten(i, d.ne, j0, j1, j2, j3);
         const char * sp = a.data + off4(a.nb, i0, i1, i2, i3);
         char * dp = d.data + off4(d.nb, j0, j1, j2, j3);
-        if (a.type == d.type && a.type == MI_TYPE_F16) *(uint16_t *) dp = *(const uint16_t *) sp;
+        if (a.type == d.type && (a.type == MI_TYPE_F16 || a.type == MI_TYPE_BF16)) *(uint16_t *) dp = *(const uint16_t *) sp;
         else st_f(dp, d.type, ld_f(sp, a.type));
     }
 }
@@ -117,7 +120,7 @@ __global__ __launch_bounds__(256) void k_cpy_multi(mi_cpy_batch b) {
         unflatten(i, d.ne, j0, j1, j2, j3);
         const char * sp = a.data + off4(a.nb, i0, i1, i2, i3);
         char * dp = d.data + off4(d.nb, j0, j1, j2, j3);
-        if (a.type == d.type && a.type == MI_TYPE_F16) *(uint16_t *) dp = *(const uint16_t *) sp;
+        if (a.type == d.type && (a.type == MI_TYPE_F16 || a.type == MI_TYPE_BF16)) *(uint16_t *) dp = *(const uint16_t *) sp;
         else st_f(dp, d.type, ld_f(sp, a.type));
     }
 }
@@ -145,7 +148,11 @@ template <int TYPE>
 __device__ __forceinline__ float dequant_elem(const uint8_t * row, int64_t c) {
     constexpr mi_type_info I = mi_type(TYPE);
     constexpr int BS = I.bytes;
-    if constexpr (TYPE == MI_TYPE_Q4_0 || TYPE == MI_TYPE_Q8_0) {  // Q4_0 (18 B) / Q8_0 (34 B) blocks of 32
+    if constexpr (TYPE == MI_TYPE_BF16) {  // dense: the bits are the upper half of the f32 (exact)
+        uint16_t b;
+        __builtin_memcpy(&b, row + c * BS, 2);
+        return mi_bf2f(b);
+    } else if constexpr (TYPE == MI_TYPE_Q4_0 || TYPE == MI_TYPE_Q8_0) {  // Q4_0 (18 B) / Q8_0 (34 B) blocks of 32
         const uint8_t * blk = row + (c >> 5) * BS;
         const int j = (int) (c & 31);
         uint16_t dh;
@@ -276,6 +283,7 @@ __device__ __forceinline__ float emb_elem(const mi_tensor_desc & a, int32_t r, i
     // (f32 / f16 resolved at compile time: a runtime type select put the loads under a branch)
     if constexpr (T == MI_TYPE_F32) return *(const float *) (a.data + c * a.nb[0] + (size_t) r * a.nb[1]);
     else if constexpr (T == MI_TYPE_F16) return mi_h2f(*(const uint16_t *) (a.data + c * a.nb[0] + (size_t) r * a.nb[1]));
+    else if constexpr (T == MI_TYPE_BF16) return mi_bf2f(*(const uint16_t *) (a.data + c * a.nb[0] + (size_t) r * a.nb[1]));
     else return dequant_elem<T>((const uint8_t *) a.data + (size_t) r * a.nb[1], c);
 }
 

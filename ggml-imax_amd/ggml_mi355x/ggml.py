@@ -31,11 +31,12 @@ GGML_TYPE_Q6_K = 14
 GGML_TYPE_Q2_K, GGML_TYPE_Q3_K = 10, 11
 GGML_TYPE_IQ4_NL, GGML_TYPE_IQ4_XS = 20, 23
 GGML_TYPE_Q4_1, GGML_TYPE_Q5_0, GGML_TYPE_Q5_1, GGML_TYPE_Q8_1 = 3, 6, 7, 9
+GGML_TYPE_BF16 = 30
 TYPE_BY_NAME = {"f32": 0, "f16": 1, "q4_0": 2, "q4_1": 3, "q5_0": 6, "q5_1": 7, "q8_0": 8, "q8_1": 9, "q2_K": 10, "q3_K": 11,
-                "q4_K": 12, "q5_K": 13, "q6_K": 14, "iq4_nl": 20, "iq4_xs": 23, "i32": 26}
+                "q4_K": 12, "q5_K": 13, "q6_K": 14, "iq4_nl": 20, "iq4_xs": 23, "i32": 26, "bf16": 30}
 BLOCK = {0: (1, 4), 1: (1, 2), 2: (32, 18), 3: (32, 20), 6: (32, 22), 7: (32, 24), 8: (32, 34), 9: (32, 36), 10: (256, 84),
          11: (256, 110), 12: (256, 144), 13: (256, 176), 14: (256, 210), 20: (32, 18), 23: (256, 136),
-         26: (1, 4)}
+         26: (1, 4), 30: (1, 2)}
 
 GGML_OP_MUL_MAT = 23
 GGML_OP_FLASH_ATTN_EXT = 56
@@ -49,6 +50,21 @@ def row_size(t: int, n: int) -> int:
     blk, sz = BLOCK[t]
     assert n % blk == 0
     return n // blk * sz
+
+
+def f32_to_bf16(x) -> np.ndarray:
+    """float32 values -> bf16 bits (uint16) by ggml_fp32_to_bf16's rules (ggml-impl.h:75-92): a NaN
+    keeps its upper half and is made quiet, a zero exponent field gives a signed zero, the rest
+    rounds to nearest even."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    rne = ((u.astype(np.uint64) + 0x7fff + ((u >> 16) & 1)) >> 16).astype(np.uint32)
+    out = np.where((u & 0x7fffffff) > 0x7f800000, (u >> 16) | 64, np.where((u & 0x7f800000) == 0, (u & 0x80000000) >> 16, rne))
+    return out.astype(np.uint16)
+
+
+def bf16_to_f32(b) -> np.ndarray:
+    """bf16 bits (uint16) -> float32: the bits are the upper half."""
+    return (np.ascontiguousarray(b, np.uint16).astype(np.uint32) << 16).view(np.float32)
 
 
 class ggml_tensor(Structure):
@@ -150,6 +166,12 @@ _SIGS = {
     "ggml_ftype_to_ggml_type": ([c_int], c_int),
     "ggml_fp32_to_fp16": ([c_float], ctypes.c_uint16),
     "ggml_fp16_to_fp32": ([ctypes.c_uint16], c_float),
+    "ggml_fp16_to_fp32_row": ([c_void_p, c_void_p, c_int64], None),
+    "ggml_fp32_to_fp16_row": ([c_void_p, c_void_p, c_int64], None),
+    "ggml_fp32_to_bf16": ([c_float], ctypes.c_uint16),
+    "ggml_bf16_to_fp32": ([ctypes.c_uint16], c_float),
+    "ggml_fp32_to_bf16_row": ([c_void_p, c_void_p, c_int64], None),
+    "ggml_bf16_to_fp32_row": ([c_void_p, c_void_p, c_int64], None),
     # GGUF (include/ggml/ggml.h:2247-2380)
     "gguf_init_empty": ([], c_void_p),
     "gguf_init_from_file": ([c_char_p, gguf_init_params], c_void_p),
@@ -450,6 +472,6 @@ def graph_once(lib: Lib, backend, build, n_tensors: int = 64):
             st = lib.ggml_backend_graph_compute(backend, g)
             assert st == GGML_STATUS_SUCCESS, st
             o = out.contents
-            return tensor_get(lib, out, np.float16 if o.type == GGML_TYPE_F16 else np.float32)
+            return tensor_get(lib, out, np.float16 if o.type == GGML_TYPE_F16 else np.uint16 if o.type == GGML_TYPE_BF16 else np.float32)
         finally:
             lib.ggml_backend_buffer_free(buf)

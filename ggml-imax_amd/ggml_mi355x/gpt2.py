@@ -135,7 +135,9 @@ QUANT_TENSORS = [r"model/wte", r"model/lm_head", r"model/h.*/attn/c_attn/w", r"m
 FTYPES = {"q4_0": (2, G.GGML_TYPE_Q4_0), "q8_0": (7, G.GGML_TYPE_Q8_0), "q4_k": (12, G.GGML_TYPE_Q4_K),
           "q5_k": (13, G.GGML_TYPE_Q5_K), "q6_k": (14, G.GGML_TYPE_Q6_K), "q4_1": (3, G.GGML_TYPE_Q4_1),
           "q5_0": (8, G.GGML_TYPE_Q5_0), "q5_1": (9, G.GGML_TYPE_Q5_1), "q2_k": (10, G.GGML_TYPE_Q2_K),
-          "q3_k": (11, G.GGML_TYPE_Q3_K), "iq4_nl": (19, G.GGML_TYPE_IQ4_NL), "iq4_xs": (22, G.GGML_TYPE_IQ4_XS)}
+          "q3_k": (11, G.GGML_TYPE_Q3_K), "iq4_nl": (19, G.GGML_TYPE_IQ4_NL), "iq4_xs": (22, G.GGML_TYPE_IQ4_XS),
+          # (no target of the reference's quantize.cpp: the bytes of ggml_quantize_chunk under the header its loader accepts)
+          "bf16": (24, G.GGML_TYPE_BF16)}
 GGML_QNT_VERSION, GGML_QNT_VERSION_FACTOR = 2, 1000
 
 

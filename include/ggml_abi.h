@@ -249,6 +249,10 @@ GGML_API float        ggml_fp16_to_fp32(ggml_fp16_t x);
 GGML_API ggml_fp16_t  ggml_fp32_to_fp16(float x);
 GGML_API void         ggml_fp16_to_fp32_row(const ggml_fp16_t * x, float * y, int64_t n);
 GGML_API void         ggml_fp32_to_fp16_row(const float * x, ggml_fp16_t * y, int64_t n);
+GGML_API float        ggml_bf16_to_fp32(ggml_bf16_t x);
+GGML_API ggml_bf16_t  ggml_fp32_to_bf16(float x);
+GGML_API void         ggml_bf16_to_fp32_row(const ggml_bf16_t * x, float * y, int64_t n);
+GGML_API void         ggml_fp32_to_bf16_row(const float * x, ggml_bf16_t * y, int64_t n);
 GGML_API bool         ggml_guid_matches(ggml_guid_t a, ggml_guid_t b);
 GGML_API void         ggml_time_init(void);
 GGML_API int64_t      ggml_time_ms(void);
