@@ -3398,6 +3398,11 @@ int ggml_backend_mi355x_last_launch_count(ggml_backend_t backend) {
     return ((mi_backend_ctx *) backend->context)->last_launches;
 }
 
+const char * ggml_backend_mi355x_last_mul_mat_route(ggml_backend_t backend) {
+    MI_ASSERT(ggml_backend_is_mi355x(backend));
+    return g_mi_last_route;
+}
+
 void ggml_backend_mi355x_set_graph_capture(ggml_backend_t backend, bool enable) {
     MI_ASSERT(ggml_backend_is_mi355x(backend));
     auto * ctx = (mi_backend_ctx *) backend->context;

@@ -474,6 +474,7 @@ __global__ __launch_bounds__(64 * NWV) void k_mmqx(mi_mmx_group g) {
         y_io(lo, false);
         y = lo + y;
     }
+    y = cfold_pos_zero_vec(y);
     y_io(y, true);
 }
 
@@ -728,6 +729,7 @@ __global__ __launch_bounds__(768, 1) void k_mmqw(mi_mmx_group g) {
         y_io(lo, false);
         y = lo + y;
     }
+    y = cfold_pos_zero_vec(y);
     y_io(y, true);
 }
 
@@ -1183,7 +1185,7 @@ __global__ __launch_bounds__(512, 1) void k_mmqt(mi_mmx_group grp) {
     if (n >= N) return;
 #pragma unroll
     for (int ct = 0; ct < 2; ct++) {
-        const f32x16 yv = y[ct] + ex[(rw * 2 + ct) * 64 + lane];  // cfold_end: lo + hi
+        const f32x16 yv = cfold_end_vec(y[ct], ex[(rw * 2 + ct) * 64 + lane]);  // lo + hi
         // element el: prompt column c0 + 32 ct + (el & 3) + 8 (el >> 2) + 4 h
 #pragma unroll
         for (int el = 0; el < 16; el++) {
@@ -1920,6 +1922,8 @@ static void mmq0_group(mi_mmx_group & g, hipStream_t s) {
         if (!q8) hipLaunchKernelGGL((KERN<false, ##__VA_ARGS__>), grid, dim3(NT), 0, s, g);     \
         else hipLaunchKernelGGL((KERN<true, ##__VA_ARGS__>), grid, dim3(NT), 0, s, g);          \
     } while (0)
+    static const char * const kRoutes[] = {"k_mmq0p", "k_mmq0x", "k_mmq0x_half", "k_mmq0x_rows2", "k_mmq0x_rows2_w8"};
+    mi_route(kRoutes[pick]);
     switch (pick) {
         case 0: MI_MMQ0(k_mmq0p, 32, 32, 256); break;  // (a deeper weight ring, RING 3, spills: 36-dword units)
         case 1: MI_MMQ0(k_mmq0x, XBM, XBN, 512, 8, 4); break;
@@ -1996,6 +2000,7 @@ void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
     constexpr int kAsksOther = kMmqShortKernels | kMmqLongKernels | kMmqd1 | kMmqNoD16 | kMmqNoShortT | kMmqd16 | kMmqd16Wide | kMmqp8;
     if (q4 && ncols > 32 && ncols <= 128 && dst_local && g_mi_tuning.mmqt_short > 0 && !(var & kAsksOther) &&
         tiles(128, 64) >= g_mi_tuning.mmqt_short) {
+        mi_route("k_mmqt_short");
         MI_MMQX((k_mmqt<MI_TYPE_Q4_K>), 128, 64, 512, 0);
         return;
     }
@@ -2007,16 +2012,19 @@ void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
         // mul_mat) and alone in a graph (11.5 / 11.4 vs 12.0 / 12.0 us)
         const int64_t lim16 = (var & kMmqd16Wide) ? 128 : (var & kMmqd16) ? 16 : 0;
         if (S <= 16 && ncols <= lim16 && !(var & (kMmqd1 | kMmqNoD16))) {
+            mi_route("k_mmqd16");
             MI_MMQX_T(k_mmqd16, 16, 16, 64 * S, (size_t) S * (64 * 4 + 16) * sizeof(float));
             return;
         }
         // k_mmqd1: one round, a wave per superblock, when asked
         if (S <= 16 && (var & kMmqd1)) {
+            mi_route("k_mmqd1");
             MI_MMQX_T(k_mmqd1, 32, 32, 64 * S, (size_t) S * (64 * 16 + 32) * sizeof(float));
             return;
         }
         // k_mmqp: pipelined 32 x 32 tiles, 4 waves per tile (two workgroups per CU) unless kMmqp8 (8
         // waves, one per CU)
+        mi_route((var & kMmqp8) ? "k_mmqp8" : "k_mmqp");
         if (var & kMmqp8) MI_MMQX_T(k_mmqp, 32, 32, 512, 0, 8);
         else MI_MMQX_T(k_mmqp, 32, 32, 256, 0, 4);
         return;
@@ -2025,6 +2033,7 @@ void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
     // k_mmqx, half-width workgroups (two per CU) when full-width tiles would leave CUs idle: Q4_K
     // B=256 27.8 -> 26.4 us (B=512 41.7 vs 34.7 us: the per-workgroup dequantization then doubles)
     if ((var & kMmqHalfWidth) || (q4 && tiles(XBM, XBN) < 256 && !(var & kMmqFullWidth))) {
+        mi_route("k_mmqx_half");
         MI_MMQX_T(k_mmqx, XBM, 64, 256, 0, 2, 4);
         return;
     }
@@ -2033,6 +2042,7 @@ void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
     // k_mmqw, B=256 18.5 vs 19.7, profiles/r04i_pf_long_mmqt.txt)
     const bool mmqx_asked = (var & (kMmqxOnly | kMmqxLead1)) != 0;
     if (q4 && !mmqx_asked) {
+        mi_route("k_mmqt");
         MI_MMQX((k_mmqt<MI_TYPE_Q4_K>), 128, 64, 512, 0);
         return;
     }
@@ -2040,11 +2050,13 @@ void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
     // k_mmqw: Q5_K, warp-specialized (4 loader + 8 MFMA waves; Q5_K B=512 46.2 -> 43.8 us grouped,
     // profiles/r03r_prefill_mmqw.txt); its loader loop needs S % 4 == 0
     if (!q4 && !mmqx_asked && S % 4 == 0) {
+        mi_route("k_mmqw");
         MI_MMQX((k_mmqw<MI_TYPE_Q5_K, 4>), XBM, XBN, 768, 0);
         return;
     }
 
     // k_mmqx: weight ring depth 4 (kMmqxLead1: 1)
+    mi_route((var & kMmqxLead1) ? "k_mmqx_lead1" : "k_mmqx");
     if (var & kMmqxLead1) MI_MMQX_T(k_mmqx, XBM, XBN, 512, 0, 1);
     else MI_MMQX_T(k_mmqx, XBM, XBN, 512, 0, 4);
 #undef MI_MMQX_T

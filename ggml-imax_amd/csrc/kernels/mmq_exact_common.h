@@ -73,8 +73,18 @@ __device__ __forceinline__ void cfold(float & g, float & y, float & lo, float t,
         }
     }
 }
-__device__ __forceinline__ float cfold_end(float lo, float y) { return lo + y; }
-__device__ __forceinline__ f32x16 cfold_end_vec(const f32x16 & lo, const f32x16 & y) { return lo + y; }
+// The folds begin at -0, so an output whose every term is a zero would come out as -0 where one of them is
+// -0 (d_a < 0 times t = +0, say), while the reference, summing from +0, returns +0. The last step of every
+// kernel adds +0: -0 + 0 == +0, and x + 0 == x for every other x (NaNs included).
+__device__ __forceinline__ float cfold_pos_zero(float y) { return y + 0.0f; }
+__device__ __forceinline__ f32x16 cfold_pos_zero_vec(const f32x16 & y) {
+    f32x16 r;
+#pragma unroll
+    for (int i = 0; i < 16; i++) r[i] = y[i] + 0.0f;
+    return r;
+}
+__device__ __forceinline__ float cfold_end(float lo, float y) { return cfold_pos_zero(lo + y); }
+__device__ __forceinline__ f32x16 cfold_end_vec(const f32x16 & lo, const f32x16 & y) { return cfold_pos_zero_vec(lo + y); }
 // the same for a whole accumulator (sb wave-uniform) without per-element selects; the resets are
 // uniform branches kept as branches (the empty asm stops their if-conversion into 16 v_cndmask
 // per superblock)
@@ -124,7 +134,7 @@ __device__ __forceinline__ float cfold_groups(int ngroups, At && at) {
     float lo = -0.0f, hi = -0.0f;
     for (int v = 0; v < ngroups && v < kCfoldHalf; v++) lo = lo + at(v);
     for (int v = kCfoldHalf; v < ngroups; v++) hi = hi + at(v);
-    return lo + hi;
+    return cfold_end(lo, hi);
 }
 
 template <int TYPE>

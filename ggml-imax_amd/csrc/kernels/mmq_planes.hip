@@ -259,7 +259,7 @@ __global__ __launch_bounds__(512, 1) void k_mmqr(mi_mmx_group grp) {
 
     const int64_t n = n0 + 32 * rw + r;
     if (n >= N) return;
-    const f32x16 yv = lo + y;  // cfold_end
+    const f32x16 yv = cfold_end_vec(lo, y);
 #pragma unroll
     for (int el = 0; el < 16; el++) {
         const int64_t c = c0 + 32 * cw + (el & 3) + 8 * (el >> 2) + 4 * h;
@@ -452,6 +452,7 @@ bool mi_mul_mat_mmqr_group(mi_mmx_group & g, hipStream_t s) {
         g.m[i].tile_begin = tiles;
         tiles += ((g.m[i].N + 63) / 64) * ((g.m[i].act.ncols + 127) / 128);
     }
+    mi_route("k_mmqr");
     hipLaunchKernelGGL((k_mmqr<MI_TYPE_Q4_K>), dim3((unsigned) tiles), dim3(512), 0, s, g);
     return true;
 }

@@ -24,6 +24,8 @@
 //   IQ4_XS x Q8_K ggml_vec_dot_iq4_xs_q8_K src/ggml-quants.c:11873-11967
 // (F16 and F32 live in mmv_ordered.hip: bit-exact CPU summation order.)
 
+#include <string>
+
 #include "mi355x_common.h"
 #include "mi355x_kernels.h"
 
@@ -959,6 +961,11 @@ static void mmv_launch(const mi_mm_desc & m, const mi_act_q8 & act, unsigned gri
                     grid_y ? grid_y : (unsigned) (g.col_chunks * m.ne12 * m.ne13));
     const uint8_t * W = (const uint8_t *) m.W;
     constexpr bool Q5 = T == MI_TYPE_Q5_K;
+    // the route's name, built once per instance: kernel family, order, columns per workgroup, MUL_MAT_ID form
+    static const std::string route = std::string(mi_type(T).blck == 32 ? "k_mmv_q0" : T == MI_TYPE_Q6_K ? "k_mmv_q6k" :
+                                                 T == MI_TYPE_Q2_K || T == MI_TYPE_Q3_K ? "k_mmv_q23k" : T == MI_TYPE_IQ4_XS ? "k_mmv_iq4xs" : "k_mmv_kq") +
+                                     (ORD ? "_ord" : "") + "<nc" + std::to_string(NC) + (ID == 1 ? ",id_pairs" : ID == 2 ? ",id_grouped" : "") + ">";
+    mi_route(route.c_str());
     if constexpr (mi_type(T).blck == 32) {
         if constexpr (ORD) hipLaunchKernelGGL((k_mmv_q0_ord<NC, T, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);
         else hipLaunchKernelGGL((k_mmv_q0<NC, T, ID>), grid, dim3(256), 0, s, W, act, m.dst, g);

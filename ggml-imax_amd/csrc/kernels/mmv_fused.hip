@@ -96,6 +96,7 @@ mi_tuning tuning_from_env() {
 
 mi_tuning g_mi_tuning = tuning_from_env();
 thread_local int tl_mi_graph_order = 0;
+const char * g_mi_last_route = "";
 
 bool mi_tuning_set(const char * name, int value) { return knob_set(g_mi_tuning, name, value); }
 

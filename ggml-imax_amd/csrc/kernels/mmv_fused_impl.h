@@ -4,6 +4,8 @@
 // exports one mi_mmv_launch_* entry point that mmv_fused.hip's dispatcher calls.
 #pragma once
 
+#include <stdio.h>
+
 #include <type_traits>
 
 #include "mi355x_common.h"
@@ -2136,6 +2138,20 @@ static int mi_cu_count() {
     return n;
 }
 
+// The route string of one k_mmv_stream instance (g_mi_last_route), built once per instance: the weight
+// format (the ggml type number unless the format reads pairs of blocks or a repacked copy) and the
+// template arguments that tell the instances apart.
+template <class F, int NC, int PD, int IPL, bool TAIL, bool ORD, bool PRO, bool XF, int MR, bool IDS>
+const char * stream_route(int type) {
+    static char name[96] = "";
+    if (!name[0]) {
+        const char * fmt = std::is_same<F, FmtQ0Pair>::value ? "pairs," : std::is_same<F, FmtQ0R>::value || std::is_same<F, FmtQ8R>::value ? "repacked," : "";
+        snprintf(name, sizeof(name), "k_mmv_stream<type%d,%snc%d,pd%d,ipl%d,tail%d,ord%d,pro%d,xf%d,mr%d,ids%d>", type, fmt, NC, PD, IPL,
+                 (int) TAIL, (int) ORD, (int) PRO, (int) XF, MR, (int) IDS);
+    }
+    return name;
+}
+
 template <class F, int NC, int PD, int IPL, bool TAIL, bool ORD, bool PRO = false, bool XF = false, int MR = 1, bool IDS = false>
 void launch_one(mi_mmv_group g, hipStream_t s) {
     const size_t act = lds_bytes<F::QKA>(NC, g.K);
@@ -2197,6 +2213,7 @@ void launch_one(mi_mmv_group g, hipStream_t s) {
     rows = (rows + 3) / 4 * 4;
     g.rows_per_block = rows;
     g.blocks_per_member = (int) ((g.N + rows - 1) / rows);
+    mi_route(stream_route<F, NC, PD, IPL, TAIL, ORD, PRO, XF, MR, IDS>(g.type));
     hipLaunchKernelGGL((k_mmv_stream<F, NC, PD, IPL, TAIL, ORD, PRO, XF, MR, IDS>), dim3((unsigned) (g.blocks_per_member * g.n)), dim3(256), lds,
                        s, g);
 }

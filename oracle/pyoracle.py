@@ -87,6 +87,17 @@ def dequantize(t: int, q: np.ndarray, n: int) -> np.ndarray:
     return out
 
 
+def mul_mat_q8(t: int, wq: np.ndarray, K: int, N: int, xq: np.ndarray, B: int) -> np.ndarray:
+    """mul_mat with src1 already rows of the weight's vec_dot type (read as they lie): vec_dot per (row, column)."""
+    wq, xq = np.ascontiguousarray(wq), np.ascontiguousarray(xq)
+    wr, xr = row_size(t, K), row_size(vec_dot_type(t), K)
+    L, y = lib(), np.empty(N * B, dtype=np.float32)
+    for c in range(B):
+        for r in range(N):
+            y[c * N + r] = L.orc_vec_dot(t, K, ctypes.c_void_p(wq.ctypes.data + r * wr), ctypes.c_void_p(xq.ctypes.data + c * xr))
+    return y
+
+
 def mul_mat(t: int, wq: np.ndarray, K: int, N: int, x: np.ndarray, B: int, nthreads: int = 8) -> np.ndarray:
     wq = np.ascontiguousarray(wq)
     x = np.ascontiguousarray(x, dtype=np.float32)
