@@ -415,12 +415,12 @@ static const ggml_backend_buffer_type_i k_mi_split_buft_i = {
 
 // The form a mul_mat's activation columns are converted to: how they are quantized (the weight
 // type's vec_dot_type; MI_ACT_NONE: src1 is read as it lies, F32 weights) and how they are laid out.
-// Valid pairs: q8_0 / q8_1 / q8_K in SOA; q8_0 / q8_K in ROWS, BLOCKED (their f16 expansion
-// f16(d * q), the operand of mmq.hip) and MFMA; f16 in ROWS and BLOCKED (plain f16 values).
+// Valid pairs: q8_0 / q8_1 / q8_K in SOA; q8_0 / q8_K in MFMA; f16 in ROWS and BLOCKED; bf16 in ROWS.
+// ROWS and BLOCKED hold f16 or bf16 elements only, never quantized activations.
 enum mi_act_layout : int {
     MI_LAYOUT_SOA,      // the GEMVs' structure-of-arrays (mi_act_q8)
-    MI_LAYOUT_ROWS,     // f16, row-major [ncols][K]
-    MI_LAYOUT_BLOCKED,  // f16, the GEMM's K-blocked layout [K/16][ncols][16]
+    MI_LAYOUT_ROWS,     // f16 / bf16 elements, row-major [ncols][K]
+    MI_LAYOUT_BLOCKED,  // f16 elements, the F16 prompt GEMMs' K-blocked layout [K/16][ncols][16] (mmq.hip)
     MI_LAYOUT_MFMA,     // the int8-MFMA layouts of the exact prefill GEMMs (mi_act_mmx, mmq_exact.hip)
 };
 struct mi_act_format {
@@ -754,7 +754,6 @@ static void * get_activations(mi_backend_ctx * ctx, const ggml_tensor * src1, mi
     const int64_t ncols = src1->ne[1] * src1->ne[2] * src1->ne[3];
     void * dev = scratch_take(ctx, act_bytes(f, K, ncols));
     const mi_src_cols x = src_cols(src1);
-    const bool blocked = f.layout == MI_LAYOUT_BLOCKED;
     if (q8_quant_of(src1->type) != MI_ACT_NONE) {
         // already quantized by the reference's rules (e.g. a CPY F32 -> Q8_K): re-laid out only
         MI_ASSERT(q8_quant_of(src1->type) == f.quant);
@@ -783,10 +782,9 @@ static void * get_activations(mi_backend_ctx * ctx, const ggml_tensor * src1, mi
         // bf16 rows (ggml_fp32_to_bf16_row's bits; a BF16 src1 is copied as it lies): never the f16 converter
         MI_ASSERT(f.layout == MI_LAYOUT_ROWS);
         mi_convert_bf16(x, K, (uint16_t *) dev, (int) src1->type, ctx->stream);
-    } else if (f.quant == MI_ACT_F16) {
-        mi_convert_f16(x, K, (uint16_t *) dev, ctx->stream, blocked, src1->type == GGML_TYPE_F16);
     } else {
-        mi_quantize_expand_f16(x, K, ncols, f.quant, (uint16_t *) dev, ctx->stream, blocked);
+        MI_ASSERT(f.quant == MI_ACT_F16);
+        mi_convert_f16(x, K, (uint16_t *) dev, ctx->stream, f.layout == MI_LAYOUT_BLOCKED, src1->type == GGML_TYPE_F16);
     }
     ctx->last_launches++;
     cache_activations(ctx, src1, f, dev);
@@ -807,34 +805,25 @@ static void invalidate_activations(mi_backend_ctx * ctx, const ggml_tensor * wri
             c.end());
 }
 
-// the batched (prompt) GEMM applies: more than 8 columns of plain 2-D operands
+// a batched (prompt) GEMM applies: more than 8 columns of plain 2-D operands that the F16 GEMMs
+// (mmq.hip) resp. the exact int8 GEMMs (mmq_exact.hip) accept. Every other weight type, and a
+// quantized shape the exact GEMM refuses (a row stride that is no multiple of 16 bytes, say), runs
+// the prompt on its GEMV in 8-column chunks.
 static bool mm_batched(const mi_mm_desc & m, const ggml_tensor * src1) {
     static const bool no_mmq = getenv("GGML_MI355X_NO_MMQ") != nullptr;
-    return !no_mmq && mi_type(m.type).act != MI_ACT_NONE && src1->ne[1] > 8 && m.ne02 == 1 && m.ne03 == 1 && m.ne12 == 1 &&
-           m.ne13 == 1 && mi_mmq_supported(m.type, m.K, m.nb01, m.nb1) && ((uintptr_t) m.W % 16) == 0;
+    if (no_mmq || src1->ne[1] <= 8 || m.ne02 != 1 || m.ne03 != 1 || m.ne12 != 1 || m.ne13 != 1 || ((uintptr_t) m.W % 16) != 0) return false;
+    if (m.type == GGML_TYPE_F16) return mi_mmq_supported(m.K, m.nb01, m.nb1);
+    return mi_mmqx_supported(m.type, m.K, m.nb1, src1->ne[1], m.nb01);
 }
 
 // The activation format mul_mat_run converts src1 to for this mul_mat (quant MI_ACT_NONE, F32
-// weights: src1 is read as it lies). Q4_K / Q5_K / Q4_0 / Q8_0 prompts: the exact-integer int8
-// GEMM's MFMA layouts of their quantization; F16 prompts: f16 rows, or K-blocked; decode: the
-// weight type's own format (q8 SoA or f16 rows). Q6_K has neither an exact MFMA GEMM nor a
-// dequantizer in the f16 GEMM (mi_mmq_supported / mi_mmqx_supported refuse it): q8_K SoA at any
-// column count, the GEMV runs the prompt in 8-column chunks. Q4_1 / Q5_0 / Q5_1 likewise: q8_1
-// resp. q8_0 SoA at any column count.
+// weights: src1 is read as it lies). Batched (mm_batched): the exact-integer int8 GEMMs' MFMA layouts
+// for Q4_K / Q5_K / Q4_0 / Q8_0 prompts, the K-blocked f16 layout for F16 prompts. Everything else: the
+// weight type's own format (q8 SoA, f16 / bf16 rows) at any column count; the quantized GEMVs run a
+// prompt in 8-column chunks.
 static mi_act_format mm_act_format(const mi_mm_desc & m, const ggml_tensor * src1) {
     mi_act_format f = act_format_of((ggml_type) m.type);
-    if (f.quant == MI_ACT_NONE || f.quant == MI_ACT_Q8_1 || !mm_batched(m, src1)) return f;
-    const int64_t ncols = src1->ne[1] * src1->ne[2] * src1->ne[3];
-    const bool exact = f.quant != MI_ACT_F16 && mi_mmqx_supported(m.type, m.K, m.nb1, ncols, m.nb01);
-    if (src1->type != GGML_TYPE_F32 && src1->type != GGML_TYPE_F16) {
-        // pre-quantized src1 (Q8_K / Q8_0 rows): the exact GEMMs' layouts, else the GEMV's
-        if (exact) f.layout = MI_LAYOUT_MFMA;
-        return f;
-    }
-    // mmq_variant bit kMmqF16Gemm selects the f16 GEMM for the quantized types too (A/B
-    // timing; the low bits are mmq_exact.hip's own kernel variants)
-    if (exact && (g_mi_tuning.mmq_variant & kMmqF16Gemm) == 0) f.layout = MI_LAYOUT_MFMA;
-    else f.layout = mi_mmq_wants_blocked() ? MI_LAYOUT_BLOCKED : MI_LAYOUT_ROWS;  // the f16 GEMM's operand: same quantization, expanded
+    if (mm_batched(m, src1)) f.layout = f.quant == MI_ACT_F16 ? MI_LAYOUT_BLOCKED : MI_LAYOUT_MFMA;
     return f;
 }
 
@@ -938,13 +927,11 @@ static void mul_mat_run(mi_backend_ctx * ctx, const ggml_tensor * src0, const vo
                 if (f.quant == MI_ACT_BF16) {
                     // BF16 weights: their own kernels at any column count and shape (mm_bf16.hip)
                     mi_mul_mat_bf16(m, xh, ctx->stream);
-                } else if (f.quant == MI_ACT_F16 && f.layout == MI_LAYOUT_BLOCKED && mi_mmf16p_supported(m.K, m.N, m.nb01, ncols, m.nb1)) {
+                } else if (f.layout == MI_LAYOUT_BLOCKED && mi_mmf16p_supported(m.K, m.N, m.nb01, ncols, m.nb1)) {
                     // F16 weights, a short prompt: 32 x 32 tiles with the K split over each tile's 4 waves
                     mi_mul_mat_f16p(m.W, m.nb01, m.K, m.N, xh, ncols, m.dst, m.nb1, ctx->stream);
-                } else if (f.quant != MI_ACT_F16 || f.layout == MI_LAYOUT_BLOCKED || mm_batched(m, src1)) {
-                    // the GEMM's activation operand: f16 for F16 weights, else f16(d * q) of the q8 quants
-                    // written by the quantizer itself
-                    mi_mul_mat_mmq(m.type, m.W, m.nb01, m.K, m.N, mi_act_q8{}, xh, ncols, m.dst, m.nb1, nullptr, ctx->stream);
+                } else if (f.layout == MI_LAYOUT_BLOCKED) {
+                    mi_mul_mat_mmq(m.W, m.nb01, m.K, m.N, xh, ncols, m.dst, m.nb1, ctx->stream);
                 } else {
                     mi_mul_mat_f16(m, xh, ctx->stream);  // f16 rows of a mul_mat that is not batched: the F16 GEMV
                 }
@@ -1530,18 +1517,17 @@ static size_t graph_scratch_bytes(const ggml_cgraph * cgraph) {
             // sums (try_fuse_attn_proj; head dim >= 64, so at most K / 64 heads)
             total += ((size_t) (n->src[0]->ne[0] / 64) * n->src[0]->ne[1] * sizeof(float) + kBufferAlign - 1) & ~(kBufferAlign - 1);
         }
-        // The weight type's own format (q8 SoA or f16 rows) always; plus, above 8 columns, the
-        // larger of the f16 GEMM's operand and the exact GEMMs' MFMA layout, where the type has one --
-        // both counted, the choice is made at run time. Q8_1 activations feed the GEMVs only.
+        // The weight type's own format (q8 SoA, f16 / bf16 rows) always; plus, above 8 columns, the
+        // layout of the type's prompt GEMM where it has one (mm_act_format: K-blocked f16 or the exact
+        // GEMMs' MFMA layout) -- both counted, the choice is made at run time.
         const mi_act_format f = act_format_of(n->src[0]->type);
         if (f.quant == MI_ACT_NONE) continue;
         const ggml_tensor * b = n->src[1];
         const int64_t ncols = b->ne[1] * b->ne[2] * b->ne[3];
         total += (act_bytes(f, b->ne[0], ncols) + kBufferAlign - 1) & ~(kBufferAlign - 1);
-        if (ncols > 8 && f.quant != MI_ACT_Q8_1 && f.quant != MI_ACT_BF16) {
-            const size_t big = std::max(act_bytes({f.quant, MI_LAYOUT_ROWS}, b->ne[0], ncols),
-                                        f.quant != MI_ACT_F16 ? act_bytes({f.quant, MI_LAYOUT_MFMA}, b->ne[0], ncols) : 0);
-            total += (big + kBufferAlign - 1) & ~(kBufferAlign - 1);
+        if (ncols > 8 && (f.quant == MI_ACT_F16 || mi_type(n->src[0]->type).mmqx)) {
+            const mi_act_layout gemm = f.quant == MI_ACT_F16 ? MI_LAYOUT_BLOCKED : MI_LAYOUT_MFMA;
+            total += (act_bytes({f.quant, gemm}, b->ne[0], ncols) + kBufferAlign - 1) & ~(kBufferAlign - 1);
         }
     }
     return total;

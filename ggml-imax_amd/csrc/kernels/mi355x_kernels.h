@@ -71,15 +71,9 @@ mi_act_q8 mi_act_q8_carve(void * base, int64_t K, int64_t ncols, mi_act_quant q)
 void mi_quantize_q8_0(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, hipStream_t s);
 void mi_quantize_q8_1(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, hipStream_t s);
 void mi_quantize_q8_K(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, hipStream_t s);
-// blocked: write the GEMM's K-blocked layout [K/16][ncols][16] instead of [ncols][K];
+// blocked: write the F16 prompt GEMMs' K-blocked layout [K/16][ncols][16] instead of [ncols][K];
 // src_f16: the columns are f16 already (copied, not rounded)
 void mi_convert_f16(const mi_src_cols & x, int64_t K, uint16_t * out, hipStream_t s, bool blocked = false, bool src_f16 = false);
-// quantize to q8_K / q8_0 exactly as above and store f16(d * q) as [ncols][K] (no q8 blocks):
-// the activation operand of mi_mul_mat_mmq for quantized weights
-void mi_quantize_expand_f16(const mi_src_cols & x, int64_t K, int64_t ncols, mi_act_quant q, uint16_t * xh, hipStream_t s,
-                            bool blocked = false);
-// the layout mi_mul_mat_mmq expects for xh under the current tuning (true: K-blocked)
-bool mi_mmq_wants_blocked();
 
 // quantized weights x quantized activations (integer dot products), any number of columns
 void mi_mul_mat_q(const mi_mm_desc & m, const mi_act_q8 & act, hipStream_t s);
@@ -149,7 +143,7 @@ struct mi_tuning {
     int mmv_variant = 0;   // 10*prefetch_depth + {0: activations in VGPRs, 1: from LDS, 2: LDS + waves/EU cap}; 0: the per-type default
     int f16_variant = 0;   // decode F16 GEMV: 0 = 16 lanes per row (k_mmv_f16_w16), 1 = quad per row (k_mmv_f16_x)
     int f16_threads = 0;   // k_mmv_f16_w16 workgroup size override (0 = automatic)
-    int mmq_variant = 0;   // prefill GEMMs: A/B selection bits (mi_mmq_variant_bits below); 0 = the defaults
+    int mmq_variant = 0;   // exact prefill GEMMs: bits that move a launcher's decision to another column count (mi_mmq_variant_bits below; any other bit is refused); 0 = the defaults
     int attn_variant = 0;  // attention block: 0 = k_attn_fast where it fits, 1 = k_attn_ordered
     int mmv_order = -1;    // decode GEMVs (quantized and F16) and attention: 1 = the reference CPU's summation order (bit-identical,
                            // slower), 0 = tree sums, -1 (default) = per graph: 1 where a quantized MUL_MAT consumes a value the
@@ -157,7 +151,6 @@ struct mi_tuning {
     int f16_waves = 0;     // fast F16 decode GEMV: target waves on the chip (0 = automatic)
     int f16_rgs = 0;       // fast F16 decode GEMV: row groups (4 rows) per workgroup (0 = automatic)
     int f16_ps_waves = 0;  // k_gemv_f16_ps (GEMV over summed partials): waves per workgroup, 2 / 4 / 8 (0 = automatic)
-    int xfirst = -1;       // lone decode GEMVs: activation loads issued and landed before the weight loads: 1 always, 0 / -1 never (-1: the default)
     int f16_norm_waves = 0;  // F16 GEMV, several columns with the norm prologue: waves per workgroup (0 = automatic)
     int planes = 0;        // long Q4_K prompts on repacked MFMA planes (mmq_planes.hip k_mmqr): 1 on, 0 off (default: slower than k_mmqt with HBM-streamed weights)
     int f16_nc = 10;       // F16 decode GEMVs: columns per workgroup at most (ones digit: plain, tens: norm prologue; 0: up to 8)
@@ -178,29 +171,20 @@ struct mi_tuning {
 };
 // looks `name` up in the knob table; false: unknown name or a value outside the knob's range
 bool mi_tuning_set(const char * name, int value);
-// mmq_variant bits. Within a weight-format family every kernel keeps the family's canonical combine,
-// so any choice gives the same bits; a bit only picks the kernel.
+// mmq_variant bits (mmq_exact.hip's two dispatch functions). All but kMmq0xRows2W8 make a kernel that the default
+// decisions also reach run at another column count or tile count -- the tests reach k_mmqt / k_mmqw / k_mmqx /
+// k_mmq0x with a 68-column prompt that way. Within a weight-format family every kernel keeps the family's canonical
+// combine, so any choice gives the same bits. The values are fixed; set_tuning refuses any bit outside kMmqVariantMask.
 enum mi_mmq_variant_bits : int {
-    kMmqActLds = 1,              // f16 GEMM (mmq.hip): k_mmq2, row-major activations via LDS (k_mmq3 / k_mmf16p read the K-blocked layout)
-    kMmqXcdOrder = 2,            // f16 GEMM: k_mmq3 with XCD-contiguous tile order
-    kMmqShortKernels = 16,       // exact GEMMs: the short-prompt kernels (k_mmqp / k_mmq0p) at any column count
-    kMmqxLead1 = 64,             // Q4_K / Q5_K long prompts: k_mmqx with a weight ring of 1
-    kMmqLongKernels = 128,       // exact GEMMs: the long-prompt kernels of the canonical blocks at any column count (k_mmq0x: 8 waves, 64 x 128)
-    kMmqd1 = 2048,               // Q4_K / Q5_K short prompts, K <= 4096: k_mmqd1 (a wave per superblock)
-    kMmqNoD16 = 4096,            // Q4_K / Q5_K short prompts: k_mmqp even where bits 2^21 / 2^22 ask for k_mmqd16
-    kMmqNoShortT = 8192,         // Q4_K prompts of 33..128 columns: never k_mmqt (as mmqt_short 0)
+    kMmqShortKernels = 16,       // the short-prompt kernels (k_mmqp / k_mmq0p) at any column count
+    kMmqLongKernels = 128,       // the long prompts' decision at any column count (Q4_0 / Q8_0: k_mmq0x NR = 2, 64 x 128)
     kMmqHalfWidth = 1 << 16,     // k_mmqx / k_mmq0x: half-width workgroups (64 x 64 tiles, 4 waves)
     kMmqFullWidth = 1 << 17,     // Q4_K: no automatic half-width k_mmqx below 256 full tiles
-    kMmqNoF16p = 1 << 18,        // F16 weights, 9..128 columns: k_mmq3 instead of k_mmf16p
-    kMmqF16p8 = 1 << 20,         // k_mmf16p: 8 waves per tile (K % 512 == 0, fewer than 512 tiles)
-    kMmqd16 = 1 << 21,           // Q4_K / Q5_K, K <= 4096: k_mmqd16 (16 x 16 tiles) up to 16 columns
-    kMmqd16Wide = 1 << 22,       // the same up to 128 columns
-    kMmq0xRows2 = 1 << 24,       // with kMmqLongKernels, Q4_0 / Q8_0: k_mmq0x NR = 2 (4 waves, 64 x 128)
-    kMmq0xRows2W8 = 1 << 25,     // with kMmqLongKernels, Q4_0 / Q8_0: k_mmq0x NR = 2 with 8 waves (64 x 256)
-    kMmqp8 = 1 << 27,            // k_mmqp: 8 waves per tile (one workgroup per CU)
+    kMmq0xRows2 = 1 << 24,       // with kMmqLongKernels, Q4_0 / Q8_0: k_mmq0x NR = 2 even with kMmqHalfWidth
+    kMmq0xRows2W8 = 1 << 25,     // with kMmqLongKernels, Q4_0 / Q8_0: k_mmq0x NR = 2 with 8 waves (64 x 256; never a default, see mmq0_group)
     kMmqxOnly = 1 << 28,         // Q4_K / Q5_K long prompts: k_mmqx instead of k_mmqt / k_mmqw
-    kMmqF16Gemm = 1 << 30,       // quantized prompts on the f16 GEMM (mi_mul_mat_mmq) instead of the exact-integer kernels
 };
+constexpr int kMmqVariantMask = kMmqShortKernels | kMmqLongKernels | kMmqHalfWidth | kMmqFullWidth | kMmq0xRows2 | kMmq0xRows2W8 | kMmqxOnly;
 extern mi_tuning g_mi_tuning;
 // the order of the graph being launched when mmv_order is -1 (set by the backend per graph)
 extern thread_local int tl_mi_graph_order;
@@ -215,21 +199,16 @@ void mi_mul_mat_q_fused(mi_mmv_group & g, hipStream_t s);
 // its per-format launchers, specialized in mmv_fused_q2k.hip, _q3k, _q4k, _q5k, _q6k, _q40, _q80, _q41, _q50, _q51, _iq4nl, _iq4xs (one
 // translation unit each, so that the formats build in parallel)
 template <int T> void mi_mmv_launch(const mi_mmv_group & g, int variant, hipStream_t s);
-// Batched (prefill) mul_mat on MFMA: 2-D weights [K, N] of type Q4_0/Q8_0/Q4_K/Q5_K/F16,
-// `ncols` activation columns already converted: xh = f16 [ncols][K] (F16 weights: the f16
-// activations; quantized weights: f16(d * q) from mi_quantize_expand_f16), or, for quantized
-// weights with xh == nullptr, the q8 blocks in act expanded into `scratch` first.
-// dst columns of ycol bytes. Requires K % 256 == 0.
-bool mi_mmq_supported(int type, int64_t K, size_t nb01, size_t ycol);
-// F16 weights, 9..128 columns (mmq.hip k_mmf16p): xh = f16 activations in the K-blocked layout
-// [K/16][ncols][16]; K % 256 == 0, 16-byte aligned rows (mmq_variant bits kMmqActLds / kMmqNoF16p turn it off)
+// Batched (prefill) mul_mat of F16 weights on MFMA (mmq.hip): 2-D weights [K, N], `ncols` f16 activation
+// columns xh in the K-blocked layout [K/16][ncols][16] (mi_convert_f16), dst columns of ycol bytes.
+// K % 256 == 0, 16-byte aligned weight rows and dst columns.
+bool mi_mmq_supported(int64_t K, size_t nb01, size_t ycol);
+void mi_mul_mat_mmq(const void * W, size_t nb01, int64_t K, int64_t N, const uint16_t * xh, int64_t ncols, float * dst, size_t ycol,
+                    hipStream_t s);
+// 9..128 columns (k_mmf16p): 32 x 32 tiles, K split over a tile's 4 waves; the same operands
 bool mi_mmf16p_supported(int64_t K, int64_t N, size_t nb01, int64_t ncols, size_t ycol);
 void mi_mul_mat_f16p(const void * W, size_t nb01, int64_t K, int64_t N, const uint16_t * xh, int64_t ncols, float * dst, size_t ycol,
                      hipStream_t s);
-// scratch for the f16 expansion of quantized activations when xh == nullptr (0 for F16 weights)
-size_t mi_mmq_scratch_bytes(int type, int64_t K, int64_t ncols);
-void mi_mul_mat_mmq(int type, const void * W, size_t nb01, int64_t K, int64_t N, const mi_act_q8 & act, const uint16_t * xh,
-                    int64_t ncols, float * dst, size_t ycol, uint16_t * scratch, hipStream_t s);
 
 // ---- exact-integer prefill GEMM for Q4_K / Q5_K (mmq_exact.hip) ----
 // q8_K activation quants in the int8-MFMA layouts: xq [K/64][ncols][64] int8, xd [K/256][ncols]
@@ -422,7 +401,6 @@ struct mi_f16_epilogue {
         char * ptr = nullptr;
         size_t col_stride = 0;
     } copy[2];
-    int xfirst = 0;               // set by the launcher (g_mi_tuning.xfirst): activations landed before the weight loads
 };
 // optional prologue: src1 = add(mul(norm|rms_norm(x, eps), g), b) computed in the kernel from x
 struct mi_norm_prologue {

@@ -48,7 +48,6 @@ struct mi_type_info {
     int mmv_variant;   // streaming decode GEMV (mi_mul_mat_q_fused): its default mmv_variant, 0: no such kernel
     int mmv_align;     // ... and the weight row alignment it needs (the tensor base: 16)
     bool mmqx;         // exact int8 prefill GEMM (mmq_exact.hip)
-    bool mmq;          // f16 GEMM dequantizer (mmq.hip)
     bool planes;       // repacked MFMA planes for long prompts (mmq_planes.hip k_mmqr)
     bool aligned_copy; // 16-byte-aligned decode copy (mmq_planes.hip k_q40_repack / k_q80_repack): as many bytes a row as the blocks
     bool get_rows;     // GET_ROWS reads it (f32 / f16 elements, or the dequantizer of ops.hip)
@@ -72,26 +71,26 @@ struct mi_type_info {
 // odd superblock count are 8 mod 16: K = 11008 has 5848-byte rows): 8.
 // planes: Q5_K has the plane format (PFmt) and its repack kernel, but no GEMM that reads them.
 constexpr mi_type_info kMiTypes[] = {
-    //  type         blck bytes act          has_m  has_qh sub  lut    mmv  align mmqx   mmq    planes copy   get_rows
-    {MI_TYPE_F32,    1,   4,   MI_ACT_NONE, false, false, 0,   false, 0,   16,   false, false, false, false, true},
-    {MI_TYPE_F16,    1,   2,   MI_ACT_F16,  false, false, 0,   false, 0,   16,   false, true,  false, false, true},
-    // (BF16: its own kernels, mm_bf16.hip. Never the f16-operand GEMM of mmq.hip or mi_convert_f16: bf16's
+    //  type         blck bytes act          has_m  has_qh sub  lut    mmv  align mmqx   planes copy   get_rows
+    {MI_TYPE_F32,    1,   4,   MI_ACT_NONE, false, false, 0,   false, 0,   16,   false, false, false, true},
+    {MI_TYPE_F16,    1,   2,   MI_ACT_F16,  false, false, 0,   false, 0,   16,   false, false, false, true},
+    // (BF16: its own kernels, mm_bf16.hip. Never the F16 GEMMs of mmq.hip or mi_convert_f16: bf16's
     // exponent range does not fit f16. Rows of an odd K are 2-byte aligned: its launchers pick the path.)
-    {MI_TYPE_BF16,   1,   2,   MI_ACT_BF16, false, false, 0,   false, 0,   2,    false, false, false, false, true},
-    {MI_TYPE_Q4_0,   32,  18,  MI_ACT_Q8_0, false, false, 8,   false, 32,  16,   true,  true,  false, true,  true},
-    {MI_TYPE_Q4_1,   32,  20,  MI_ACT_Q8_1, true,  false, 0,   false, 21,  16,   false, false, false, false, true},
-    {MI_TYPE_Q5_0,   32,  22,  MI_ACT_Q8_0, false, true,  16,  false, 21,  16,   false, false, false, false, true},
-    {MI_TYPE_Q5_1,   32,  24,  MI_ACT_Q8_1, true,  true,  0,   false, 21,  16,   false, false, false, false, true},
-    {MI_TYPE_Q8_0,   32,  34,  MI_ACT_Q8_0, false, false, 0,   false, 11,  16,   true,  true,  false, true,  true},
-    {MI_TYPE_Q2_K,   256, 84,  MI_ACT_Q8_K, false, false, 0,   false, 21,  4,    false, false, false, false, true},
-    {MI_TYPE_Q3_K,   256, 110, MI_ACT_Q8_K, false, false, 0,   false, 11,  2,    false, false, false, false, true},
-    {MI_TYPE_Q4_K,   256, 144, MI_ACT_Q8_K, false, false, 0,   false, 31,  16,   true,  true,  true,  false, true},
-    {MI_TYPE_Q5_K,   256, 176, MI_ACT_Q8_K, false, false, 0,   false, 21,  16,   true,  true,  false, false, true},
-    {MI_TYPE_Q6_K,   256, 210, MI_ACT_Q8_K, false, false, 0,   false, 21,  2,    false, false, false, false, true},
-    {MI_TYPE_IQ4_NL, 32,  18,  MI_ACT_Q8_0, false, false, 0,   true,  21,  16,   false, false, false, false, true},
-    {MI_TYPE_IQ4_XS, 256, 136, MI_ACT_Q8_K, false, false, 0,   true,  21,  8,    false, false, false, false, true},
+    {MI_TYPE_BF16,   1,   2,   MI_ACT_BF16, false, false, 0,   false, 0,   2,    false, false, false, true},
+    {MI_TYPE_Q4_0,   32,  18,  MI_ACT_Q8_0, false, false, 8,   false, 32,  16,   true,  false, true,  true},
+    {MI_TYPE_Q4_1,   32,  20,  MI_ACT_Q8_1, true,  false, 0,   false, 21,  16,   false, false, false, true},
+    {MI_TYPE_Q5_0,   32,  22,  MI_ACT_Q8_0, false, true,  16,  false, 21,  16,   false, false, false, true},
+    {MI_TYPE_Q5_1,   32,  24,  MI_ACT_Q8_1, true,  true,  0,   false, 21,  16,   false, false, false, true},
+    {MI_TYPE_Q8_0,   32,  34,  MI_ACT_Q8_0, false, false, 0,   false, 11,  16,   true,  false, true,  true},
+    {MI_TYPE_Q2_K,   256, 84,  MI_ACT_Q8_K, false, false, 0,   false, 21,  4,    false, false, false, true},
+    {MI_TYPE_Q3_K,   256, 110, MI_ACT_Q8_K, false, false, 0,   false, 11,  2,    false, false, false, true},
+    {MI_TYPE_Q4_K,   256, 144, MI_ACT_Q8_K, false, false, 0,   false, 31,  16,   true,  true,  false, true},
+    {MI_TYPE_Q5_K,   256, 176, MI_ACT_Q8_K, false, false, 0,   false, 21,  16,   true,  false, false, true},
+    {MI_TYPE_Q6_K,   256, 210, MI_ACT_Q8_K, false, false, 0,   false, 21,  2,    false, false, false, true},
+    {MI_TYPE_IQ4_NL, 32,  18,  MI_ACT_Q8_0, false, false, 0,   true,  21,  16,   false, false, false, true},
+    {MI_TYPE_IQ4_XS, 256, 136, MI_ACT_Q8_K, false, false, 0,   true,  21,  8,    false, false, false, true},
 };
-constexpr mi_type_info kMiNoType = {-1, 1, 0, MI_ACT_NONE, false, false, 0, false, 0, 16, false, false, false, false, false};
+constexpr mi_type_info kMiNoType = {-1, 1, 0, MI_ACT_NONE, false, false, 0, false, 0, 16, false, false, false, false};
 
 // the row of `type` (kMiNoType: none): a compile-time constant in kernels, a lookup on the host
 constexpr mi_type_info mi_type(int type) {

@@ -733,10 +733,10 @@ __global__ __launch_bounds__(768, 1) void k_mmqw(mi_mmx_group g) {
     y_io(y, true);
 }
 
-// ---- short prompts, pipelined: 8 waves per tile, one superblock group each -----------------------
+// ---- short prompts, pipelined: 4 waves per tile, two superblock groups each ----------------------
 // A workgroup computes one tile of 32 weight rows x 32 prompt columns; wave w computes the terms
-// of superblock group w of the canonical order (cfold: kCfoldGroups = 8 contiguous groups) one
-// superblock after the other and left-folds them in registers. The weights of the next superblock
+// of superblock groups w and w + 4 of the canonical order (cfold: kCfoldGroups = 8 contiguous groups)
+// one superblock after the other and left-folds them in registers. The weights of the next superblock
 // are requested before the current one's MFMAs (register double buffer); each 32-deep activation
 // fragment of the next superblock is requested into the register its step has just consumed. The
 // 8 group sums meet in LDS and are folded by the whole workgroup.
@@ -744,18 +744,19 @@ __global__ __launch_bounds__(768, 1) void k_mmqw(mi_mmx_group g) {
 // scale bytes (one bit-field extract per factor), loads advance by a wave-uniform SGPR offset (no
 // per-load address VALU), and the activation scales travel as one float per lane through a
 // wave-private LDS row.
-// MFMA orientation as k_mmqd1: A = activation fragment (accumulator row = prompt column), B = the
+// MFMA orientation: A = activation fragment (accumulator row = prompt column), B = the
 // dequantized weight planes (accumulator column = the lane's own weight row r).
-// NW = 4: two workgroups per CU (<= 256 VGPRs at two waves per SIMD), each wave computing groups
-// w and w + 4 one after the other (each group's sum goes to LDS when it ends).
+// Two workgroups per CU (<= 256 VGPRs at two waves per SIMD); each group's sum goes to LDS when it
+// ends. (8 waves with one group each, one workgroup per CU: 10.5 / 6.1 us against 7.65 / 4.91 us, removed.)
 // Two weight register buffers: superblock k + 1's weights are requested when step k starts.
 // r03v counters (B = 32, 16 members): waves wait ~45 % of their cycles (SQ_WAIT_INST_ANY),
 // MFMA 9 % busy, 18 VALU per MFMA. A ring of 4 measured slower (r03w): the activation fragments of
 // step k + 1 are requested after those weights, and vmcnt retires in order.
-template <int TYPE, int NW>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_mmqp(mi_mmx_group grp) {
+template <int TYPE>
+__global__ __launch_bounds__(256, 2) void k_mmqp(mi_mmx_group grp) {
     MI_MMX_MEMBER(grp);
     using F = XFmt<TYPE>;
+    constexpr int NW = 4;
     constexpr int NP = F::NP;
     constexpr int NE = 16;  // accumulator elements per lane
     constexpr int NG = kCfoldGroups / NW;  // groups per wave
@@ -1400,9 +1401,10 @@ __global__ __launch_bounds__(256, 2) void k_mmq0p(mi_mmx_group grp) {
 // NR = 2: each wave computes both 32-row halves of its 32 columns (64 x 32: every activation
 // fragment feeds two MFMAs, half the activation traffic per MFMA); the workgroup's NWV waves then
 // cover 32 NWV columns.
-template <bool Q8, int NWV, int LEAD, int NR = 1>
+template <bool Q8, int NWV, int NR>
 __global__ __launch_bounds__(64 * NWV, NR == 2 ? 2 : 1) void k_mmq0x(mi_mmx_group grp) {
     MI_MMX_MEMBER(grp);
+    constexpr int LEAD = 2;                   // weight ring depth (stages)
     constexpr int BS = mi_type(Q8 ? MI_TYPE_Q8_0 : MI_TYPE_Q4_0).bytes;
     constexpr int UB = 8 * BS;                // bytes of a row's unit
     constexpr int ND = Q8 ? 9 : 5;            // dwords covering a block (2-byte aligned)
@@ -1616,259 +1618,6 @@ __global__ __launch_bounds__(64 * NWV, NR == 2 ? 2 : 1) void k_mmq0x(mi_mmx_grou
     }
 }
 
-// ---- short prompts, K <= 4096: one round -------------------------------------------------------
-// A workgroup of S waves (one superblock each) per 32 x 32 tile, so every load of the tile is
-// requested at once and no wave runs a second round (k_mmqd's rounds each wait a full memory
-// latency: the load -> MFMA -> fold phases of the two waves of a SIMD do not overlap). Four waves
-// per SIMD at S = 16: <= 128 VGPRs, so the 16 da of a lane's accumulator elements go through a
-// wave-private LDS row instead of registers. Same operands, same exact T / U and the same
-// canonical fold (terms left-folded in superblock order) as k_mmqd / k_mmqx: bit-identical.
-template <int TYPE>
-__global__ __launch_bounds__(1024) void k_mmqd1(mi_mmx_group g) {
-    MI_MMX_MEMBER(g);
-    using F = XFmt<TYPE>;
-    constexpr int NP = F::NP;
-    extern __shared__ __attribute__((aligned(16))) float red[];  // [wave][lane][16] terms, then [wave][32] da
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int64_t ncols = act.ncols;
-    const int S = (int) (K / 256);  // == waves of the workgroup
-    const int64_t nrt = (N + 31) / 32;
-    const int64_t n0 = (mmx_tile % nrt) * 32, c0 = (mmx_tile / nrt) * 32;
-    const int sb = w;
-
-    const int nrows = (int) std::min<int64_t>(32, N - n0);
-    const __amdgpu_buffer_rsrc_t wres = __builtin_amdgcn_make_buffer_rsrc((void *) (W + n0 * nb01), (short) 0, (int) (nrows * nb01), 0x00020000);
-    const uint32_t wrow = (uint32_t) (min(r, nrows - 1) * nb01) + (uint32_t) sb * F::BS;
-    const uint32_t acol = (uint32_t) std::min<int64_t>(c0 + r, ncols - 1);
-    const __amdgpu_buffer_rsrc_t xres = __builtin_amdgcn_make_buffer_rsrc((void *) act.xq, (short) 0, (int) (K * ncols), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ures = __builtin_amdgcn_make_buffer_rsrc((void *) act.xu, (short) 0, (int) (S * ncols * 32), 0x00020000);
-    const __amdgpu_buffer_rsrc_t dres = __builtin_amdgcn_make_buffer_rsrc((void *) act.xd, (short) 0, (int) (S * ncols * 4), 0x00020000);
-    const uint32_t xstep = (uint32_t) ncols * 32;
-    const uint32_t xcol = acol * 32 + 16 * h + (uint32_t) sb * 8 * xstep;
-    constexpr uint32_t kQs = F::Q5 ? 48 : 16;
-
-    // every load of the wave, weights first (HBM), then the activation fragments (L2)
-    auto ld_w = [&](uint32_t off) -> uint4 { return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(wres, wrow + off, 0, 0)); };
-    const uint4 hdr = ld_w(0);
-    uint4 q4[4];
-#pragma unroll
-    for (int p = 0; p < 4; p++) q4[p] = ld_w(kQs + 32 * p + 16 * h);
-    const uint4 qh = F::Q5 ? ld_w(16 + 16 * h) : uint4{};
-    i32x4 xa[8];
-#pragma unroll
-    for (int kk = 0; kk < 8; kk++) xa[kk] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(xres, xcol + kk * xstep, 0, 0));
-    const half8 xu = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(ures, ((uint32_t) sb * (uint32_t) ncols + acol) * 32 + 16 * h, 0, 0));
-    // da of prompt column c0 + r (lanes >= 32 duplicate), parked in this wave's LDS row: columns
-    // past ncols read a clamped column's value (never stored)
-    const float dal = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dres, ((uint32_t) sb * (uint32_t) ncols + acol) * 4, 0, 0));
-    float * dal_row = red + (size_t) S * 64 * 16 + w * 32;
-    if (h == 0) dal_row[r] = dal;
-    __builtin_amdgcn_wave_barrier();  // wave-private row: LDS ops of a wave complete in order
-    __atomic_signal_fence(__ATOMIC_SEQ_CST);
-
-    const uint32_t w0 = hdr.y, w1 = hdr.z, w2 = hdr.w;
-    const float dw = mi_h2f((uint16_t) (hdr.x & 0xFFFF)), dm = mi_h2f((uint16_t) (hdr.x >> 16));
-    i32x16 acc[NP];
-#pragma unroll
-    for (int kk = 0; kk < 8; kk++) {
-        const int jj = kk & 3;
-        const uint32_t sc = kk < 4 ? ((w0 >> (8 * jj)) & 63) : (((w2 >> (8 * jj)) & 0xF) | (((w0 >> (8 * jj + 6)) & 3) << 4));
-        const uint4 q = q4[kk >> 1];
-        uint32_t v[4] = {q.x, q.y, q.z, q.w};
-        const uint32_t hb[4] = {qh.x, qh.y, qh.z, qh.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            v[e] = (kk & 1) ? (v[e] >> 4) & 0x0F0F0F0Fu : v[e] & 0x0F0F0F0Fu;
-            if constexpr (F::Q5) v[e] |= ((hb[e] >> kk) & 0x01010101u) << 4;
-        }
-#pragma unroll
-        for (int p = 0; p < NP; p++) {
-            uint32_t f = F::factor((int) sc, p);
-            f |= f << 16;
-            const i32x4 b = {(int) mulb(v[0], f), (int) mulb(v[1], f), (int) mulb(v[2], f), (int) mulb(v[3], f)};
-            acc[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[kk], b, kk == 0 ? i32x16{} : acc[p], 0, 0, 0);
-        }
-    }
-    half8 mu;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int j = 4 * h + q;  // this lane's k-halves of the U MFMA: sub-blocks 4h .. 4h + 3
-        const int jj = j & 3;
-        const uint32_t m = j < 4 ? ((w1 >> (8 * jj)) & 63) : (((w2 >> (8 * jj + 4)) & 0xF) | (((w1 >> (8 * jj + 6)) & 3) << 4));
-        mu[2 * q] = (_Float16) (float) m;
-        mu[2 * q + 1] = (_Float16) (float) (64 * m);
-    }
-    const f32x16 Uv = __builtin_amdgcn_mfma_f32_32x32x16_f16(xu, mu, f32x16{}, 0, 0, 0);
-    float * mine = red + ((size_t) w * 64 + lane) * 16;
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-        const float4 d4 = *(const float4 *) (dal_row + 8 * g + 4 * h);
-        const float dav[4] = {d4.x, d4.y, d4.z, d4.w};
-        float term[4];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const int el = 4 * g + e;
-            int T = acc[NP - 1][el];
-#pragma unroll
-            for (int p = NP - 2; p >= 0; p--) T = (T << F::SHIFT) + acc[p][el];
-            term[e] = mmqx_pre(T, Uv[el], dw, dm);
-        }
-        (void) dav;
-        *(float4 *) (mine + 4 * g) = make_float4(term[0], term[1], term[2], term[3]);
-    }
-    mi_lds_barrier();
-    // The 1024 outputs of the tile are folded by all S waves together: output o = 64 (w + S i) +
-    // lane is accumulator element el = o % 16 of lane lo = o / 16; its terms (one per superblock =
-    // per wave) are combined in the canonical order (cfold). Reads red[v][lo][el]: 64 consecutive
-    // floats per wave-load.
-    const int gs = cfold_gs(S);
-    for (int o = 64 * w + lane; o < 1024; o += 64 * S) {
-        const int lo = o >> 4, el = o & 15;
-        const float * src = red + (size_t) lo * 16 + el;
-        // d_a of superblock v for this output's column (the waves' da rows after the terms)
-        const float * dsrc = red + (size_t) S * 64 * 16 + ((el & 3) + 8 * (el >> 2) + 4 * (lo >> 5));
-        float y = -0.0f, ylo = -0.0f, gsum = 0.0f;
-        for (int v = 0; v < S; v++) cfold(gsum, y, ylo, src[(size_t) v * 64 * 16], dsrc[v * 32], v, gs, S);
-        y = cfold_end(ylo, y);
-        // element el of lane lo = prompt column c0 + (el & 3) + 8 (el >> 2) + 4 (lo >> 5), row n0 + lo % 32
-        const int64_t n = n0 + (lo & 31);
-        const int64_t c = c0 + (el & 3) + 8 * (el >> 2) + 4 * (lo >> 5);
-        if (n < N && c < ncols) *(float *) ((char *) dst + c * ycol + n * sizeof(float)) = y;
-    }
-}
-
-// ---- very short prompts (<= 16 columns), K <= 4096: 16 x 16 tiles --------------------------------
-// k_mmqd1 on v_mfma_i32_16x16x64_i8: a 16-row x 16-column tile per workgroup (one wave per
-// superblock), so a 16-column prompt spreads over N / 16 workgroups (every CU at N = 4096) instead
-// of N / 32 with half of each 32-column tile idle. Lane (g = lane / 16, i = lane % 16): prompt
-// column / weight row i, K bytes 16 g .. 16 g + 15 of each 64-deep step (step t = sub-blocks 2t,
-// 2t + 1: Q4_K quant bytes 32 t + 16 (g & 1), low nibbles for g < 2, high for g >= 2). The
-// accumulator element e of a lane is prompt column 4 g + e, weight row i. Same exact T / U and
-// the same fold as every kernel of this file: bit-identical.
-template <int TYPE>
-__global__ __launch_bounds__(1024) void k_mmqd16(mi_mmx_group grp) {
-    MI_MMX_MEMBER(grp);
-    using F = XFmt<TYPE>;
-    constexpr int NP = F::NP;
-    extern __shared__ __attribute__((aligned(16))) float red[];  // [wave][lane][4] terms, then [wave][16] da
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int i = lane & 15, g = lane >> 4;
-    const int64_t ncols = act.ncols;
-    const int S = (int) (K / 256);  // == waves of the workgroup
-    const int64_t nrt = (N + 15) / 16;
-    const int64_t n0 = (mmx_tile % nrt) * 16, c0 = (mmx_tile / nrt) * 16;
-    const int sb = w;
-
-    const int nrows = (int) std::min<int64_t>(16, N - n0);
-    const __amdgpu_buffer_rsrc_t wres = __builtin_amdgcn_make_buffer_rsrc((void *) (W + n0 * nb01), (short) 0, (int) (nrows * nb01), 0x00020000);
-    const uint32_t wrow = (uint32_t) (min(i, nrows - 1) * nb01) + (uint32_t) sb * F::BS;
-    const uint32_t acol = (uint32_t) std::min<int64_t>(c0 + i, ncols - 1);
-    const __amdgpu_buffer_rsrc_t xres = __builtin_amdgcn_make_buffer_rsrc((void *) act.xq, (short) 0, (int) (K * ncols), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ures = __builtin_amdgcn_make_buffer_rsrc((void *) act.xu, (short) 0, (int) (S * ncols * 32), 0x00020000);
-    const __amdgpu_buffer_rsrc_t dres = __builtin_amdgcn_make_buffer_rsrc((void *) act.xd, (short) 0, (int) (S * ncols * 4), 0x00020000);
-    // 64-deep step t of this superblock = 32-deep steps 2 t (lanes g < 2) and 2 t + 1 (g >= 2)
-    const uint32_t xstep = (uint32_t) ncols * 32;
-    const uint32_t xcol = acol * 32 + 16 * (g & 1) + ((uint32_t) sb * 8 + (uint32_t) (g >> 1)) * xstep;
-    constexpr uint32_t kQs = F::Q5 ? 48 : 16;
-
-    auto ld_w = [&](uint32_t off) -> uint4 { return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(wres, wrow + off, 0, 0)); };
-    const uint4 hdr = ld_w(0);
-    uint4 q4[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) q4[t] = ld_w(kQs + 32 * t + 16 * (g & 1));
-    const uint4 qh = F::Q5 ? ld_w(16 + 16 * (g & 1)) : uint4{};
-    i32x4 xa[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) xa[t] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(xres, xcol + 2 * t * xstep, 0, 0));
-    // U operand: sub-block halves of lanes g < 2 (g >= 2: zero K padding of the 16x16x32 MFMA)
-    half8 xu = {};
-    {
-        const half8 u = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(ures, ((uint32_t) sb * (uint32_t) ncols + acol) * 32 + 16 * (g & 1), 0, 0));
-        if (g < 2) xu = u;
-    }
-    const float dal = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dres, ((uint32_t) sb * (uint32_t) ncols + acol) * 4, 0, 0));
-    float * dal_row = red + (size_t) S * 64 * 4 + w * 16;
-    if (g == 0) dal_row[i] = dal;
-    __builtin_amdgcn_wave_barrier();  // wave-private row: LDS ops of a wave complete in order
-    __atomic_signal_fence(__ATOMIC_SEQ_CST);
-
-    const uint32_t w0 = hdr.y, w1 = hdr.z, w2 = hdr.w;
-    const float dw = mi_h2f((uint16_t) (hdr.x & 0xFFFF)), dm = mi_h2f((uint16_t) (hdr.x >> 16));
-    const int hi = g >> 1;  // high nibbles: the odd sub-block of each step
-    i32x4 acc[NP];
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-        const int j = 2 * t + hi;  // this lane's sub-block (lane-dependent: no unrolled constant)
-        const int jj = j & 3;
-        const uint32_t sc = j < 4 ? ((w0 >> (8 * jj)) & 63) : (((w2 >> (8 * jj)) & 0xF) | (((w0 >> (8 * jj + 6)) & 3) << 4));
-        const uint4 q = q4[t];
-        uint32_t v[4] = {q.x, q.y, q.z, q.w};
-        const uint32_t hb[4] = {qh.x, qh.y, qh.z, qh.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            v[e] = (v[e] >> (4 * hi)) & 0x0F0F0F0Fu;
-            if constexpr (F::Q5) v[e] |= ((hb[e] >> j) & 0x01010101u) << 4;
-        }
-#pragma unroll
-        for (int p = 0; p < NP; p++) {
-            uint32_t f = F::factor((int) sc, p);
-            f |= f << 16;
-            const i32x4 b = {(int) mulb(v[0], f), (int) mulb(v[1], f), (int) mulb(v[2], f), (int) mulb(v[3], f)};
-            acc[p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xa[t], b, t == 0 ? i32x4{} : acc[p], 0, 0, 0);
-        }
-    }
-    half8 mu = {};
-    if (g < 2) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int j = 4 * g + q;  // K halves 8 g .. 8 g + 7: sub-blocks 4 g .. 4 g + 3
-            const int jj = j & 3;
-            const uint32_t m = j < 4 ? ((w1 >> (8 * jj)) & 63) : (((w2 >> (8 * jj + 4)) & 0xF) | (((w1 >> (8 * jj + 6)) & 3) << 4));
-            mu[2 * q] = (_Float16) (float) m;
-            mu[2 * q + 1] = (_Float16) (float) (64 * m);
-        }
-    }
-    typedef float f32x4v __attribute__((ext_vector_type(4)));
-    const f32x4v Uv = __builtin_amdgcn_mfma_f32_16x16x32_f16(xu, mu, f32x4v{}, 0, 0, 0);
-    float * mine = red + ((size_t) w * 64 + lane) * 4;
-    {
-        const float4 d4 = *(const float4 *) (dal_row + 4 * g);
-        const float dav[4] = {d4.x, d4.y, d4.z, d4.w};
-        float term[4];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            int T = acc[NP - 1][e];
-#pragma unroll
-            for (int p = NP - 2; p >= 0; p--) T = (T << F::SHIFT) + acc[p][e];
-            term[e] = mmqx_pre(T, Uv[e], dw, dm);
-        }
-        (void) dav;
-        *(float4 *) mine = make_float4(term[0], term[1], term[2], term[3]);
-    }
-    mi_lds_barrier();
-    if (w != 0) return;
-    float4 y = {-0.0f, -0.0f, -0.0f, -0.0f}, lo = y, gsum = {};
-    const int gs = cfold_gs(S);
-    for (int v = 0; v < S; v++) {
-        const float4 t4 = *(const float4 *) (red + ((size_t) v * 64 + lane) * 4);
-        const float4 d4 = *(const float4 *) (red + (size_t) S * 64 * 4 + v * 16 + 4 * g);  // d_a of columns 4 g ..
-        cfold(gsum.x, y.x, lo.x, t4.x, d4.x, v, gs, S);
-        cfold(gsum.y, y.y, lo.y, t4.y, d4.y, v, gs, S);
-        cfold(gsum.z, y.z, lo.z, t4.z, d4.z, v, gs, S);
-        cfold(gsum.w, y.w, lo.w, t4.w, d4.w, v, gs, S);
-    }
-    y = make_float4(cfold_end(lo.x, y.x), cfold_end(lo.y, y.y), cfold_end(lo.z, y.z), cfold_end(lo.w, y.w));
-    const int64_t n = n0 + i;
-    if (n >= N) return;
-    const float yv[4] = {y.x, y.y, y.z, y.w};
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        const int64_t c = c0 + 4 * g + e;
-        if (c < ncols) *(float *) ((char *) dst + c * ycol + n * sizeof(float)) = yv[e];
-    }
-}
-
 } // namespace
 
 bool mi_mmqx_supported(int type, int64_t K, size_t ycol, int64_t ncols, size_t nb01) {
@@ -1876,7 +1625,7 @@ bool mi_mmqx_supported(int type, int64_t K, size_t ycol, int64_t ncols, size_t n
     // Q4_0 / Q8_0: 16-byte aligned 8-block units (K % 256 == 0, rows of 16-byte multiples)
     if (!mi_type(type).mmqx) return false;
     if (mi_type(type).blck == 32) {
-        return K % 256 == 0 && K >= 256 && nb01 % 16 == 0 && K * ncols < ((int64_t) 1 << 31) && (int64_t) nb01 * 32 < ((int64_t) 1 << 31);
+        return K % 256 == 0 && K >= 256 && nb01 % 16 == 0 && ycol % 16 == 0 && K * ncols < ((int64_t) 1 << 31) && (int64_t) nb01 * 32 < ((int64_t) 1 << 31);
     }
     return K % 256 == 0 && K >= 256 && ycol % 16 == 0 && K * ncols < ((int64_t) 1 << 31) &&
            (int64_t) nb01 * XBM < ((int64_t) 1 << 31);
@@ -1895,15 +1644,18 @@ static int64_t mmx_deal(mi_mmx_group & g, int64_t tr, int64_t tc) {
 // Q4_0 / Q8_0 (q8_0 activations, mi_act_mmx0_*), every column count. By workgroup count: 64 x 128
 // tiles of 4 waves, each 64 rows x 32 columns (k_mmq0x NR = 2) when there are >= 256 of them; else
 // 64 x 64 tiles of 4 waves (k_mmq0x half width) when >= 256 (Q8_0: 128); else 32 x 32 tiles of 4 waves
-// on one tile (k_mmq0p). Variant bits force one: kMmqShortKernels k_mmq0p, kMmqLongKernels k_mmq0x
-// (8 waves, 64 x 128), with kMmqHalfWidth half width, with kMmq0xRows2 NR = 2, with kMmq0xRows2W8
-// NR = 2 with 8 waves (64 x 256). Every one keeps the family's canonical combine: the same bits.
+// on one tile (k_mmq0p). Variant bits force one at any column count: kMmqShortKernels k_mmq0p,
+// kMmqLongKernels k_mmq0x NR = 2 (the long prompts' choice; kMmq0xRows2 says the same), with kMmqHalfWidth
+// half width, with kMmq0xRows2W8 NR = 2 with 8 waves (64 x 256: never picked by tile count, kept for its
+// 1-3 % lead in grouped launches at B = 256 / 512, profiles/r03m_prefill_q4_0_q8_0.txt; alone in a graph
+// it is 18-40 % behind). Every one keeps the family's canonical combine: the same bits.
+// (8-wave workgroups of 64 x 128 with NR = 1 were never picked and have no measurement in their favour: removed.)
 static void mmq0_group(mi_mmx_group & g, hipStream_t s) {
     const int var = g_mi_tuning.mmq_variant;
     const bool q8 = g.type == MI_TYPE_Q8_0;
     int pick;
     if (var & kMmqShortKernels) pick = 0;
-    else if (var & kMmqLongKernels) pick = (var & kMmq0xRows2W8) ? 4 : (var & kMmq0xRows2) ? 3 : (var & kMmqHalfWidth) ? 2 : 1;
+    else if (var & kMmqLongKernels) pick = (var & kMmq0xRows2W8) ? 3 : (var & kMmq0xRows2) ? 2 : (var & kMmqHalfWidth) ? 1 : 2;
     else {
         int64_t t2 = 0, th = 0;
         for (int i = 0; i < g.n; i++) {
@@ -1913,7 +1665,7 @@ static void mmq0_group(mi_mmx_group & g, hipStream_t s) {
         }
         // (k_mmq0p's Q8_0 operands -- five dword loads per block and lane -- make it the
         // slower one for Q8_0 from 128 half-width tiles on)
-        pick = t2 >= 256 && g.m[0].act.ncols > 64 ? 3 : th >= (q8 ? 128 : 256) ? 2 : 0;
+        pick = t2 >= 256 && g.m[0].act.ncols > 64 ? 2 : th >= (q8 ? 128 : 256) ? 1 : 0;
     }
     // tiles of TR rows x TC columns, NT threads each
 #define MI_MMQ0(KERN, TR, TC, NT, ...)                                                          \
@@ -1922,14 +1674,13 @@ static void mmq0_group(mi_mmx_group & g, hipStream_t s) {
         if (!q8) hipLaunchKernelGGL((KERN<false, ##__VA_ARGS__>), grid, dim3(NT), 0, s, g);     \
         else hipLaunchKernelGGL((KERN<true, ##__VA_ARGS__>), grid, dim3(NT), 0, s, g);          \
     } while (0)
-    static const char * const kRoutes[] = {"k_mmq0p", "k_mmq0x", "k_mmq0x_half", "k_mmq0x_rows2", "k_mmq0x_rows2_w8"};
+    static const char * const kRoutes[] = {"k_mmq0p", "k_mmq0x_half", "k_mmq0x_rows2", "k_mmq0x_rows2_w8"};
     mi_route(kRoutes[pick]);
     switch (pick) {
         case 0: MI_MMQ0(k_mmq0p, 32, 32, 256); break;  // (a deeper weight ring, RING 3, spills: 36-dword units)
-        case 1: MI_MMQ0(k_mmq0x, XBM, XBN, 512, 8, 4); break;
-        case 2: MI_MMQ0(k_mmq0x, XBM, 64, 256, 4, 2); break;
-        case 3: MI_MMQ0(k_mmq0x, XBM, 128, 256, 4, 2, 2); break;
-        default: MI_MMQ0(k_mmq0x, XBM, 256, 512, 8, 2, 2); break;
+        case 1: MI_MMQ0(k_mmq0x, XBM, 64, 256, 4, 1); break;
+        case 2: MI_MMQ0(k_mmq0x, XBM, 128, 256, 4, 2); break;
+        default: MI_MMQ0(k_mmq0x, XBM, 256, 512, 8, 2); break;
     }
 #undef MI_MMQ0
 }
@@ -1954,10 +1705,12 @@ static bool mmx_dst_local(const mi_mmx_group & g) {
 }
 
 // Q4_K / Q5_K (q8_K activations). Short prompts (<= 128 columns): pipelined 32 x 32 tiles (k_mmqp),
-// a wave per superblock (k_mmqd1, k_mmqd16) when asked, or k_mmqt where its tiles fill the chip; long
-// ones: the planes kernel, k_mmqt (Q4_K), k_mmqw (Q5_K) or k_mmqx. All follow the same canonical
-// combine order (cfold), so a prompt's column shards give the whole prompt's bits whichever kernel
-// runs them. One decision per kernel, top to bottom; the first that applies launches.
+// or k_mmqt where its tiles fill the chip; long ones: the planes kernel, k_mmqt (Q4_K), k_mmqw (Q5_K)
+// or k_mmqx. All follow the same canonical combine order (cfold), so a prompt's column shards give
+// the whole prompt's bits whichever kernel runs them. One decision per kernel, top to bottom; the
+// first that applies launches. Variant bits move a decision, never a kernel's shape: kMmqShortKernels /
+// kMmqLongKernels take the short / long prompts' decisions at any column count, kMmqHalfWidth /
+// kMmqFullWidth force / forbid half-width k_mmqx, kMmqxOnly takes k_mmqx where k_mmqt / k_mmqw would run.
 void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
     if (g.n <= 0) return;
     MI_ASSERT(mi_type(g.type).mmqx);
@@ -1996,8 +1749,9 @@ void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
     // (r06s2b_mmqt_short_groups.txt, r06s2c_mmqt_short_threshold.txt) k_mmqt wins from 192 of its
     // workgroups (3 x B = 128: 13.99 -> 11.19 us; 6 x B = 64: 6.98 -> 5.72 us) and loses below (4 x
     // B = 64, 128 workgroups: 7.76 vs 7.86; a lone B = 64 member's 32: 12.4 vs 26.6 us); B = 32 stays
-    // on k_mmqp (4.52 vs 4.85). Variant bits that ask for a particular kernel turn it off.
-    constexpr int kAsksOther = kMmqShortKernels | kMmqLongKernels | kMmqd1 | kMmqNoD16 | kMmqNoShortT | kMmqd16 | kMmqd16Wide | kMmqp8;
+    // on k_mmqp (4.52 vs 4.85). The two bits that pin the short or the long prompts' kernels turn it
+    // off (mmqt_short 0 does so alone).
+    constexpr int kAsksOther = kMmqShortKernels | kMmqLongKernels;
     if (q4 && ncols > 32 && ncols <= 128 && dst_local && g_mi_tuning.mmqt_short > 0 && !(var & kAsksOther) &&
         tiles(128, 64) >= g_mi_tuning.mmqt_short) {
         mi_route("k_mmqt_short");
@@ -2006,27 +1760,9 @@ void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
     }
 
     if ((var & kMmqShortKernels) || (ncols <= 128 && !(var & kMmqLongKernels)) || !dst_local) {
-        // k_mmqd16: 16 x 16 tiles only when asked (kMmqd16 up to 16 columns, kMmqd16Wide up to 128).
-        // Round 6 (profiles/r06a_short_prefill.txt, Q4_K / Q5_K 4096^2, 8 rotated weights): k_mmqp's
-        // 32 x 32 tiles are faster at B = 9 and 16 both grouped (Q4_K 3.98 / 4.07 vs 5.56 / 5.63 us per
-        // mul_mat) and alone in a graph (11.5 / 11.4 vs 12.0 / 12.0 us)
-        const int64_t lim16 = (var & kMmqd16Wide) ? 128 : (var & kMmqd16) ? 16 : 0;
-        if (S <= 16 && ncols <= lim16 && !(var & (kMmqd1 | kMmqNoD16))) {
-            mi_route("k_mmqd16");
-            MI_MMQX_T(k_mmqd16, 16, 16, 64 * S, (size_t) S * (64 * 4 + 16) * sizeof(float));
-            return;
-        }
-        // k_mmqd1: one round, a wave per superblock, when asked
-        if (S <= 16 && (var & kMmqd1)) {
-            mi_route("k_mmqd1");
-            MI_MMQX_T(k_mmqd1, 32, 32, 64 * S, (size_t) S * (64 * 16 + 32) * sizeof(float));
-            return;
-        }
-        // k_mmqp: pipelined 32 x 32 tiles, 4 waves per tile (two workgroups per CU) unless kMmqp8 (8
-        // waves, one per CU)
-        mi_route((var & kMmqp8) ? "k_mmqp8" : "k_mmqp");
-        if (var & kMmqp8) MI_MMQX_T(k_mmqp, 32, 32, 512, 0, 8);
-        else MI_MMQX_T(k_mmqp, 32, 32, 256, 0, 4);
+        // k_mmqp: pipelined 32 x 32 tiles, 4 waves per tile (two workgroups per CU)
+        mi_route("k_mmqp");
+        MI_MMQX_T(k_mmqp, 32, 32, 256, 0);
         return;
     }
 
@@ -2040,7 +1776,7 @@ void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
 
     // k_mmqt: Q4_K, K split over wave pairs, 128 x 64 tiles (the default; B=512 33.4 vs 36.6 us for
     // k_mmqw, B=256 18.5 vs 19.7, profiles/r04i_pf_long_mmqt.txt)
-    const bool mmqx_asked = (var & (kMmqxOnly | kMmqxLead1)) != 0;
+    const bool mmqx_asked = (var & kMmqxOnly) != 0;
     if (q4 && !mmqx_asked) {
         mi_route("k_mmqt");
         MI_MMQX((k_mmqt<MI_TYPE_Q4_K>), 128, 64, 512, 0);
@@ -2055,10 +1791,9 @@ void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
         return;
     }
 
-    // k_mmqx: weight ring depth 4 (kMmqxLead1: 1)
-    mi_route((var & kMmqxLead1) ? "k_mmqx_lead1" : "k_mmqx");
-    if (var & kMmqxLead1) MI_MMQX_T(k_mmqx, XBM, XBN, 512, 0, 1);
-    else MI_MMQX_T(k_mmqx, XBM, XBN, 512, 0, 4);
+    // k_mmqx: weight ring depth 4
+    mi_route("k_mmqx");
+    MI_MMQX_T(k_mmqx, XBM, XBN, 512, 0, 4);
 #undef MI_MMQX_T
 #undef MI_MMQX
 }

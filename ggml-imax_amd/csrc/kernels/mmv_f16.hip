@@ -301,8 +301,7 @@ __global__ __launch_bounds__(512) void k_gemv_f16(const uint8_t * __restrict__ W
         // branch is waited for at its join, before the weights below are even requested)
         if constexpr (!XH) st.load((const float *) (x.base + c0 * x.nb1), K, 0);
     }
-    // xfirst: the activation-side loads land before any weight load is queued behind them
-    if (e.xfirst) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);  // the activation-side loads above are issued before the weight loads below (vmcnt retires in order)
     uint4 cur[U];
 #pragma unroll
     for (int u = 0; u < U; u++) cur[u] = ld(u);
@@ -465,7 +464,7 @@ __global__ __launch_bounds__(256) void k_gemv_f16_tall(const uint8_t * __restric
     ColStager<4> st;
     if constexpr (JM > 0) norm_load<JM, GB>((const float *) (x.base + (size_t) (wid < nc ? wid : 0) * x.nb1), K, lane, pro, pv, pg, pb);
     else if (NC == 1) st.load((const float *) x.base, K, 0);
-    if (e.xfirst) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);  // the activation-side loads above are issued before the weight loads below (vmcnt retires in order)
     uint4 cur[U];
     float eb = 0.0f;
     load_group(cur, eb, grp);
@@ -664,7 +663,7 @@ __global__ __launch_bounds__(512) void k_gemv_f16_ps(const uint8_t * __restrict_
         if (EPI >= 1) e_bias = e.bias[rc];
         if (EPI == 2) e_res = *(const float *) (e.resid + rc * sizeof(float));
     }
-    if (e.xfirst) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);  // the activation-side loads above are issued before the weight loads below (vmcnt retires in order)
     uint4 cur[U];
 #pragma unroll
     for (int u = 0; u < U; u++) {
@@ -831,9 +830,7 @@ void launch_nc(const void * W, size_t nb01, int64_t K, int64_t N, const mi_src_c
     const size_t lds = (size_t) (priv ? ks : NC) * kp * sizeof(uint16_t) + (size_t) ks * rgs * 4 * NC * sizeof(float);
     const int epi = e.gelu_table ? 3 : (e.resid ? 2 : (e.bias ? 1 : 0));
     const uint8_t * w = (const uint8_t *) W;
-    mi_f16_epilogue es = e;
-    es.xfirst = g_mi_tuning.xfirst == 1;  // (off by default: GPT-2 decode 304 -> 316 us per token with it)
-#define MI_GEMV_F16X(EP, XHV) hipLaunchKernelGGL((k_gemv_f16<NC, EP, U, ONE, JM, XHV>), grid, dim3(64 * ks * rgs), lds, s, w, nb01, K, N, x, xh, ncols, dst, ycol, es, pro, kp, rgs)
+#define MI_GEMV_F16X(EP, XHV) hipLaunchKernelGGL((k_gemv_f16<NC, EP, U, ONE, JM, XHV>), grid, dim3(64 * ks * rgs), lds, s, w, nb01, K, N, x, xh, ncols, dst, ycol, e, pro, kp, rgs)
 #define MI_GEMV_F16(EP) do { if constexpr (JM == 0) { if (xh) MI_GEMV_F16X(EP, true); else MI_GEMV_F16X(EP, false); } else MI_GEMV_F16X(EP, false); } while (0)
     switch (epi) {
         case 0: MI_GEMV_F16(0); break;
@@ -922,12 +919,11 @@ void mi_mul_mat_f16_fast(const void * W, size_t nb01, int64_t K, int64_t N, cons
         const size_t lds = (size_t) nc * kp * sizeof(uint16_t);
         const int epi = e.gelu_table ? 3 : (e.bias ? 1 : 0);
         const uint8_t * w = (const uint8_t *) W;
-        mi_f16_epilogue es = e;
         if (nc >= 2 && ncols >= 2 && K % 32 == 0 && K <= 768 && g_mi_tuning.f16_mt) {
             // several columns on the matrix cores (k_gemv_f16_mt): 16-row tiles, grid-stride
             const dim3 gridm((unsigned) std::min<int64_t>(((N + 15) / 16 + 3) / 4, 512));
             const size_t ldsm = (size_t) 8 * kp * sizeof(uint16_t);
-#define MI_GEMV_MT(EP, JMV) hipLaunchKernelGGL((k_gemv_f16_mt<EP, JMV, 24>), gridm, dim3(256), ldsm, s, w, nb01, K, N, x, (int) ncols, dst, ycol, es, pro, kp)
+#define MI_GEMV_MT(EP, JMV) hipLaunchKernelGGL((k_gemv_f16_mt<EP, JMV, 24>), gridm, dim3(256), ldsm, s, w, nb01, K, N, x, (int) ncols, dst, ycol, e, pro, kp)
             if (pro.mode) {
                 if (epi == 0) MI_GEMV_MT(0, 4); else if (epi == 1) MI_GEMV_MT(1, 4); else MI_GEMV_MT(3, 4);
             } else {
@@ -936,8 +932,7 @@ void mi_mul_mat_f16_fast(const void * W, size_t nb01, int64_t K, int64_t N, cons
 #undef MI_GEMV_MT
             return;
         }
-        es.xfirst = g_mi_tuning.xfirst == 1;  // (off by default: GPT-2 decode 304 -> 316 us per token with it)
-#define MI_GEMV_TALL_N(EP, JMV, NCV) hipLaunchKernelGGL((k_gemv_f16_tall<EP, 8, JMV, NCV>), grid, dim3(256), lds, s, w, nb01, K, N, x, (int) ncols, dst, ycol, es, pro, kp)
+#define MI_GEMV_TALL_N(EP, JMV, NCV) hipLaunchKernelGGL((k_gemv_f16_tall<EP, 8, JMV, NCV>), grid, dim3(256), lds, s, w, nb01, K, N, x, (int) ncols, dst, ycol, e, pro, kp)
 #define MI_GEMV_TALL(EP, JMV) do { switch (nc) { case 1: MI_GEMV_TALL_N(EP, JMV, 1); break; case 2: MI_GEMV_TALL_N(EP, JMV, 2); break; \
                                                   case 4: MI_GEMV_TALL_N(EP, JMV, 4); break; default: MI_GEMV_TALL_N(EP, JMV, 8); break; } } while (0)
         if (pro.mode) {
@@ -959,9 +954,7 @@ void mi_mul_mat_f16_fast(const void * W, size_t nb01, int64_t K, int64_t N, cons
         const size_t lds = (size_t) rw * kp * sizeof(uint16_t) + (size_t) kp * sizeof(float);
         const int epi = e.gelu_table ? 3 : (e.resid ? 2 : (e.bias ? 1 : 0));
         const uint8_t * w = (const uint8_t *) W;
-        mi_f16_epilogue es = e;
-        es.xfirst = g_mi_tuning.xfirst == 1;  // (off by default: GPT-2 decode 304 -> 316 us per token with it)
-#define MI_GEMV_PS(EP, NPM, QPT) hipLaunchKernelGGL((k_gemv_f16_ps<EP, 8, 4, NPM, QPT>), grid, dim3(64 * rw), lds, s, w, nb01, K, N, dst, es, pro, kp)
+#define MI_GEMV_PS(EP, NPM, QPT) hipLaunchKernelGGL((k_gemv_f16_ps<EP, 8, 4, NPM, QPT>), grid, dim3(64 * rw), lds, s, w, nb01, K, N, dst, e, pro, kp)
 #define MI_GEMV_PS_E(NPM, QPT)                     \
         switch (epi) {                             \
             case 0: MI_GEMV_PS(0, NPM, QPT); break; \

@@ -49,13 +49,12 @@ const knob kKnobs[] = {
     {"mmv_variant", &mi_tuning::mmv_variant, INT_MIN, kAny, nullptr},
     {"f16_variant", &mi_tuning::f16_variant, INT_MIN, kAny, nullptr},
     {"f16_threads", &mi_tuning::f16_threads, 0, 256, [](int v) { return v == 0 || v == 64 || v == 128 || v == 256; }},
-    {"mmq_variant", &mi_tuning::mmq_variant, INT_MIN, kAny, nullptr},
+    {"mmq_variant", &mi_tuning::mmq_variant, 0, kMmqVariantMask, [](int v) { return (v & ~kMmqVariantMask) == 0; }},
     {"attn_variant", &mi_tuning::attn_variant, INT_MIN, kAny, nullptr},
     {"mmv_order", &mi_tuning::mmv_order, -1, 1, nullptr},
     {"f16_waves", &mi_tuning::f16_waves, 0, kAny, nullptr},
     {"f16_rgs", &mi_tuning::f16_rgs, 0, 8, nullptr},
     {"f16_ps_waves", &mi_tuning::f16_ps_waves, 0, 8, [](int v) { return v == 0 || v == 2 || v == 4 || v == 8; }},
-    {"xfirst", &mi_tuning::xfirst, -1, 1, nullptr},
     {"f16_norm_waves", &mi_tuning::f16_norm_waves, 0, 8, nullptr},
     {"planes", &mi_tuning::planes, 0, 1, nullptr},
     {"f16_nc", &mi_tuning::f16_nc, 0, 88, [](int v) { return v % 10 <= 8; }},

@@ -1768,18 +1768,13 @@ __device__ __forceinline__ void store_out(const mi_mmv_group & g, float * dst, i
 // 64-item chunk of a row leaves its per-item lane sums in the wave's LDS scratch, then lane
 // (column c, CPU lane l) runs the reference's sequential fma chain over the chunk.
 // PRO: the graph's norm prologue (g.pro) and store epilogue (g.epi) are compiled in
-// XF (lone members): the activation side first -- its loads issued and waited for before any weight
-// load, so they do not queue behind every workgroup's weight stream (phase stamps: with the weights
-// requested first, a lone Q4_K 4096^2 member's activations took 3.6 us to land and quantize,
-// profiles/r05b_lone_gemv_stamps.txt); the weights are then requested while the activations are
-// quantized (PRO: after the prologue's quantization)
 // MR > 1 (one column, rows of at most 16 items: tall short-K matrices such as GPT-2's lm_head,
 // K = 768 = 12 Q4_K items): each wave step covers MR rows, 16 lanes per row (lane 16 r + i: item i
 // of the step's row r) instead of one row on 64 lanes of which K / ITEM do work
 // IDS (GGML_OP_MUL_MAT_ID decode): the member's W field points at its expert id in device memory;
 // the workgroup reads it at entry and streams expert id's matrix of the stack g.ids_w (stride
 // g.ids_nb02). An id outside [0, g.ids_n_as) ends the workgroup here, before any barrier.
-template <class F, int NC, int PD, int IPL, bool TAIL, bool ORD, bool PRO, bool XF, int MR = 1, bool IDS = false>
+template <class F, int NC, int PD, int IPL, bool TAIL, bool ORD, bool PRO, int MR = 1, bool IDS = false>
 __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     constexpr int NB = PD + 1;  // ring slots
@@ -1842,7 +1837,7 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
     const bool p4 = P4 && g.pro.mode && g.pro_q;
     const int nsl = (int) (K / 256);
     const int total = nsl * ncols;
-    float4 xfirst[4];
+    float4 x0[4];  // the first quantization round's slices
     // Q8_K (R16): a round of a wave = slices p0 .. p0 + 3, one per 16-lane row (lane: 16 consecutive
     // elements, quantize_row16); Q8_0: slices p0, p0 + 4, p0 + 8, p0 + 12, four elements per lane
     constexpr bool R16 = F::QKA == 256;
@@ -1876,21 +1871,18 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
         }
         epi_prefetch<NC>(g, row_begin + wave < Nr ? row_begin + wave : Nr - 1, X, epre);
     } else {
-        load_round(xfirst, X, g.xcol, p_first);
+        load_round(x0, X, g.xcol, p_first);
     }
     // (keep these loads ahead of the weight prefetch: the scheduler hoisted the prefetch above
     // them, and vmcnt retires in order -- the activations then waited for the weights)
 #ifndef MI_AB_NO_ACT_ORDER  // (A/B builds only)
     asm volatile("" ::: "memory");
 #endif
-    if constexpr (XF && !PRO) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // 1) the first PD rows' weights in flight
-    if constexpr (!(XF && PRO)) {
 #pragma unroll
-        for (int u = 0; u < PD; u++) {
-            if constexpr (MR > 1) prefetch_mr(ring[u], u < klast ? u : klast);
-            else prefetch(ring[u], u < klast ? u : klast);
-        }
+    for (int u = 0; u < PD; u++) {
+        if constexpr (MR > 1) prefetch_mr(ring[u], u < klast ? u : klast);
+        else prefetch(ring[u], u < klast ? u : klast);
     }
 
     // 2) quantize the member's activation columns into LDS (wave w: 256-slices w, w+4, ...),
@@ -1912,7 +1904,7 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
             float4 v[4];
             if (!PRO && p0 == p_first) {
 #pragma unroll
-                for (int u = 0; u < 4; u++) v[u] = xfirst[u];
+                for (int u = 0; u < 4; u++) v[u] = x0[u];
             } else {
                 load_round(v, Xq, xcolq, p0);
             }
@@ -1930,13 +1922,6 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
                     }
                 }
             }
-        }
-    }
-    if constexpr (XF && PRO) {
-#pragma unroll
-        for (int u = 0; u < PD; u++) {
-            if constexpr (MR > 1) prefetch_mr(ring[u], u < klast ? u : klast);
-            else prefetch(ring[u], u < klast ? u : klast);
         }
     }
     __syncthreads();
@@ -2141,18 +2126,18 @@ static int mi_cu_count() {
 // The route string of one k_mmv_stream instance (g_mi_last_route), built once per instance: the weight
 // format (the ggml type number unless the format reads pairs of blocks or a repacked copy) and the
 // template arguments that tell the instances apart.
-template <class F, int NC, int PD, int IPL, bool TAIL, bool ORD, bool PRO, bool XF, int MR, bool IDS>
+template <class F, int NC, int PD, int IPL, bool TAIL, bool ORD, bool PRO, int MR, bool IDS>
 const char * stream_route(int type) {
     static char name[96] = "";
     if (!name[0]) {
         const char * fmt = std::is_same<F, FmtQ0Pair>::value ? "pairs," : std::is_same<F, FmtQ0R>::value || std::is_same<F, FmtQ8R>::value ? "repacked," : "";
-        snprintf(name, sizeof(name), "k_mmv_stream<type%d,%snc%d,pd%d,ipl%d,tail%d,ord%d,pro%d,xf%d,mr%d,ids%d>", type, fmt, NC, PD, IPL,
-                 (int) TAIL, (int) ORD, (int) PRO, (int) XF, MR, (int) IDS);
+        snprintf(name, sizeof(name), "k_mmv_stream<type%d,%snc%d,pd%d,ipl%d,tail%d,ord%d,pro%d,mr%d,ids%d>", type, fmt, NC, PD, IPL,
+                 (int) TAIL, (int) ORD, (int) PRO, MR, (int) IDS);
     }
     return name;
 }
 
-template <class F, int NC, int PD, int IPL, bool TAIL, bool ORD, bool PRO = false, bool XF = false, int MR = 1, bool IDS = false>
+template <class F, int NC, int PD, int IPL, bool TAIL, bool ORD, bool PRO = false, int MR = 1, bool IDS = false>
 void launch_one(mi_mmv_group g, hipStream_t s) {
     const size_t act = lds_bytes<F::QKA>(NC, g.K);
     size_t lds = act;
@@ -2178,7 +2163,7 @@ void launch_one(mi_mmv_group g, hipStream_t s) {
     }
     if constexpr (MR > 1 && ORD) {
         if (g.ord_rows < MR) {  // a chain pass must hold whole multi-row steps: the one-row form
-            launch_one<F, NC, PD, IPL, TAIL, ORD, PRO, XF, 1, IDS>(g, s);
+            launch_one<F, NC, PD, IPL, TAIL, ORD, PRO, 1, IDS>(g, s);
             return;
         }
     }
@@ -2187,7 +2172,7 @@ void launch_one(mi_mmv_group g, hipStream_t s) {
         g.pro_off = (int) ord_offset(lds);
         lds = (size_t) g.pro_off + (size_t) NC * g.K * sizeof(float);
     }
-    const void * fn = (const void *) k_mmv_stream<F, NC, PD, IPL, TAIL, ORD, PRO, XF, MR, IDS>;
+    const void * fn = (const void *) k_mmv_stream<F, NC, PD, IPL, TAIL, ORD, PRO, MR, IDS>;
     if (lds > 64 * 1024) {
         static bool attr_set = false;  // per instance
         if (!attr_set) {
@@ -2213,16 +2198,16 @@ void launch_one(mi_mmv_group g, hipStream_t s) {
     rows = (rows + 3) / 4 * 4;
     g.rows_per_block = rows;
     g.blocks_per_member = (int) ((g.N + rows - 1) / rows);
-    mi_route(stream_route<F, NC, PD, IPL, TAIL, ORD, PRO, XF, MR, IDS>(g.type));
-    hipLaunchKernelGGL((k_mmv_stream<F, NC, PD, IPL, TAIL, ORD, PRO, XF, MR, IDS>), dim3((unsigned) (g.blocks_per_member * g.n)), dim3(256), lds,
+    mi_route(stream_route<F, NC, PD, IPL, TAIL, ORD, PRO, MR, IDS>(g.type));
+    hipLaunchKernelGGL((k_mmv_stream<F, NC, PD, IPL, TAIL, ORD, PRO, MR, IDS>), dim3((unsigned) (g.blocks_per_member * g.n)), dim3(256), lds,
                        s, g);
 }
 
 
-template <class F, int NC, int PD, int IPL, bool ORD, bool XF = false>
+template <class F, int NC, int PD, int IPL, bool ORD>
 void launch_tail(const mi_mmv_group & g, hipStream_t s) {
-    if (g.K / F::ITEM > 64 * IPL) launch_one<F, NC, PD, IPL, true, ORD, false, XF>(g, s);
-    else launch_one<F, NC, PD, IPL, false, ORD, false, XF>(g, s);
+    if (g.K / F::ITEM > 64 * IPL) launch_one<F, NC, PD, IPL, true, ORD>(g, s);
+    else launch_one<F, NC, PD, IPL, false, ORD>(g, s);
 }
 
 // formats that read the canonical blocks (MUL_MAT_ID has no repacked copies: those need 2-D leaves)
@@ -2232,22 +2217,18 @@ template <class F, int NC, bool ORD>
 void launch_stream(const mi_mmv_group & g, int variant, hipStream_t s) {
     const int items = (int) (g.K / F::ITEM);
     const mi_mmv_group::epilogue & e = g.epi;
-    // XF (activations landed before any weight request) is opt-in only (xfirst 1). It was the
-    // automatic choice for lone members at K >= 2048 while the scheduler hoisted the weight prefetch
-    // above the activation loads (lone Q4_K 4096^2 6.93 -> 6.11 us per graph then); with the
-    // activation loads pinned ahead of the prefetch, both stream together and XF only serializes
-    // them: 5.45 -> 4.95 us per graph without it (profiles/r05xf_xfirst_ab.txt)
-    const bool xf = g.n == 1 && g_mi_tuning.xfirst == 1;
+    // (Instances that waited for a lone member's activation loads before requesting any weight measured
+    // 5.45 us per graph against 4.95 us without the wait: removed)
     const bool pro_epi = g.pro.mode || e.bias || e.resid || e.gelu_table || e.copy[0].ptr || e.copy[1].ptr;
     if constexpr (NC == 1 && kFmtCanonical<F>) {
         // MUL_MAT_ID decode: the plain one-column forms with the device-resolved weight base
         // (no prologue / epilogue, no repacked copies)
         if (g.ids_w) {
-            if (items > 128) launch_one<F, 1, 2, 2, true, ORD, false, false, 1, true>(g, s);
-            else if (items > 64) launch_one<F, 1, 2, 2, false, ORD, false, false, 1, true>(g, s);
-            else if (variant / 10 == 1) launch_one<F, 1, 1, 1, false, ORD, false, false, 1, true>(g, s);
-            else if (variant / 10 == 3) launch_one<F, 1, 3, 1, false, ORD, false, false, 1, true>(g, s);
-            else launch_one<F, 1, 2, 1, false, ORD, false, false, 1, true>(g, s);
+            if (items > 128) launch_one<F, 1, 2, 2, true, ORD, false, 1, true>(g, s);
+            else if (items > 64) launch_one<F, 1, 2, 2, false, ORD, false, 1, true>(g, s);
+            else if (variant / 10 == 1) launch_one<F, 1, 1, 1, false, ORD, false, 1, true>(g, s);
+            else if (variant / 10 == 3) launch_one<F, 1, 3, 1, false, ORD, false, 1, true>(g, s);
+            else launch_one<F, 1, 2, 1, false, ORD, false, 1, true>(g, s);
             return;
         }
     }
@@ -2255,20 +2236,14 @@ void launch_stream(const mi_mmv_group & g, int variant, hipStream_t s) {
         // tall lone members with rows of <= 16 items (GPT-2 lm_head: 50257 x 768, 12 Q4_K items per
         // row): four rows per wave step on 16 lanes each (MR = 4); variant 9x: the one-row form
         if (g.n == 1 && g.N >= 16384 && items <= 16 && variant / 10 != 9) {
-            if (pro_epi) launch_one<F, 1, 4, 1, false, ORD, true, false, 4>(g, s);
-            else launch_one<F, 1, 4, 1, false, ORD, false, false, 4>(g, s);
+            if (pro_epi) launch_one<F, 1, 4, 1, false, ORD, true, 4>(g, s);
+            else launch_one<F, 1, 4, 1, false, ORD, false, 4>(g, s);
             return;
         }
     }
     if (pro_epi) {
         // the graph's norm prologue and/or epilogue: instances of their own (prefetch depth 1) so
         // that their registers and per-row branches do not weigh on the plain kernels
-        if (xf) {
-            if (items > 128) launch_one<F, NC, 2, 2, true, ORD, true, true>(g, s);
-            else if (items > 64) launch_one<F, NC, 2, 2, false, ORD, true, true>(g, s);
-            else launch_one<F, NC, 4, 1, false, ORD, true, true>(g, s);
-            return;
-        }
         if (items > 128) launch_one<F, NC, 1, 2, true, ORD, true>(g, s);
         else if (items > 64) launch_one<F, NC, 1, 2, false, ORD, true>(g, s);
         else launch_one<F, NC, 1, 1, false, ORD, true>(g, s);
@@ -2276,13 +2251,8 @@ void launch_stream(const mi_mmv_group & g, int variant, hipStream_t s) {
     }
     if (items > 64) {
         // two items per lane in the ring (Q4_0 / Q8_0 at K=4096)
-        if (xf) launch_tail<F, NC, 2, 2, ORD, true>(g, s);
-        else if (variant / 10 == 1) launch_tail<F, NC, 1, 2, ORD>(g, s);
+        if (variant / 10 == 1) launch_tail<F, NC, 1, 2, ORD>(g, s);
         else launch_tail<F, NC, 2, 2, ORD>(g, s);
-        return;
-    }
-    if (xf) {
-        launch_one<F, NC, 4, 1, false, ORD, false, true>(g, s);
         return;
     }
     switch (variant / 10) {

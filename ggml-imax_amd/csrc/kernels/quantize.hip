@@ -26,7 +26,7 @@ static __device__ __forceinline__ const float * col_ptr(const mi_src_cols & x, u
     return (const float *) (x.base + (size_t) i1 * x.nb1 + (size_t) i2 * x.nb2 + (size_t) i3 * x.nb3);
 }
 
-// f16 GEMM operand layouts: row-major [ncols][K], or K-blocked [K/16][ncols][16] (nblk > 0 =
+// f16 activation layouts (mi_convert_f16): row-major [ncols][K], or K-blocked [K/16][ncols][16] (nblk > 0 =
 // ncols) so that the 32 columns x 16 halves of one MFMA K step are 1 KB of contiguous memory
 static __device__ __forceinline__ int64_t xh_index(int64_t c, int64_t k, int64_t K, int64_t nblk) {
     return nblk ? ((k >> 4) * nblk + c) * 16 + (k & 15) : c * K + k;
@@ -53,11 +53,9 @@ mi_act_q8 mi_act_q8_carve(void * base, int64_t K, int64_t ncols, mi_act_quant q)
 }
 
 // One 32-element block per half-wave, one element per lane; grid (column, group of 8 blocks).
-// XH: write f16(d * q) to xh[c*K + k] (the batched-prompt GEMM's operand, mmq.hip) instead of the
-// q8 blocks. S1: Q8_1 -- also the block's s, as fp16 bits in act.s32.
-template <bool XH, bool S1 = false>
-__global__ __launch_bounds__(256) void k_quantize_q8_0(mi_src_cols x, int64_t K, mi_act_q8 act, uint16_t * xh,
-                                                       int64_t xh_blk = 0) {
+// S1: Q8_1 -- also the block's s, as fp16 bits in act.s32.
+template <bool S1>
+__global__ __launch_bounds__(256) void k_quantize_q8_0(mi_src_cols x, int64_t K, mi_act_q8 act) {
     const int64_t nb_per_col = K / 32;
     const int64_t b = (int64_t) blockIdx.y * 8 + (threadIdx.x >> 5);
     const int l = threadIdx.x & 31;
@@ -70,10 +68,6 @@ __global__ __launch_bounds__(256) void k_quantize_q8_0(mi_src_cols x, int64_t K,
     const float d = amax / 127.f;
     const float id = amax != 0.0f ? 127.f / amax : 0.0f;
     const float q = __builtin_rintf(__fmul_rn(v, id));
-    if constexpr (XH) {
-        xh[xh_index(c, b * 32 + l, K, xh_blk)] = mi_f2h(mi_h2f(mi_f2h(d)) * (float) (int8_t) (int) q);
-        return;
-    }
     act.qs[c * K + b * 32 + l] = (int8_t) (int) q;
     if (l == 0) act.d[c * nb_per_col + b] = mi_h2f(mi_f2h(d));
     if constexpr (S1) {
@@ -85,10 +79,8 @@ __global__ __launch_bounds__(256) void k_quantize_q8_0(mi_src_cols x, int64_t K,
 }
 
 // One 256-element superblock per wave, four consecutive elements per lane; grid (column, group of
-// 4 superblocks) (XH as for q8_0).
-template <bool XH>
-__global__ __launch_bounds__(256) void k_quantize_q8_K(mi_src_cols x, int64_t K, mi_act_q8 act, uint16_t * xh,
-                                                       int64_t xh_blk = 0) {
+// 4 superblocks).
+__global__ __launch_bounds__(256) void k_quantize_q8_K(mi_src_cols x, int64_t K, mi_act_q8 act) {
     const int wave = __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const int64_t nb_per_col = K / 256;
@@ -112,24 +104,6 @@ __global__ __launch_bounds__(256) void k_quantize_q8_K(mi_src_cols x, int64_t K,
         const float ov = __shfl_xor(vmax, off, 64);
         const int oi = __shfl_xor(idx, off, 64);
         if (oa > amax || (oa == amax && oi < idx)) { amax = oa; vmax = ov; idx = oi; }
-    }
-    if constexpr (XH) {
-        uint2 o = make_uint2(0, 0);
-        if (amax != 0.0f) {
-            const float iscale = -127.f / vmax;
-            const float d = 1.0f / iscale;
-            uint32_t h[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int bits = __float_as_int(__builtin_fmaf(iscale, v[i], 12582912.f));
-                int q = (bits & 0x007fffff) - 0x00400000;
-                q = q < 127 ? q : 127;
-                h[i] = mi_f2h(d * (float) (int8_t) q);
-            }
-            o = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
-        }
-        *(uint2 *) (xh + xh_index(c, b * 256 + lane * 4, K, xh_blk)) = o;
-        return;
     }
     int8_t * qs = act.qs + c * K + b * 256;
     int16_t * s32 = act.s32 + c * (K / 32) + b * 8;
@@ -173,33 +147,17 @@ __global__ __launch_bounds__(256) void k_convert_f16(mi_src_cols x, int64_t K, u
 
 void mi_quantize_q8_0(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, hipStream_t s) {
     if (act.ncols == 0 || K < 32) return;
-    hipLaunchKernelGGL(k_quantize_q8_0<false>, dim3((unsigned) act.ncols, (unsigned) ((K / 32 + 7) / 8)), dim3(256), 0, s, x, K, act,
-                       nullptr);
+    hipLaunchKernelGGL(k_quantize_q8_0<false>, dim3((unsigned) act.ncols, (unsigned) ((K / 32 + 7) / 8)), dim3(256), 0, s, x, K, act);
 }
 
 void mi_quantize_q8_1(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, hipStream_t s) {
     if (act.ncols == 0 || K < 32) return;
-    hipLaunchKernelGGL((k_quantize_q8_0<false, true>), dim3((unsigned) act.ncols, (unsigned) ((K / 32 + 7) / 8)), dim3(256), 0, s, x, K,
-                       act, nullptr, 0);
+    hipLaunchKernelGGL(k_quantize_q8_0<true>, dim3((unsigned) act.ncols, (unsigned) ((K / 32 + 7) / 8)), dim3(256), 0, s, x, K, act);
 }
 
 void mi_quantize_q8_K(const mi_src_cols & x, int64_t K, const mi_act_q8 & act, hipStream_t s) {
     if (act.ncols == 0 || K < 256) return;
-    hipLaunchKernelGGL(k_quantize_q8_K<false>, dim3((unsigned) act.ncols, (unsigned) ((K / 256 + 3) / 4)), dim3(256), 0, s, x, K, act,
-                       nullptr);
-}
-
-void mi_quantize_expand_f16(const mi_src_cols & x, int64_t K, int64_t ncols, mi_act_quant q, uint16_t * xh, hipStream_t s,
-                            bool blocked) {
-    const int64_t xb = blocked ? ncols : 0;
-    if (ncols == 0 || K < 32) return;
-    if (q == MI_ACT_Q8_K) {
-        hipLaunchKernelGGL(k_quantize_q8_K<true>, dim3((unsigned) ncols, (unsigned) ((K / 256 + 3) / 4)), dim3(256), 0, s, x, K,
-                           mi_act_q8{}, xh, xb);
-    } else {
-        hipLaunchKernelGGL(k_quantize_q8_0<true>, dim3((unsigned) ncols, (unsigned) ((K / 32 + 7) / 8)), dim3(256), 0, s, x, K,
-                           mi_act_q8{}, xh, xb);
-    }
+    hipLaunchKernelGGL(k_quantize_q8_K, dim3((unsigned) act.ncols, (unsigned) ((K / 256 + 3) / 4)), dim3(256), 0, s, x, K, act);
 }
 
 void mi_convert_f16(const mi_src_cols & x, int64_t K, uint16_t * out, hipStream_t s, bool blocked, bool src_f16) {

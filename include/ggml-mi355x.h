@@ -55,7 +55,7 @@ GGML_API void * ggml_backend_mi355x_get_stream(ggml_backend_t backend);
 GGML_API int ggml_backend_mi355x_last_launch_count(ggml_backend_t backend);
 
 // The kernel the launchers picked for the most recent quantized MUL_MAT / MUL_MAT_ID launch from the
-// host (a replayed capture launches none): a static string such as "k_mmqp", "k_mmqd1",
+// host (a replayed capture launches none): a static string such as "k_mmqp", "k_mmqt",
 // "k_mmv_kq_ord<nc8>" or "k_mmv_stream<type12,nc1,pd3,...>"; "" before the first. For tests: a forced
 // route (set_tuning) that the shape makes the launcher ignore shows here.
 GGML_API const char * ggml_backend_mi355x_last_mul_mat_route(ggml_backend_t backend);

@@ -33,7 +33,7 @@ F32 = [c["id"] for c in bc.CASES if c["f32"]]
 KQ_ALL = [c["id"] for c in bc.CASES if c["type"] in KQ]
 LEGACY_ALL = [c["id"] for c in bc.CASES if c["type"] not in KQ]
 LEGACY_F32 = [c for c in F32 if bc.BY_ID[c]["type"] not in KQ]
-DEFAULTS = dict(mmv_order=-1, mmv_variant=0, mmq_variant=0, q40r=1, q80r=1, xfirst=-1, planes=0, mmqt_short=192, mmid_group=1, mmid_stream=8)
+DEFAULTS = dict(mmv_order=-1, mmv_variant=0, mmq_variant=0, q40r=1, q80r=1, planes=0, mmqt_short=192, mmid_group=1, mmid_stream=8)
 FRACTIONS = {}
 
 
@@ -196,20 +196,6 @@ def test_decode_repacked_copy_on_and_off(rt, backend, oracle_y, cid):
             check(c, K, 1, y, 0, "decode repacked" if on else "decode canonical blocks", oracle_y)
 
 
-@pytest.mark.parametrize("cid", F32)
-def test_decode_activations_first(rt, backend, oracle_y, cid):
-    """xfirst 1: the XF instances of a lone GEMV."""
-    c = bc.BY_ID[cid]
-    for K in (256, 2304):
-        for B in (1, 5):
-            for order in (0, 1):
-                with knobs(rt, mmv_order=order, xfirst=1):
-                    y = run_case(rt, backend, c, K, B)
-                    r = route(rt, backend)
-                assert r.startswith(stream_prefix(c["type"])) and ",xf1," in r, r
-                check(c, K, B, y, order, "decode xfirst", oracle_y)
-
-
 TALL_N = 16384  # launch_stream: a lone one-column GEMV of at least this many rows of <= 16 items runs four rows per wave step
 
 
@@ -299,7 +285,7 @@ def test_prompt_of_unaligned_columns_takes_the_generic_gemv(rt, backend, oracle_
     c = bc.BY_ID[cid]
     t = c["type"]
     for K in (256, 2304):
-        for B, v in ((9, 0), (17, 2048 if t in KQ else 128)):
+        for B, v in ((9, 0), (17, 128)):
             with knobs(rt, mmv_order=0, mmq_variant=v):
                 y = run_case(rt, backend, c, K, B)
                 r = route(rt, backend)
@@ -317,25 +303,22 @@ def kq_prefill_route(t, S, B, var):
             return "k_mmqx"
         return "k_mmqt" if q4 else "k_mmqw" if S % 4 == 0 else "k_mmqx"
     if B <= 128:
-        if var & (1 << 21) and B <= 16:
-            return "k_mmqd16"
-        return "k_mmqd1" if var & 2048 else "k_mmqp8" if var & (1 << 27) else "k_mmqp"
+        return "k_mmqp"
     return "k_mmqx_half" if q4 else "k_mmqw" if S % 4 == 0 else "k_mmqx"
 
 
-KQ_VARIANTS = (2048, 1 << 27, 128 | 131072, 128 | 65536, 128 | 131072 | (1 << 28))
+KQ_VARIANTS = (128 | 131072, 128 | 65536, 128 | 131072 | (1 << 28))
 
 
 @pytest.mark.parametrize("cid", KQ_ALL)
 def test_prefill_mfma_kernels_k_quants(rt, backend, oracle_y, cid):
     """Tree order, F32 and hand-made Q8_K src1 (the MFMA layout of pre-quantized rows): the default kernel at
-    B in {9, 13, 16, 33, 72, 130}, every mmq_variant of test_prefill_kernels_bit_equal at B in {13, 72, 130},
-    k_mmqd16 at 9 and 16; K = 1024 besides for Q5_K's k_mmqw (superblock counts that are multiples of 4)."""
+    B in {9, 13, 16, 33, 72, 130}, every mmq_variant of test_prefill_kernels_bit_equal at B in {13, 72, 130};
+    K = 1024 besides for Q5_K's k_mmqw (superblock counts that are multiples of 4)."""
     c = bc.BY_ID[cid]
     t = c["type"]
     runs = [(K, B, 0) for K in KS for B in (9, 13, 16, 33, 72, 130)]
     runs += [(K, B, v) for K in KS for B in (13, 72, 130) for v in KQ_VARIANTS]
-    runs += [(K, B, 1 << 21) for K in KS for B in (9, 16)]
     if t == bc.Q5_K:
         runs += [(1024, 130, 0), (1024, 72, 128 | 131072)]
     for K, B, v in runs:
@@ -346,7 +329,7 @@ def test_prefill_mfma_kernels_k_quants(rt, backend, oracle_y, cid):
         check(c, K, B, y, 0, "prefill " + r, oracle_y, n=NP)
 
 
-LEGACY_VARIANTS = {0: "k_mmq0p", 16: "k_mmq0p", 128: "k_mmq0x", 128 | 65536: "k_mmq0x_half", 128 | (1 << 24): "k_mmq0x_rows2",
+LEGACY_VARIANTS = {0: "k_mmq0p", 16: "k_mmq0p", 128: "k_mmq0x_rows2", 128 | 65536: "k_mmq0x_half", 128 | (1 << 24): "k_mmq0x_rows2",
                    128 | (1 << 25): "k_mmq0x_rows2_w8"}
 
 

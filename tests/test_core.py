@@ -39,6 +39,25 @@ def test_backend_exports_every_declared_symbol(rt):
     assert not missing, missing
 
 
+def test_removed_knobs_and_variant_bits_are_refused(rt):
+    """set_tuning knows no `xfirst`, and mmq_variant takes the seven bits of mi_mmq_variant_bits only: a script
+    that still asks for a removed kernel fails instead of timing the default."""
+    st = rt.ggml_backend_mi355x_set_tuning
+    assert not st(b"xfirst", 1)
+    removed = (1, 2, 64, 2048, 4096, 8192, 1 << 18, 1 << 20, 1 << 21, 1 << 22, 1 << 27, 1 << 30)
+    kept = (16, 128, 1 << 16, 1 << 17, 1 << 24, 1 << 25, 1 << 28)
+    try:
+        for v in removed:
+            assert not st(b"mmq_variant", v), v
+            assert not st(b"mmq_variant", v | 128), v
+        for v in kept:
+            assert st(b"mmq_variant", v), v
+        assert st(b"mmq_variant", sum(kept))
+        assert not st(b"mmq_variant", -1)
+    finally:
+        assert st(b"mmq_variant", 0)
+
+
 def test_core_exports_every_declared_symbol(rt):
     lib = ctypes.CDLL(G.CORE_LIB)
     names = _declared("ggml_abi.h")

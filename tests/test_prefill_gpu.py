@@ -143,20 +143,19 @@ def test_prefill_kernels_bit_equal(rt, backend, tname, B):
     """Every prefill kernel shares the canonical combine (exact T and U per superblock, terms
     combined in the cfold order: 8 contiguous superblock groups, each left-folded; groups 0-3 and
     4-7 left-folded separately, then added), so any kernel choice gives the same bits: k_mmqp (the default for <= 128
-    columns), k_mmqd1 (variant bit 2048), k_mmqp with 8 waves (2^27), the long-prompt kernels forced
-    onto these shapes (128 | 131072: k_mmqt for Q4_K, k_mmqw for Q5_K; with 2^28 k_mmqx full width;
-    128 | 65536 k_mmqx half width) and, for <= 16
-    columns, k_mmqd16 (variant bit 2^21; 16 x 16 tiles on the 16x16x64 MFMA). Q4_0 / Q8_0:
-    k_mmq0p (32 x 32 tiles, <= 64 columns) and k_mmq0x (weights staged per 64 x 128 workgroup)."""
+    columns) and the long-prompt kernels forced onto these shapes (128 | 131072: k_mmqt for Q4_K, k_mmqw for
+    Q5_K; with 2^28 k_mmqx full width; 128 | 65536 k_mmqx half width). Q4_0 / Q8_0:
+    k_mmq0p (32 x 32 tiles) and k_mmq0x (weights staged per workgroup: 64 x 128 with 128, 64 x 64 with 128 | 65536,
+    64 x 256 on 8 waves with 128 | 2^25)."""
     t = orc.TYPES_BY_NAME[tname]
     K, N = 4096, 320
     w = synth.uniform(11, K * N)
     x = synth.uniform(12, K * B)
     wq = orc.quantize(t, w, K)
-    if tname in ("q4_0", "q8_0"):  # k_mmq0p (16), k_mmq0x full / half width (128, 128 | 65536)
+    if tname in ("q4_0", "q8_0"):  # k_mmq0p (16), k_mmq0x NR = 2 / half width (128, 128 | 65536)
         variants = [0, 16, 128, 128 | 65536, 128 | (1 << 24), 128 | (1 << 25)]
     else:
-        variants = [0, 2048, 1 << 27, 128 | 131072, 128 | 65536, 128 | 131072 | (1 << 28)] + ([1 << 21] if B <= 16 else [])
+        variants = [0, 128 | 131072, 128 | 65536, 128 | 131072 | (1 << 28)]
     outs = {}
     try:
         for v in variants:

@@ -1,5 +1,5 @@
 // kfloor.hip -- what a dependent kernel costs before it does any work, by launch geometry: the
-// floor under the short-prompt prefill kernels (k_quantize_q8_K_mmx, k_mmqd1). Back-to-back
+// floor under the short-prompt prefill kernels (k_quantize_q8_K_mmx, a GEMM tile of 1024 threads and 66 KB of LDS). Back-to-back
 // launches on one stream, HIP events around 400 of them (per-launch = the chain's step time).
 //   hipcc --offload-arch=gfx950 -O3 tools/kfloor.hip -o tools/kfloor && tools/kfloor
 #include <hip/hip_runtime.h>
