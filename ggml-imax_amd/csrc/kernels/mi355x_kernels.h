@@ -189,11 +189,17 @@ extern mi_tuning g_mi_tuning;
 // the order of the graph being launched when mmv_order is -1 (set by the backend per graph)
 extern thread_local int tl_mi_graph_order;
 inline int mi_mmv_order() { return g_mi_tuning.mmv_order >= 0 ? g_mi_tuning.mmv_order : tl_mi_graph_order; }
-// The kernel the launchers picked for the most recent quantized MUL_MAT / MUL_MAT_ID launch: a static
-// string stored at each selection site (ggml_backend_mi355x_last_mul_mat_route; the tests assert that a
-// forced route was taken). A replayed capture launches no kernel from the host and leaves it alone.
+// The kernel the launchers picked for the most recent MUL_MAT / MUL_MAT_ID launch (quantized, BF16 aside:
+// every F16 selection site too -- mi_mul_mat_f16_fast, the ordered launchers, mi_mul_mat_f16p,
+// mi_mul_mat_mmq, the generic mi_mul_mat_f16): a string that lives as long as the library, stored at each
+// selection site (ggml_backend_mi355x_last_mul_mat_route; the tests assert that a forced route was taken).
+// It names the kernel and the template arguments that select an instance, then in square brackets the
+// launch geometry a knob moves: "k_gemv_f16<nc4,u2,one,jm0,epi1,xh0>[ks3,rgs1]". A replayed capture
+// launches no kernel from the host and leaves it alone.
 extern const char * g_mi_last_route;
 inline void mi_route(const char * name) { g_mi_last_route = name; }
+// the same with a name formatted on the first launch of `key` (unique per site and instance) and kept
+void mi_route_fmt(uint32_t key, const char * fmt, ...) __attribute__((format(printf, 2, 3)));
 size_t mi_mmv_fused_lds_bytes(int type, int64_t K, int64_t ncols);
 void mi_mul_mat_q_fused(mi_mmv_group & g, hipStream_t s);
 // its per-format launchers, specialized in mmv_fused_q2k.hip, _q3k, _q4k, _q5k, _q6k, _q40, _q80, _q41, _q50, _q51, _iq4nl, _iq4xs (one

@@ -277,6 +277,7 @@ bool mi_mmf16p_supported(int64_t K, int64_t N, size_t nb01, int64_t ncols, size_
 void mi_mul_mat_f16p(const void * W, size_t nb01, int64_t K, int64_t N, const uint16_t * xh, int64_t ncols, float * dst, size_t ycol,
                      hipStream_t s) {
     const int64_t tiles = ((N + 31) / 32) * ((ncols + 31) / 32);
+    mi_route("k_mmf16p<pf3>");
     hipLaunchKernelGGL((k_mmf16p<3>), dim3((unsigned) tiles), dim3(256), 0, s, (const uint8_t *) W, nb01, K, N, xh, ncols, dst, ycol);
 }
 
@@ -292,7 +293,8 @@ void mi_mul_mat_mmq(const void * W, size_t nb01, int64_t K, int64_t N, const uin
     // runtime-K loop makes the compiler drain the load ring: measured 47 -> 43 us at 4096)
     const bool sk2 = K % (2 * BK * kPF) == 0;
     const int nst2 = sk2 ? (int) (K / BK / 2) : 0;
-#define MI_MMQ3(SK, NST) hipLaunchKernelGGL((k_mmq3<SK, NST>), grid, dim3(256 * SK), 0, s, w, nb01, K, N, xh, ncols, dst, ycol)
+#define MI_MMQ3(SK, NST) do { mi_route("k_mmq3<sk" #SK ",nst" #NST ">"); \
+        hipLaunchKernelGGL((k_mmq3<SK, NST>), grid, dim3(256 * SK), 0, s, w, nb01, K, N, xh, ncols, dst, ycol); } while (0)
     if (nst2 == 32) MI_MMQ3(2, 32);
     else if (nst2 == 24) MI_MMQ3(2, 24);
     else if (nst2 == 16) MI_MMQ3(2, 16);

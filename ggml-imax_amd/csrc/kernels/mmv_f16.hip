@@ -9,8 +9,9 @@
 // bias / residual / GELU nodes and K/V row copies are applied in the store. What differs from the
 // reference is only the order of the f32 sums (products of two halves are exact in f32; lane
 // partial sums + a 16-lane tree instead of ggml_vec_dot_f16's 32 AVX partial sums + the
-// GGML_F32x8_REDUCE tree, src/ggml.c:1680-1720), and the norm's sums (f32 tree instead of a
-// sequential double), ~1e-7 relative per dot.
+// GGML_F32x8_REDUCE tree, src/ggml.c:1680-1720), ~1e-7 relative per dot. The norm's sums are double
+// as the reference's, in tree order: the normalized f16 activations are the reference's bits
+// (norm_store).
 //
 // Geometry (wave64): 16 lanes per weight row, four rows per wave, one to four waves per
 // workgroup. Lane m of a row reads the row's 16-byte chunks m, m + 16, ... (a wave-instruction
@@ -91,31 +92,37 @@ __device__ __forceinline__ void norm_load(const float * __restrict__ xc, int64_t
 template <int JM, bool GB>
 __device__ __forceinline__ void norm_store(float4 (&v)[JM], const float4 (&g)[GB ? JM : 1], const float4 (&bb)[GB ? JM : 1], int64_t K,
                                            int64_t kp, const mi_norm_prologue & pro, uint16_t * xs, int lane) {
-    const float fk = (float) K;
+    // The sums in double, as the reference's (f32 terms, double accumulator, the quotient rounded to f32): the f32
+    // mean, variance and scale are then the reference's own unless the order of the double sums decides a
+    // float rounding (~K 2^-29 of the columns), so the f16 activations are its bits. With f32 tree sums the
+    // scale came out an ulp off for a good share of the columns, and with it single activations one f16
+    // step off: 2^-11 of a term, outside the summation bound of the dot (tests/f16_cases.py, S-range-rms).
+    const double dk = (double) K;
 #pragma unroll
     for (int j = 0; j < JM; j++)  // elements past K (clamped loads) are zero
         if ((int64_t) j * 256 + lane * 4 >= K) v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
     float scale;
     if (pro.mode == 2) {
-        float s2 = 0.0f;
+        double s2 = 0.0;
 #pragma unroll
-        for (int j = 0; j < JM; j++) s2 += (v[j].x * v[j].x + v[j].y * v[j].y) + (v[j].z * v[j].z + v[j].w * v[j].w);
-        scale = 1.0f / sqrtf(mi_wave_sum_u(s2) / fk + pro.eps);
+        for (int j = 0; j < JM; j++)
+            s2 += ((double) (v[j].x * v[j].x) + (double) (v[j].y * v[j].y)) + ((double) (v[j].z * v[j].z) + (double) (v[j].w * v[j].w));
+        scale = 1.0f / sqrtf((float) (mi_wave_sum_u_f64(s2) / dk) + pro.eps);
     } else {
-        float s = 0.0f;
+        double s = 0.0;
 #pragma unroll
-        for (int j = 0; j < JM; j++) s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
-        const float mean = mi_wave_sum_u(s) / fk;
-        float s2 = 0.0f;
+        for (int j = 0; j < JM; j++) s += ((double) v[j].x + (double) v[j].y) + ((double) v[j].z + (double) v[j].w);
+        const float mean = (float) (mi_wave_sum_u_f64(s) / dk);
+        double s2 = 0.0;
 #pragma unroll
         for (int j = 0; j < JM; j++) {
             const int64_t k = (int64_t) j * 256 + lane * 4;
             if (k < K) {
                 v[j].x -= mean; v[j].y -= mean; v[j].z -= mean; v[j].w -= mean;
-                s2 += (v[j].x * v[j].x + v[j].y * v[j].y) + (v[j].z * v[j].z + v[j].w * v[j].w);
+                s2 += ((double) (v[j].x * v[j].x) + (double) (v[j].y * v[j].y)) + ((double) (v[j].z * v[j].z) + (double) (v[j].w * v[j].w));
             }
         }
-        scale = 1.0f / sqrtf(mi_wave_sum_u(s2) / fk + pro.eps);
+        scale = 1.0f / sqrtf((float) (mi_wave_sum_u_f64(s2) / dk) + pro.eps);
     }
 #pragma unroll
     for (int j = 0; j < JM; j++) {
@@ -830,6 +837,9 @@ void launch_nc(const void * W, size_t nb01, int64_t K, int64_t N, const mi_src_c
     const size_t lds = (size_t) (priv ? ks : NC) * kp * sizeof(uint16_t) + (size_t) ks * rgs * 4 * NC * sizeof(float);
     const int epi = e.gelu_table ? 3 : (e.resid ? 2 : (e.bias ? 1 : 0));
     const uint8_t * w = (const uint8_t *) W;
+    const int xhv = JM == 0 && xh ? 1 : 0;
+    mi_route_fmt(1u << 28 | (uint32_t) (NC << 20 | U << 16 | (int) ONE << 15 | JM << 11 | epi << 9 | xhv << 8 | ks << 4 | rgs),
+                 "k_gemv_f16<nc%d,u%d,%s,jm%d,epi%d,xh%d>[ks%d,rgs%d]", NC, U, ONE ? "one" : "ring", JM, epi, xhv, ks, rgs);
 #define MI_GEMV_F16X(EP, XHV) hipLaunchKernelGGL((k_gemv_f16<NC, EP, U, ONE, JM, XHV>), grid, dim3(64 * ks * rgs), lds, s, w, nb01, K, N, x, xh, ncols, dst, ycol, e, pro, kp, rgs)
 #define MI_GEMV_F16(EP) do { if constexpr (JM == 0) { if (xh) MI_GEMV_F16X(EP, true); else MI_GEMV_F16X(EP, false); } else MI_GEMV_F16X(EP, false); } while (0)
     switch (epi) {
@@ -923,6 +933,7 @@ void mi_mul_mat_f16_fast(const void * W, size_t nb01, int64_t K, int64_t N, cons
             // several columns on the matrix cores (k_gemv_f16_mt): 16-row tiles, grid-stride
             const dim3 gridm((unsigned) std::min<int64_t>(((N + 15) / 16 + 3) / 4, 512));
             const size_t ldsm = (size_t) 8 * kp * sizeof(uint16_t);
+            mi_route_fmt(3u << 28 | (uint32_t) ((pro.mode ? 4 : 0) << 4 | epi), "k_gemv_f16_mt<jm%d,nk24,epi%d>", pro.mode ? 4 : 0, epi);
 #define MI_GEMV_MT(EP, JMV) hipLaunchKernelGGL((k_gemv_f16_mt<EP, JMV, 24>), gridm, dim3(256), ldsm, s, w, nb01, K, N, x, (int) ncols, dst, ycol, e, pro, kp)
             if (pro.mode) {
                 if (epi == 0) MI_GEMV_MT(0, 4); else if (epi == 1) MI_GEMV_MT(1, 4); else MI_GEMV_MT(3, 4);
@@ -935,6 +946,7 @@ void mi_mul_mat_f16_fast(const void * W, size_t nb01, int64_t K, int64_t N, cons
 #define MI_GEMV_TALL_N(EP, JMV, NCV) hipLaunchKernelGGL((k_gemv_f16_tall<EP, 8, JMV, NCV>), grid, dim3(256), lds, s, w, nb01, K, N, x, (int) ncols, dst, ycol, e, pro, kp)
 #define MI_GEMV_TALL(EP, JMV) do { switch (nc) { case 1: MI_GEMV_TALL_N(EP, JMV, 1); break; case 2: MI_GEMV_TALL_N(EP, JMV, 2); break; \
                                                   case 4: MI_GEMV_TALL_N(EP, JMV, 4); break; default: MI_GEMV_TALL_N(EP, JMV, 8); break; } } while (0)
+        mi_route_fmt(2u << 28 | (uint32_t) (nc << 8 | (pro.mode ? 4 : 0) << 4 | epi), "k_gemv_f16_tall<nc%d,u8,jm%d,epi%d>", nc, pro.mode ? 4 : 0, epi);
         if (pro.mode) {
             if (epi == 0) MI_GEMV_TALL(0, 4); else if (epi == 1) MI_GEMV_TALL(1, 4); else MI_GEMV_TALL(3, 4);
         } else {
@@ -962,6 +974,8 @@ void mi_mul_mat_f16_fast(const void * W, size_t nb01, int64_t K, int64_t N, cons
             case 2: MI_GEMV_PS(2, NPM, QPT); break; \
             default: MI_GEMV_PS(3, NPM, QPT); break; \
         }
+        mi_route_fmt(4u << 28 | (uint32_t) ((pro.nparts <= 12 ? 12 : 16) << 12 | (qpt <= 1 ? 1 : 2) << 8 | epi << 4 | rw),
+                     "k_gemv_f16_ps<npm%d,qpt%d,epi%d>[rw%d]", pro.nparts <= 12 ? 12 : 16, qpt <= 1 ? 1 : 2, epi, rw);
         if (qpt <= 1) {
             if (pro.nparts <= 12) { MI_GEMV_PS_E(12, 1) } else { MI_GEMV_PS_E(16, 1) }
         } else {
@@ -982,6 +996,7 @@ void mi_mul_mat_f16_fast(const void * W, size_t nb01, int64_t K, int64_t N, cons
 #define MI_GEMV_BN(EP, NWV, KSV) hipLaunchKernelGGL((k_gemv_f16_bn<EP, 4, NWV, KSV>), grid, dim3(64 * NWV), lds, s, w, nb01, K, N, x, ncols, dst, ycol, e, pro, kp)
 #define MI_GEMV_BN_E(NWV, KSV) switch (epi) { case 0: MI_GEMV_BN(0, NWV, KSV); break; case 1: MI_GEMV_BN(1, NWV, KSV); break; \
                                                   case 2: MI_GEMV_BN(2, NWV, KSV); break; default: MI_GEMV_BN(3, NWV, KSV); break; }
+        mi_route_fmt(5u << 28 | (uint32_t) (NWv << 8 | KSv << 4 | epi), "k_gemv_f16_bn<nw%d,ks%d,epi%d>", NWv, KSv, epi);
         if (bn == 5) { MI_GEMV_BN_E(16, 4) } else if (bn == 4) { MI_GEMV_BN_E(8, 4) } else if (KSv == 2) { MI_GEMV_BN_E(8, 2) }
         else if (NWv == 8) { MI_GEMV_BN_E(8, 1) } else { MI_GEMV_BN_E(4, 1) }
 #undef MI_GEMV_BN_E

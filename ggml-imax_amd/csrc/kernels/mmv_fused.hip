@@ -28,11 +28,14 @@
 
 #include <ctype.h>
 #include <limits.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <mutex>
 #include <string>
+#include <unordered_map>
 
 // The one list of knobs: set_tuning(name, v) and GGML_MI355X_<NAME>=v (read once at start-up) both go
 // through mi_tuning_set, so both accept lo <= v <= hi (and ok(v) where a knob takes only some values).
@@ -96,6 +99,22 @@ mi_tuning tuning_from_env() {
 mi_tuning g_mi_tuning = tuning_from_env();
 thread_local int tl_mi_graph_order = 0;
 const char * g_mi_last_route = "";
+
+void mi_route_fmt(uint32_t key, const char * fmt, ...) {
+    static std::mutex mu;
+    static std::unordered_map<uint32_t, std::string> names;  // (node-based: a stored string never moves)
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = names.find(key);
+    if (it == names.end()) {
+        char buf[128];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(buf, sizeof(buf), fmt, ap);
+        va_end(ap);
+        it = names.emplace(key, buf).first;
+    }
+    g_mi_last_route = it->second.c_str();
+}
 
 bool mi_tuning_set(const char * name, int value) { return knob_set(g_mi_tuning, name, value); }
 

@@ -505,6 +505,7 @@ void launch_f16_w16(const void * W, size_t nb01, int64_t K, int64_t N, const mi_
     const dim3 grid((unsigned) ((N + rpb - 1) / rpb), (unsigned) ((ncols + NC - 1) / NC));
     const size_t lds = (size_t) NC * K * sizeof(uint16_t) + (pro.mode ? (size_t) K * sizeof(float) : 0);
     const int epi = e.gelu_table ? 3 : (e.resid ? 2 : (e.bias ? 1 : 0));
+    mi_route_fmt(6u << 28 | (uint32_t) (NC << 16 | kS << 8 | epi << 4 | threads / 64), "k_mmv_f16_w16<nc%d,ks%d,epi%d>[t%d]", NC, kS, epi, threads);
     switch (epi) {
         case 0: hipLaunchKernelGGL((k_mmv_f16_w16<NC, 0, kS>), grid, dim3(threads), lds, s, (const uint8_t *) W, nb01, K, N, x, xh, ncols, dst, ycol, e, pro); break;
         case 1: hipLaunchKernelGGL((k_mmv_f16_w16<NC, 1, kS>), grid, dim3(threads), lds, s, (const uint8_t *) W, nb01, K, N, x, xh, ncols, dst, ycol, e, pro); break;
@@ -520,6 +521,7 @@ void launch_f16_x_u(const void * W, size_t nb01, int64_t K, int64_t N, const mi_
     const dim3 grid((unsigned) ((N + rpb - 1) / rpb), (unsigned) ((ncols + NC - 1) / NC));
     const size_t lds = (size_t) NC * K * sizeof(uint16_t) + (pro.mode ? (size_t) K * sizeof(float) : 0);
     const int epi = e.gelu_table ? 3 : (e.resid ? 2 : (e.bias ? 1 : 0));
+    mi_route_fmt(7u << 28 | (uint32_t) (NC << 16 | U << 8 | epi << 4 | threads / 64), "k_mmv_f16_x<nc%d,u%d,epi%d>[t%d]", NC, U, epi, threads);
     switch (epi) {
         case 0: hipLaunchKernelGGL((k_mmv_f16_x<NC, 0, U>), grid, dim3(threads), lds, s, (const uint8_t *) W, nb01, K, N, x, xh, ncols, dst, ycol, e, pro); break;
         case 1: hipLaunchKernelGGL((k_mmv_f16_x<NC, 1, U>), grid, dim3(threads), lds, s, (const uint8_t *) W, nb01, K, N, x, xh, ncols, dst, ycol, e, pro); break;
@@ -869,6 +871,7 @@ template <int NC> void launch_f16(const mi_mm_desc & m, const uint16_t * xh, hip
     const ord_geom g = make_ord_geom(m, NC);
     const dim3 grid((unsigned) ((m.N + kQuadsPerBlock - 1) / kQuadsPerBlock), (unsigned) (g.col_chunks * m.ne12 * m.ne13));
     const bool aligned = m.K % 8 == 0 && ((uintptr_t) m.W | m.nb01 | m.nb02 | m.nb03 | (uintptr_t) xh) % 16 == 0;
+    mi_route_fmt(10u << 28 | (uint32_t) (NC << 4 | (int) aligned), "k_mmv_f16_ord<nc%d,aligned%d,id0>", NC, (int) aligned);
     if (aligned) hipLaunchKernelGGL((k_mmv_f16_ord<NC, true>), grid, dim3(256), 0, s, (const uint8_t *) m.W, xh, m.dst, g);
     else hipLaunchKernelGGL((k_mmv_f16_ord<NC, false>), grid, dim3(256), 0, s, (const uint8_t *) m.W, xh, m.dst, g);
 }
@@ -880,6 +883,7 @@ void mi_mul_mat_f16(const mi_mm_desc & m, const uint16_t * xh, hipStream_t s) {
         const ord_geom g = make_ord_geom(m, 1);
         const dim3 grid((unsigned) ((m.N + kQuadsPerBlock - 1) / kQuadsPerBlock), (unsigned) ((int64_t) m.id.n_ids * m.ne12));
         const bool aligned = m.K % 8 == 0 && ((uintptr_t) m.W | m.nb01 | m.nb02 | (uintptr_t) xh) % 16 == 0;
+        mi_route(aligned ? "k_mmv_f16_ord<nc1,aligned1,id1>" : "k_mmv_f16_ord<nc1,aligned0,id1>");
         if (aligned) hipLaunchKernelGGL((k_mmv_f16_ord<1, true, true>), grid, dim3(256), 0, s, (const uint8_t *) m.W, xh, m.dst, g);
         else hipLaunchKernelGGL((k_mmv_f16_ord<1, false, true>), grid, dim3(256), 0, s, (const uint8_t *) m.W, xh, m.dst, g);
         return;

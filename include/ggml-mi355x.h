@@ -54,10 +54,14 @@ GGML_API void * ggml_backend_mi355x_get_stream(ggml_backend_t backend);
 // Number of kernels launched by the last graph_compute (for tests / profiling).
 GGML_API int ggml_backend_mi355x_last_launch_count(ggml_backend_t backend);
 
-// The kernel the launchers picked for the most recent quantized MUL_MAT / MUL_MAT_ID launch from the
-// host (a replayed capture launches none): a static string such as "k_mmqp", "k_mmqt",
-// "k_mmv_kq_ord<nc8>" or "k_mmv_stream<type12,nc1,pd3,...>"; "" before the first. For tests: a forced
-// route (set_tuning) that the shape makes the launcher ignore shows here.
+// The kernel the launchers picked for the most recent quantized or F16 MUL_MAT / MUL_MAT_ID launch from
+// the host (a replayed capture launches none): a string that stays valid, such as "k_mmqp", "k_mmqt",
+// "k_mmv_kq_ord<nc8>", "k_mmv_stream<type12,nc1,pd3,...>", and for F16 weights
+// "k_gemv_f16<nc4,u2,one,jm0,epi1,xh0>[ks3,rgs1]", "k_gemv_f16_bn<nw16,ks4,epi3>", "k_gemv_f16_ps<npm12,qpt1,epi3>[rw4]",
+// "k_gemv_f16_tall<nc8,u8,jm4,epi1>", "k_gemv_f16_mt<jm0,nk24,epi0>", "k_mmv_f16_w16<nc1,ks48,epi0>[t256]",
+// "k_mmv_f16_x<nc1,u32,epi0>[t64]", "k_mmv_f16_ord<nc4,aligned1,id0>", "k_mmf16p<pf3>", "k_mmq3<sk2,nst16>": the
+// template arguments that select an instance, then in square brackets the launch geometry a knob moves.
+// "" before the first. For tests: a forced route (set_tuning) that the shape makes the launcher ignore shows here.
 GGML_API const char * ggml_backend_mi355x_last_mul_mat_route(ggml_backend_t backend);
 
 // hipGraphs. graph_compute captures a graph's launches and replays the capture whenever the same
