@@ -229,7 +229,7 @@ static std::vector<size_t> plan_graph(ggml_gallocr * ga, ggml_cgraph * g, std::u
 
     // 2) nodes in order; a base is released kFreeDelay nodes after its last consumer, so the
     //    outputs of the next few nodes never land on it. A backend that executes a short chain
-    //    of nodes as one kernel (ggml-mi355x.cpp node fusion) then never finds the chain's output
+    //    of nodes as one kernel (csrc/backend/fusion.cpp node fusion) then never finds the chain's output
     //    placed over the chain's inputs.
     constexpr int kFreeDelay = 4;
     std::vector<std::vector<ggml_tensor *>> release_at(g->n_nodes + kFreeDelay + 1);

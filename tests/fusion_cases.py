@@ -1,4 +1,4 @@
-"""Small graphs around the backend's fusion passes (ggml-mi355x.cpp: try_fuse_norm, try_fuse_softmax,
+"""Small graphs around the backend's fusion passes (csrc/backend/fusion.cpp: try_fuse_norm, try_fuse_softmax,
 collect_epilogue / try_fuse_f16_gemv / try_fuse_q_gemv, try_fuse_copies, try_fuse_embedding, plan_attention,
 try_fuse_attn_proj), shared by tests/test_fusion.py (reference CPU alone) and tests/test_fusion_gpu.py.
 

@@ -492,7 +492,7 @@ def _teacher_forced_direct(m, toks):
 
 def _run_sched_child(model_path, tmp_path, layers, order="1"):
     """order "1": the MI355X layers' decode GEMVs in the reference order (bit-identical splits);
-    None: the backend's default (per graph, ggml-mi355x.cpp graph_decode_order)."""
+    None: the backend's default (per graph, csrc/backend/graph.cpp graph_decode_order)."""
     import sys
     env = dict(os.environ)
     env.pop("GGML_MI355X_MMV_ORDER", None)
