@@ -219,19 +219,3 @@ __device__ __forceinline__ void mi_q8K_superblock(const float (&v)[4], int lane,
     sum32 = mi_sum8(s);
     d = 1.0f / iscale;
 }
-
-// 6-bit scale / min j of the 12-byte K-quant scale array (src/ggml-quants.c:1357-1364),
-// taking the array as three little-endian dwords.
-__device__ __forceinline__ void mi_scale_min_k4(int j, uint32_t s0, uint32_t s1, uint32_t s2, int & sc, int & m) {
-    auto byte = [&](int i) -> int {
-        const uint32_t w = i < 4 ? s0 : (i < 8 ? s1 : s2);
-        return (int) ((w >> (8 * (i & 3))) & 0xFF);
-    };
-    if (j < 4) {
-        sc = byte(j) & 63;
-        m = byte(j + 4) & 63;
-    } else {
-        sc = (byte(j + 4) & 0xF) | ((byte(j - 4) >> 6) << 4);
-        m = (byte(j + 4) >> 4) | ((byte(j) >> 6) << 4);
-    }
-}

@@ -40,6 +40,7 @@
 #pragma clang fp contract(off)
 
 #include "mmq_exact_common.h"
+#include "quant_decode.h"
 
 // ---- activations: q8_K quants in the MFMA layouts ------------------------------------------------
 // xq [K/32][ncols][32] int8 (a 32-deep MFMA step of 32 columns is one contiguous 1 KB), xd
@@ -299,11 +300,11 @@ __global__ __launch_bounds__(64 * NWV) void k_mmqx(mi_mmx_group g) {
         const uint32_t qh[4] = {raw.qh.x, raw.qh.y, raw.qh.z, raw.qh.w};
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            dq.lo[i] = q[i] & 0x0F0F0F0Fu;
-            dq.hi[i] = (q[i] >> 4) & 0x0F0F0F0Fu;
+            dq.lo[i] = qd_nib_lo(q[i]);
+            dq.hi[i] = qd_nib_hi(q[i]);
             if constexpr (F::Q5) {
-                dq.lo[i] |= ((qh[i] >> j0) & 0x01010101u) << 4;
-                dq.hi[i] |= ((qh[i] >> (j0 + 1)) & 0x01010101u) << 4;
+                dq.lo[i] |= qd_bit4(qh[i], j0);
+                dq.hi[i] |= qd_bit4(qh[i], j0 + 1);
             }
         }
     };
@@ -578,11 +579,11 @@ __global__ __launch_bounds__(768, 1) void k_mmqw(mi_mmx_group g) {
         uint32_t lo[4], hi[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            lo[i] = q[i] & 0x0F0F0F0Fu;
-            hi[i] = (q[i] >> 4) & 0x0F0F0F0Fu;
+            lo[i] = qd_nib_lo(q[i]);
+            hi[i] = qd_nib_hi(q[i]);
             if constexpr (F::Q5) {
-                lo[i] |= ((qh[i] >> j0) & 0x01010101u) << 4;
-                hi[i] |= ((qh[i] >> (j0 + 1)) & 0x01010101u) << 4;
+                lo[i] |= qd_bit4(qh[i], j0);
+                hi[i] |= qd_bit4(qh[i], j0 + 1);
             }
         }
         char * pl0 = lds + buf * kBuf + row * XR + 32 * j0 + 16 * hf;
@@ -843,8 +844,7 @@ __global__ __launch_bounds__(256, 2) void k_mmqp(mi_mmx_group grp) {
             load_w(nxt, sn);
             const uint32_t w0 = cur.hdr.y, w1 = cur.hdr.z, w2 = cur.hdr.w;
             // the 6-bit scales of sub-blocks 0..3 / 4..7 as bytes (get_scale_min_k4)
-            const uint32_t sca = w0 & 0x3F3F3F3Fu;
-            const uint32_t scb = (w2 & 0x0F0F0F0Fu) | ((w0 >> 2) & 0x30303030u);
+            const uint32_t sca = qd_kq_scales4<0>(w0, w2), scb = qd_kq_scales4<1>(w0, w2);
             const float dw = mi_h2f((uint16_t) (cur.hdr.x & 0xFFFF)), dm = mi_h2f((uint16_t) (cur.hdr.x >> 16));
             i32x16 acc[NP];
             uint32_t lo[4], hi[4];
@@ -855,8 +855,8 @@ __global__ __launch_bounds__(256, 2) void k_mmqp(mi_mmx_group grp) {
                     const uint32_t qv[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
                     for (int e = 0; e < 4; e++) {
-                        lo[e] = qv[e] & 0x0F0F0F0Fu;
-                        hi[e] = (qv[e] >> 4) & 0x0F0F0F0Fu;
+                        lo[e] = qd_nib_lo(qv[e]);
+                        hi[e] = qd_nib_hi(qv[e]);
                     }
                 }
                 uint32_t v[4];
@@ -865,7 +865,7 @@ __global__ __launch_bounds__(256, 2) void k_mmqp(mi_mmx_group grp) {
                     v[e] = (kk & 1) ? hi[e] : lo[e];
                     if constexpr (F::Q5) {
                         const uint32_t hb[4] = {cur.qh.x, cur.qh.y, cur.qh.z, cur.qh.w};
-                        v[e] |= ((hb[e] >> kk) & 0x01010101u) << 4;
+                        v[e] |= qd_bit4(hb[e], kk);
                     }
                 }
                 const uint32_t scw = kk < 4 ? sca : scb;
@@ -879,8 +879,7 @@ __global__ __launch_bounds__(256, 2) void k_mmqp(mi_mmx_group grp) {
                 xa[kk] = ld_x(sn, kk);
             }
             // U on the f16 MFMA: A = [S & 63, S >> 6] of the lane's column, B = [m, 64 m] of its row
-            const uint32_t ma = w1 & 0x3F3F3F3Fu;
-            const uint32_t mb = ((w2 >> 4) & 0x0F0F0F0Fu) | ((w1 >> 2) & 0x30303030u);
+            const uint32_t ma = qd_kq_mins4<0>(w1, w2), mb = qd_kq_mins4<1>(w1, w2);
             const uint32_t mw = h ? mb : ma;  // this lane's k-halves: sub-blocks 4h .. 4h + 3
             half8 mu;
 #pragma unroll
@@ -1071,8 +1070,7 @@ __global__ __launch_bounds__(512, 1) void k_mmqt(mi_mmx_group grp) {
 #pragma unroll
         for (int p = 0; p < 4; p++) q4[p] = *(const uint4 *) (wr + kQs + 32 * p + 16 * h);
         const uint32_t w0 = hdr.y, w2 = hdr.w;
-        const uint32_t sca = w0 & 0x3F3F3F3Fu;
-        const uint32_t scb = (w2 & 0x0F0F0F0Fu) | ((w0 >> 2) & 0x30303030u);
+        const uint32_t sca = qd_kq_scales4<0>(w0, w2), scb = qd_kq_scales4<1>(w0, w2);
         uint32_t lo[4], hi[4];
 #pragma unroll
         for (int kk = 0; kk < 8; kk++) {
@@ -1083,8 +1081,8 @@ __global__ __launch_bounds__(512, 1) void k_mmqt(mi_mmx_group grp) {
                 const uint32_t qv[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
-                    lo[e] = qv[e] & 0x0F0F0F0Fu;
-                    hi[e] = (qv[e] >> 4) & 0x0F0F0F0Fu;
+                    lo[e] = qd_nib_lo(qv[e]);
+                    hi[e] = qd_nib_hi(qv[e]);
                 }
             }
             const uint32_t scw = kk < 4 ? sca : scb;
@@ -1105,8 +1103,7 @@ __global__ __launch_bounds__(512, 1) void k_mmqt(mi_mmx_group grp) {
     auto combine = [&](const char * hdrp, const char * xup, const float * dal, int sb) {
         const uint4 hdr = *(const uint4 *) hdrp;
         const float dw = mi_h2f((uint16_t) (hdr.x & 0xFFFF)), dm = mi_h2f((uint16_t) (hdr.x >> 16));
-        const uint32_t ma = hdr.z & 0x3F3F3F3Fu;
-        const uint32_t mb = ((hdr.w >> 4) & 0x0F0F0F0Fu) | ((hdr.z >> 2) & 0x30303030u);
+        const uint32_t ma = qd_kq_mins4<0>(hdr.z, hdr.w), mb = qd_kq_mins4<1>(hdr.z, hdr.w);
         const uint32_t mw = h ? mb : ma;
         half8 mu;
 #pragma unroll
@@ -1304,7 +1301,7 @@ __global__ __launch_bounds__(256, 2) void k_mmq0p(mi_mmx_group grp) {
             for (int e = 0; e < 4; e++) {
                 const int ob = oq + 4 * e;
                 const uint32_t x = (ob & 3) == 0 ? o.v[ob >> 2] : __builtin_amdgcn_alignbyte(o.v[(ob >> 2) + 1], o.v[ob >> 2], ob & 3);
-                t[e] = (((x >> (4 * h)) & 0x0F0F0F0Fu) + 0x78787878u) ^ 0x80808080u;
+                t[e] = qd_q40_center(qd_nib_lo(x >> (4 * h)));
             }
             const int od = BS * j;
             const uint32_t x = (od & 3) == 0 ? o.v[od >> 2] : __builtin_amdgcn_alignbyte(o.v[(od >> 2) + 1], o.v[od >> 2], od & 3);
@@ -1491,8 +1488,8 @@ __global__ __launch_bounds__(64 * NWV, NR == 2 ? 2 : 1) void k_mmq0x(mi_mmx_grou
             uint32_t lo[4], hi[4];
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                lo[i] = ((t[i] & 0x0F0F0F0Fu) + 0x78787878u) ^ 0x80808080u;          // elements 4i..: q - 8
-                hi[i] = (((t[i] >> 4) & 0x0F0F0F0Fu) + 0x78787878u) ^ 0x80808080u;   // elements 16 + 4i..
+                lo[i] = qd_q40_center(qd_nib_lo(t[i]));  // elements 4i..: q - 8
+                hi[i] = qd_q40_center(qd_nib_hi(t[i]));  // elements 16 + 4i..
             }
             *(uint4 *) pl = make_uint4(lo[0], lo[1], lo[2], lo[3]);
             *(uint4 *) (pl + 16) = make_uint4(hi[0], hi[1], hi[2], hi[3]);

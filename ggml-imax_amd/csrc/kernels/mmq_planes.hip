@@ -37,6 +37,7 @@
 #include <mutex>
 
 #include "mmq_exact_common.h"
+#include "quant_decode.h"
 
 namespace {
 
@@ -47,7 +48,8 @@ struct PFmt {
     static constexpr int RB = PB + 1024 + 256;
 };
 
-// 6-bit scale and min of sub-block j from the 12 packed bytes (get_scale_min_k4, ggml-quants.c)
+// 6-bit scale and min of sub-block j from the 12 packed bytes: qd_kq_scale_min's integers (quant_decode.h)
+// read byte by byte. Through qd_kq_scale_min on three dwords k_planes_repack<Q5_K> fell from 8 waves to 3.
 __device__ __forceinline__ void scale_min_k4(int j, const uint8_t * q, int & sc, int & m) {
     if (j < 4) {
         sc = q[j] & 63;
@@ -72,9 +74,10 @@ __global__ __launch_bounds__(64) void k_planes_repack(const uint8_t * __restrict
     const int64_t rt = rt0 + (int64_t) blockIdx.y;
     const int64_t n = std::min<int64_t>(rt * 32 + r, N - 1);
     const uint8_t * blk = W + (size_t) n * nb01 + (size_t) s * BS;
-    const uint8_t * scales = blk + 4;
-    const uint8_t * qh = blk + 16;                   // Q5_K high bits
-    const uint8_t * qs = blk + (Q5 ? 48 : 16);
+    using L = kq_fmt<Q5>;
+    const uint8_t * scales = blk + L::SC;
+    const uint8_t * qh = blk + L::QH;                // Q5_K high bits
+    const uint8_t * qs = blk + L::QS;
     char * out = planes + ((size_t) rt * S + s) * P::RB;
     for (int kk = 0; kk < 8; kk++) {
         int sc, m;

@@ -9,25 +9,15 @@
 // ggml_vec_dot_q4_K_q8_K (src/ggml-quants.c:7007-7502); only the f32 combination order across
 // superblocks differs from the CPU.
 //
-// Reference per-type dot products mirrored here:
-//   Q4_0 x Q8_0  ggml_vec_dot_q4_0_q8_0  src/ggml-quants.c:3469-3874
-//   Q8_0 x Q8_0  ggml_vec_dot_q8_0_q8_0  src/ggml-quants.c:4819+
-//   Q4_1 x Q8_1  ggml_vec_dot_q4_1_q8_1  src/ggml-quants.c:4006-4039 (AVX2)
-//   Q5_0 x Q8_0  ggml_vec_dot_q5_0_q8_0  src/ggml-quants.c:4279-4301 (AVX2)
-//   Q5_1 x Q8_1  ggml_vec_dot_q5_1_q8_1  src/ggml-quants.c:4623-4648 (AVX2)
-//   Q4_K x Q8_K  ggml_vec_dot_q4_K_q8_K  src/ggml-quants.c:7007-7502
-//   Q5_K x Q8_K  ggml_vec_dot_q5_K_q8_K  src/ggml-quants.c:7833-8378
-//   Q6_K x Q8_K  ggml_vec_dot_q6_K_q8_K  src/ggml-quants.c:8730-9310
-//   Q2_K x Q8_K  ggml_vec_dot_q2_K_q8_K  src/ggml-quants.c:5105-5169
-//   Q3_K x Q8_K  ggml_vec_dot_q3_K_q8_K  src/ggml-quants.c:6001-6103
-//   IQ4_NL x Q8_0 ggml_vec_dot_iq4_nl_q8_0 src/ggml-quants.c:11733-11815
-//   IQ4_XS x Q8_K ggml_vec_dot_iq4_xs_q8_K src/ggml-quants.c:11873-11967
+// The formats' layouts, their integer decode and the list of the reference dot products mirrored
+// here are in quant_decode.h; the kernels below keep their loads and their f32 combination.
 // (F16 and F32 live in mmv_ordered.hip: bit-exact CPU summation order.)
 
 #include <string>
 
 #include "mi355x_common.h"
 #include "mi355x_kernels.h"
+#include "quant_decode.h"
 
 namespace {
 
@@ -142,7 +132,8 @@ __global__ __launch_bounds__(256) void k_mmv_kq(const uint8_t * __restrict__ W, 
     if (row >= g.N) return;
     mmv_item<NC, ID> bi;
     if (!bi.init(g)) return;
-    constexpr int BS = mi_type(Q5 ? MI_TYPE_Q5_K : MI_TYPE_Q4_K).bytes;
+    using L = kq_fmt<Q5>;
+    constexpr int BS = L::BS;
     const uint8_t * wrow = W + bi.wofs + row * g.nb01;
     const int nsb = (int) (g.K / 256);
 
@@ -155,32 +146,26 @@ __global__ __launch_bounds__(256) void k_mmv_kq(const uint8_t * __restrict__ W, 
         const int j = it & 3;
         const uint8_t * blk = wrow + (size_t) s * BS;
         const uint4 hdr = *(const uint4 *) blk;
-        const uint8_t * qp = blk + (Q5 ? 48 : 16) + 32 * j;
+        const uint8_t * qp = blk + L::QS + 32 * j;
         const uint4 qa = *(const uint4 *) qp;
         const uint4 qb = *(const uint4 *) (qp + 16);
         uint32_t q[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
         uint32_t qlo[8], qhi[8];
         if constexpr (Q5) {
-            const uint4 ha = *(const uint4 *) (blk + 16);
-            const uint4 hb = *(const uint4 *) (blk + 32);
+            const uint4 ha = *(const uint4 *) (blk + L::QH);
+            const uint4 hb = *(const uint4 *) (blk + L::QH + 16);
             const uint32_t h[8] = {ha.x, ha.y, ha.z, ha.w, hb.x, hb.y, hb.z, hb.w};
 #pragma unroll
-            for (int i = 0; i < 8; i++) {
-                qlo[i] = (q[i] & 0x0F0F0F0Fu) | (((h[i] >> (2 * j)) & 0x01010101u) << 4);
-                qhi[i] = ((q[i] >> 4) & 0x0F0F0F0Fu) | (((h[i] >> (2 * j + 1)) & 0x01010101u) << 4);
-            }
+            for (int i = 0; i < 8; i++) qd_kq_levels<true>(q[i], h[i], j, qlo[i], qhi[i]);
         } else {
 #pragma unroll
-            for (int i = 0; i < 8; i++) {
-                qlo[i] = q[i] & 0x0F0F0F0Fu;
-                qhi[i] = (q[i] >> 4) & 0x0F0F0F0Fu;
-            }
+            for (int i = 0; i < 8; i++) qd_kq_levels<false>(q[i], 0u, j, qlo[i], qhi[i]);
         }
         const float dw = mi_h2f((uint16_t) (hdr.x & 0xFFFF));
         const float dmw = mi_h2f((uint16_t) (hdr.x >> 16));
         int sc0, m0, sc1, m1;
-        mi_scale_min_k4(2 * j, hdr.y, hdr.z, hdr.w, sc0, m0);
-        mi_scale_min_k4(2 * j + 1, hdr.y, hdr.z, hdr.w, sc1, m1);
+        qd_kq_scale_min(2 * j, hdr.y, hdr.z, hdr.w, sc0, m0);
+        qd_kq_scale_min(2 * j + 1, hdr.y, hdr.z, hdr.w, sc1, m1);
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             if (NC > 1 && !bi.has(g, c)) break;
@@ -206,30 +191,7 @@ __global__ __launch_bounds__(256) void k_mmv_kq(const uint8_t * __restrict__ W, 
 }
 
 // ---------------------------------------------------------------- 32-element blocks x Q8_0 / Q8_1
-//
-// T is the weight's ggml_type: Q4_0 (18 B: fp16 d, qs[16]), Q8_0 (34 B: fp16 d, int8 qs[32]),
-// Q4_1 (20 B: fp16 d, m, qs[16]), Q5_0 (22 B: fp16 d, qh[4], qs[16]), Q5_1 (24 B: fp16 d, m,
-// qh[4], qs[16]); the facts below are its row of the table in mi355x_types.h. In the nibble
-// formats element j < 16 is the low nibble of qs[j], element j >= 16 the high nibble of
-// qs[j - 16]; bit j of the little-endian qh is the fifth bit of element j.
-// Values: Q4_0 (q - 8) d, Q5_0 (q - 16) d, Q4_1 / Q5_1 q d + m. Q4_1 / Q5_1 dot with Q8_1
-// activations, whose per-block s = fp16(d * sum(qs)) lies as fp16 bits in act.s32.
-// IQ4_NL (18 B: fp16 d, qs[16]) has Q4_0's geometry; its nibbles index the codebook kvalues_iq4nl
-// (LUT), value d kvalues[q], nothing subtracted.
-template <int T> struct q32_fmt {
-    static constexpr bool Q8 = T == MI_TYPE_Q8_0;
-    static constexpr bool HAS_M = mi_type(T).has_m;    // fp16 m after d, Q8_1 activations
-    static constexpr bool HAS_QH = mi_type(T).has_qh;  // fifth bits
-    static constexpr int BS = mi_type(T).bytes;
-    static constexpr int QH = HAS_M ? 4 : 2;          // offset of qh
-    static constexpr int QS = (HAS_M ? 4 : 2) + (HAS_QH ? 4 : 0);  // offset of the quants
-    static constexpr int SUB = mi_type(T).sub;  // subtracted from every level
-    static constexpr bool LUT = mi_type(T).lut;  // the nibbles index the IQ4 codebook
-};
-
-// four fifth bits (bits 0..3 of x) to bit 4 of four bytes: bit b of x * 0x00204081 lands at b, b + 7,
-// b + 14, b + 21 -- sixteen distinct positions, no carries -- of which 0, 8, 16, 24 are kept
-__device__ __forceinline__ uint32_t q5_spread(uint32_t x) { return (((x & 0xFu) * 0x00204081u) & 0x01010101u) << 4; }
+// (q32_fmt<T>, quant_decode.h: the format facts of the weight's ggml_type T)
 
 // 32 quants of a block starting at a 2-byte aligned address, gathered from aligned dwords.
 template <int NBYTES>
@@ -279,15 +241,15 @@ __global__ __launch_bounds__(256) void k_mmv_q0(const uint8_t * __restrict__ W, 
                 if constexpr (F::LUT) {
                     mi_iq4nl_levels8(t[i], wq[i], wq[i + 4]);
                 } else {
-                    wq[i] = (int) (t[i] & 0x0F0F0F0Fu);          // elements 4i..4i+3
-                    wq[i + 4] = (int) ((t[i] >> 4) & 0x0F0F0F0Fu);  // elements 16+4i..
+                    wq[i] = (int) qd_nib_lo(t[i]);      // elements 4i..4i+3
+                    wq[i + 4] = (int) qd_nib_hi(t[i]);  // elements 16+4i..
                 }
             }
             if constexpr (F::HAS_QH) {
                 uint32_t qh[1];
                 load_qs_unaligned<4>(blk + F::QH, qh);
 #pragma unroll
-                for (int i = 0; i < 8; i++) wq[i] |= (int) q5_spread(qh[0] >> (4 * i));
+                for (int i = 0; i < 8; i++) wq[i] |= (int) qd_spread4(qh[0] >> (4 * i));
             }
         }
         float mw = 0.0f;
@@ -364,7 +326,7 @@ __global__ __launch_bounds__(256) void k_mmv_q0_ord(const uint8_t * __restrict__
         const uintptr_t qa = blk + qoff;
         const uint32_t * qp = (const uint32_t *) (qa & ~(uintptr_t) 3);
         uint32_t q = __builtin_amdgcn_alignbyte(qp[1], qp[0], (uint32_t) (qa & 3));
-        if constexpr (!Q8) q = (l < 4 ? q : q >> 4) & 0x0F0F0F0Fu;
+        if constexpr (!Q8) q = qd_nib_lo(l < 4 ? q : q >> 4);
         if constexpr (F::LUT) q = (uint32_t) mi_iq4nl_levels(q);
         float mw = 0.0f;
         if constexpr (F::HAS_M) mw = mi_h2f((uint16_t) ((blk & 2) ? *(const uint32_t *) (blk + 2) & 0xFFFF : dw0 >> 16));
@@ -372,7 +334,7 @@ __global__ __launch_bounds__(256) void k_mmv_q0_ord(const uint8_t * __restrict__
             const uintptr_t ha = blk + F::QH;
             const uint32_t * hp = (const uint32_t *) (ha & ~(uintptr_t) 3);
             const uint32_t qh = (ha & 3) ? __builtin_amdgcn_alignbyte(hp[1], hp[0], (uint32_t) (ha & 3)) : hp[0];
-            q |= q5_spread(qh >> (4 * l));  // elements 4l..4l+3: bits 4l.. of qh
+            q |= qd_spread4(qh >> (4 * l));  // elements 4l..4l+3: bits 4l.. of qh
         }
 #pragma unroll
         for (int c = 0; c < NC; c++) {
@@ -417,7 +379,8 @@ __global__ __launch_bounds__(256) void k_mmv_kq_ord(const uint8_t * __restrict__
     const int64_t rc = live ? row : g.N - 1;  // (dead groups run a valid row: no early exit before the shuffles)
     mmv_item<NC, ID> bi;
     if (!bi.init(g)) return;
-    constexpr int BS = mi_type(Q5 ? MI_TYPE_Q5_K : MI_TYPE_Q4_K).bytes;
+    using L = kq_fmt<Q5>;
+    constexpr int BS = L::BS;
     const uint8_t * wrow = W + bi.wofs + rc * g.nb01;
     const int nsb = (int) (g.K / 256);
 
@@ -433,16 +396,16 @@ __global__ __launch_bounds__(256) void k_mmv_kq_ord(const uint8_t * __restrict__
         uint32_t qlo[4], qhi[4];
         int sc[8], mn[8];
 #pragma unroll
-        for (int j = 0; j < 8; j++) mi_scale_min_k4(j, hdr.y, hdr.z, hdr.w, sc[j], mn[j]);
-        const uint32_t hb = Q5 ? *(const uint32_t *) (blk + 16 + 4 * l) : 0u;  // qh bytes 4l..4l+3
+        for (int j = 0; j < 8; j++) qd_kq_scale_min(j, hdr.y, hdr.z, hdr.w, sc[j], mn[j]);
+        const uint32_t hb = Q5 ? *(const uint32_t *) (blk + L::QH + 4 * l) : 0u;  // qh bytes 4l..4l+3
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            const uint32_t q = *(const uint32_t *) (blk + (Q5 ? 48 : 16) + 32 * j + 4 * l);
-            qlo[j] = q & 0x0F0F0F0Fu;
-            qhi[j] = (q >> 4) & 0x0F0F0F0Fu;
+            const uint32_t q = *(const uint32_t *) (blk + L::QS + 32 * j + 4 * l);
+            qlo[j] = qd_nib_lo(q);  // (qd_kq_levels' integers, in this kernel's own statement order)
+            qhi[j] = qd_nib_hi(q);
             if constexpr (Q5) {
-                qlo[j] |= ((hb >> (2 * j)) & 0x01010101u) << 4;
-                qhi[j] |= ((hb >> (2 * j + 1)) & 0x01010101u) << 4;
+                qlo[j] |= qd_bit4(hb, 2 * j);
+                qhi[j] |= qd_bit4(hb, 2 * j + 1);
             }
         }
 #pragma unroll
@@ -492,18 +455,9 @@ __global__ __launch_bounds__(256) void k_mmv_kq_ord(const uint8_t * __restrict__
 
 // ---------------------------------------------------------------- Q6_K x Q8_K
 //
-// ggml_vec_dot_q6_K_q8_K (src/ggml-quants.c:8838-8915, the AVX2 branch). A 210-byte block is
-// ql[128] | qh[64] | int8 scales[16] | fp16 d; element e of the superblock is
-// d * scales[e / 16] * (q - 32) with q in 0..63. For the 128-half h, byte p (0..31):
-//   ql[64h + p]      low nibble -> element 128h + p,      high nibble -> element 128h + 64 + p
-//   ql[64h + 32 + p] low nibble -> element 128h + 32 + p, high nibble -> element 128h + 96 + p
-//   qh[32h + p]      bits 2t, 2t+1 -> bits 4, 5 of element 128h + 32t + p
-// Blocks are only 2-byte aligned (210 = 2 * 105; rows of an odd superblock count are 2 mod 4):
-// every load is an aligned dword (+ v_alignbyte) or narrower, never a uint4 on a block address.
-
-// bytes of q (each 0..63) -> bytes of q - 32 as int8, no carries between the bytes:
-// (q + 128 - 32) never borrows, the xor takes the 128 back out mod 256
-__device__ __forceinline__ int q6_center(uint32_t q) { return (int) (((q | 0x80808080u) - 0x20202020u) ^ 0x80808080u); }
+// The block's layout: q6k_fmt and qd_q6k_levels (quant_decode.h). Blocks are only 2-byte aligned
+// (210 = 2 * 105; rows of an odd superblock count are 2 mod 4): every load is an aligned dword
+// (+ v_alignbyte) or narrower, never a uint4 on a block address.
 
 // a dword at a 2-byte aligned address from the two aligned dwords covering it
 __device__ __forceinline__ uint32_t ld32_a2(const uint8_t * p) {
@@ -520,6 +474,7 @@ __device__ __forceinline__ uint32_t ld32_a2(const uint8_t * p) {
 // (up to 4 * 8,323,072, over 2^24) is accumulated in int32 and converted once.
 template <int NC, int ID = 0>
 __global__ __launch_bounds__(256) void k_mmv_q6k(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
+    using L = q6k_fmt;
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t) blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
     if (row >= g.N) return;
@@ -536,22 +491,17 @@ __global__ __launch_bounds__(256) void k_mmv_q6k(const uint8_t * __restrict__ W,
         const int s = it >> 2;
         const int h = (it >> 1) & 1;
         const int u = it & 1;
-        const uint8_t * blk = wrow + (size_t) s * mi_type(MI_TYPE_Q6_K).bytes;
+        const uint8_t * blk = wrow + (size_t) s * L::BS;
         uint32_t la[4], lb[4], hh[4];
-        load_qs_unaligned<16>(blk + 64 * h + 16 * u, la);
-        load_qs_unaligned<16>(blk + 64 * h + 32 + 16 * u, lb);
-        load_qs_unaligned<16>(blk + 128 + 32 * h + 16 * u, hh);
+        load_qs_unaligned<16>(blk + L::QL + 64 * h + 16 * u, la);
+        load_qs_unaligned<16>(blk + L::QL + 64 * h + 32 + 16 * u, lb);
+        load_qs_unaligned<16>(blk + L::QH + 32 * h + 16 * u, hh);
         int q[4][4];
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-            q[0][i] = q6_center((la[i] & 0x0F0F0F0Fu) | ((hh[i] & 0x03030303u) << 4));
-            q[1][i] = q6_center((lb[i] & 0x0F0F0F0Fu) | (((hh[i] >> 2) & 0x03030303u) << 4));
-            q[2][i] = q6_center(((la[i] >> 4) & 0x0F0F0F0Fu) | (((hh[i] >> 4) & 0x03030303u) << 4));
-            q[3][i] = q6_center(((lb[i] >> 4) & 0x0F0F0F0Fu) | (((hh[i] >> 6) & 0x03030303u) << 4));
-        }
-        const int8_t * scp = (const int8_t *) blk + 192 + 8 * h + u;
+        for (int i = 0; i < 4; i++) qd_q6k_levels<4>(la[i], lb[i], hh[i], &q[0][i]);
+        const int8_t * scp = (const int8_t *) blk + L::SC + 8 * h + u;
         const int sc[4] = {scp[0], scp[2], scp[4], scp[6]};
-        const float dw = mi_h2f(*(const uint16_t *) (blk + 208));
+        const float dw = mi_h2f(*(const uint16_t *) (blk + L::D));
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             if (NC > 1 && !bi.has(g, c)) break;
@@ -582,6 +532,7 @@ __global__ __launch_bounds__(256) void k_mmv_q6k(const uint8_t * __restrict__ W,
 // eight CPU lanes of one row (8 rows per wave), as k_mmv_kq_ord.
 template <int NC, int ID = 0>
 __global__ __launch_bounds__(256) void k_mmv_q6k_ord(const uint8_t * __restrict__ W, mi_act_q8 act, float * __restrict__ dst, mmv_geom g) {
+    using L = q6k_fmt;
     const int l = threadIdx.x & 7;
     const int64_t row = (int64_t) blockIdx.x * 32 + (threadIdx.x >> 3);
     const bool live = row < g.N;
@@ -597,21 +548,18 @@ __global__ __launch_bounds__(256) void k_mmv_q6k_ord(const uint8_t * __restrict_
     for (int c = 0; c < NC; c++) A[c] = 0.0f;
 
     for (int s = 0; s < nsb; s++) {
-        const uint8_t * blk = wrow + (size_t) s * mi_type(MI_TYPE_Q6_K).bytes;
-        const float dw = mi_h2f(*(const uint16_t *) (blk + 208));
+        const uint8_t * blk = wrow + (size_t) s * L::BS;
+        const float dw = mi_h2f(*(const uint16_t *) (blk + L::D));
         int q[8], sc[8];
 #pragma unroll
         for (int h = 0; h < 2; h++) {
-            const uint32_t la = ld32_a2(blk + 64 * h + 4 * l);
-            const uint32_t lb = ld32_a2(blk + 64 * h + 32 + 4 * l);
-            const uint32_t hh = ld32_a2(blk + 128 + 32 * h + 4 * l);
-            q[4 * h + 0] = q6_center((la & 0x0F0F0F0Fu) | ((hh & 0x03030303u) << 4));
-            q[4 * h + 1] = q6_center((lb & 0x0F0F0F0Fu) | (((hh >> 2) & 0x03030303u) << 4));
-            q[4 * h + 2] = q6_center(((la >> 4) & 0x0F0F0F0Fu) | (((hh >> 4) & 0x03030303u) << 4));
-            q[4 * h + 3] = q6_center(((lb >> 4) & 0x0F0F0F0Fu) | (((hh >> 6) & 0x03030303u) << 4));
+            const uint32_t la = ld32_a2(blk + L::QL + 64 * h + 4 * l);
+            const uint32_t lb = ld32_a2(blk + L::QL + 64 * h + 32 + 4 * l);
+            const uint32_t hh = ld32_a2(blk + L::QH + 32 * h + 4 * l);
+            qd_q6k_levels(la, lb, hh, &q[4 * h]);
         }
 #pragma unroll
-        for (int j = 0; j < 8; j++) sc[j] = ((const int8_t *) blk)[192 + 2 * j + hi];
+        for (int j = 0; j < 8; j++) sc[j] = ((const int8_t *) blk)[L::SC + 2 * j + hi];
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             if (NC > 1 && !bi.has(g, c)) break;
@@ -635,38 +583,9 @@ __global__ __launch_bounds__(256) void k_mmv_q6k_ord(const uint8_t * __restrict_
 
 // ---------------------------------------------------------------- Q2_K / Q3_K x Q8_K
 //
-// ggml_vec_dot_q2_K_q8_K (src/ggml-quants.c:5105-5169) and ggml_vec_dot_q3_K_q8_K (:6001-6103), the
-// AVX2 branches. Q2_K (84 B): scales[16] | qs[64] | fp16 d | fp16 dmin, element d (sc & 0xF) q -
-// dmin (sc >> 4) with q in 0..3. Q3_K (110 B): hmask[32] | qs[64] | scales[12] | fp16 d, element
-// d (sc - 32) (q - (hbit ? 0 : 4)) with the 6-bit sc as q3k_scale unpacks it. Both pack the quants
-// alike: byte qs[32h + b] holds at bit 2t element 128h + 32t + b (h = 0..1, t = 0..3, b = 0..31);
-// bit 4h + t of hmask[b] is that element's high bit. Q2_K blocks are 4-byte aligned, Q3_K blocks
-// 2-byte aligned (rows of an odd superblock count are 2 mod 4): aligned dwords (+ v_alignbyte) or
-// narrower loads only, as Q6_K.
-template <int T> struct q23k_fmt {
-    static constexpr bool Q3 = T == MI_TYPE_Q3_K;
-    static constexpr int BS = mi_type(T).bytes;
-    static constexpr int QS = Q3 ? 32 : 16;   // offset of qs
-    static constexpr int SC = Q3 ? 96 : 0;    // offset of scales
-    static constexpr int D = Q3 ? 108 : 80;   // offset of d (Q2_K: dmin follows)
-};
-
-// sub-block t's quants of a dword of qs (and, Q3_K, of the hmask dword of the same bytes, high bit
-// 4h + t) as int8x4: Q2_K q in 0..3; Q3_K (q | hbit << 2) - 4 = q - (hbit ? 0 : 4), no carries
-// between the bytes ((v + 128 - 4) never borrows, the xor takes the 128 back out)
-template <bool Q3>
-__device__ __forceinline__ int q23k_quants(uint32_t qs, uint32_t hm, int h, int t) {
-    const uint32_t q = (qs >> (2 * t)) & 0x03030303u;
-    if constexpr (!Q3) return (int) q;
-    else return (int) (((q | (((hm >> (4 * h + t)) & 0x01010101u) << 2) | 0x80808080u) - 0x04040404u) ^ 0x80808080u);
-}
-
-// Q3_K: sub-block j's scale minus 32 -- low four bits in the nibbles of scales[0..7], upper two in
-// scales[8 + j % 4] at bit 2 (j / 4) (the kmask1 / kmask2 unpack of the reference)
-__device__ __forceinline__ int q3k_scale(const uint8_t * scales, int j) {
-    const int lo = (scales[j & 7] >> (4 * (j >> 3))) & 0xF;
-    return (lo | (((scales[8 + (j & 3)] >> (2 * (j >> 2))) & 3) << 4)) - 32;
-}
+// The blocks' layouts: q23k_fmt, qd_q23k_levels and qd_q3k_scale (quant_decode.h). Q2_K blocks are
+// 4-byte aligned, Q3_K blocks 2-byte aligned (rows of an odd superblock count are 2 mod 4): aligned
+// dwords (+ v_alignbyte) or narrower loads only, as Q6_K.
 
 // Tree order: Q6_K's item (superblock s, 128-half h, 16-byte range u), item = 4s + 2h + u. It
 // reads qs[32h + 16u ..+15] (and hmask[16u ..+15]): the four 16-element sub-blocks at elements
@@ -700,9 +619,9 @@ __global__ __launch_bounds__(256) void k_mmv_q23k(const uint8_t * __restrict__ W
 #pragma unroll
         for (int t = 0; t < 4; t++) {
 #pragma unroll
-            for (int i = 0; i < 4; i++) q[t][i] = q23k_quants<F::Q3>(qs[i], hm[i], h, t);
+            for (int i = 0; i < 4; i++) q[t][i] = qd_q23k_levels<F::Q3>(qs[i], hm[i], h, t);
             if constexpr (F::Q3) {
-                sc[t] = q3k_scale(blk + F::SC, 8 * h + 2 * t + u);
+                sc[t] = qd_q3k_scale(blk + F::SC, 8 * h + 2 * t + u);
                 mn[t] = 0;
             } else {
                 const int b = blk[8 * h + 2 * t + u];
@@ -777,10 +696,10 @@ __global__ __launch_bounds__(256) void k_mmv_q23k_ord(const uint8_t * __restrict
         for (int h = 0; h < 2; h++) {
             const uint32_t qs = ld32_a2(blk + F::QS + 32 * h + 4 * l);
 #pragma unroll
-            for (int t = 0; t < 4; t++) q[4 * h + t] = q23k_quants<F::Q3>(qs, hm, h, t);
+            for (int t = 0; t < 4; t++) q[4 * h + t] = qd_q23k_levels<F::Q3>(qs, hm, h, t);
         }
 #pragma unroll
-        for (int j = 0; j < 8; j++) sc[j] = F::Q3 ? q3k_scale(blk + F::SC, 2 * j + hi) : (blk[2 * j + hi] & 0xF);
+        for (int j = 0; j < 8; j++) sc[j] = F::Q3 ? qd_q3k_scale(blk + F::SC, 2 * j + hi) : (blk[2 * j + hi] & 0xF);
         int m0 = 0, m1 = 0;
         if constexpr (!F::Q3) {
             m0 = blk[2 * l] >> 4;
@@ -816,14 +735,7 @@ __global__ __launch_bounds__(256) void k_mmv_q23k_ord(const uint8_t * __restrict
 
 // ---------------------------------------------------------------- IQ4_XS x Q8_K
 //
-// ggml_vec_dot_iq4_xs_q8_K (src/ggml-quants.c:11873-11967). IQ4_XS (136 B): fp16 d | u16 scales_h |
-// scales_l[4] | qs[128]; sub-block ib (32 elements, quants qs[16 ib ..], element j < 16 the low
-// nibble of byte j, element 16 + j its high nibble) has the 6-bit scale ls = (nibble ib of scales_l)
-// | (bits 2 ib .. of scales_h) << 4 and the value d (ls - 32) kvalues_iq4nl[q]. Blocks are whole
-// dwords (136 = 4 * 34) of rows that start on one.
-__device__ __forceinline__ int iq4xs_scale(uint32_t sl, uint32_t sh, int ib) {
-    return (int) (((sl >> (4 * ib)) & 0xF) | (((sh >> (2 * ib)) & 3) << 4)) - 32;
-}
+// The block's layout and qd_iq4xs_scale: quant_decode.h.
 
 // Tree order: item (superblock s, quarter u) = 4 s + u: the sub-blocks 2u and 2u + 1, 32 bytes of
 // quants, looked up once and used for every column. A sub-block's sum is below 32 * 127 * 127 * 32 <
@@ -848,7 +760,7 @@ __global__ __launch_bounds__(256) void k_mmv_iq4xs(const uint8_t * __restrict__ 
         const uint32_t * blk = (const uint32_t *) (wrow + (size_t) s * BS);
         const uint32_t h0 = blk[0], sl = blk[1];
         const float dw = mi_h2f((uint16_t) (h0 & 0xFFFF));
-        const int ls0 = iq4xs_scale(sl, h0 >> 16, 2 * u), ls1 = iq4xs_scale(sl, h0 >> 16, 2 * u + 1);
+        const int ls0 = qd_iq4xs_scale(sl, h0 >> 16, 2 * u), ls1 = qd_iq4xs_scale(sl, h0 >> 16, 2 * u + 1);
         int lv[16];  // [0..7] sub-block 2u (elements 4i.. in lv[i]), [8..15] sub-block 2u + 1
 #pragma unroll
         for (int i = 0; i < 4; i++) {
@@ -905,8 +817,8 @@ __global__ __launch_bounds__(256) void k_mmv_iq4xs_ord(const uint8_t * __restric
 #pragma unroll
         for (int ib = 0; ib < 8; ib++) {
             const uint32_t q = blk[2 + 4 * ib + (l & 3)];
-            lv[ib] = mi_iq4nl_levels((l < 4 ? q : q >> 4) & 0x0F0F0F0Fu);
-            sc[ib] = iq4xs_scale(sl, h0 >> 16, ib);
+            lv[ib] = mi_iq4nl_levels(qd_nib_lo(l < 4 ? q : q >> 4));
+            sc[ib] = qd_iq4xs_scale(sl, h0 >> 16, ib);
         }
 #pragma unroll
         for (int c = 0; c < NC; c++) {

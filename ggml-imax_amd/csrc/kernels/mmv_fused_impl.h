@@ -10,6 +10,7 @@
 
 #include "mi355x_common.h"
 #include "mi355x_kernels.h"
+#include "quant_decode.h"
 
 // the norm prologue replays the CPU's rounding (cpu_order.h turns FMA contraction off); the rest
 // of this file keeps the default contraction
@@ -239,14 +240,14 @@ struct FmtKQ {
             const uint32_t h[8] = {r.ha.x, r.ha.y, r.ha.z, r.ha.w, r.hb.x, r.hb.y, r.hb.z, r.hb.w};
 #pragma unroll
             for (int i = 0; i < 8; i++) {
-                qlo[i] = (q[i] & 0x0F0F0F0Fu) | (((h[i] >> (2 * j)) & 0x01010101u) << 4);
-                qhi[i] = ((q[i] >> 4) & 0x0F0F0F0Fu) | (((h[i] >> (2 * j + 1)) & 0x01010101u) << 4);
+                qlo[i] = qd_nib_lo(q[i]) | qd_bit4(h[i], 2 * j);
+                qhi[i] = qd_nib_hi(q[i]) | qd_bit4(h[i], 2 * j + 1);
             }
         } else {
 #pragma unroll
             for (int i = 0; i < 8; i++) {
-                qlo[i] = q[i] & 0x0F0F0F0Fu;
-                qhi[i] = (q[i] >> 4) & 0x0F0F0F0Fu;
+                qlo[i] = qd_nib_lo(q[i]);
+                qhi[i] = qd_nib_hi(q[i]);
             }
         }
         const float dw = mi_h2f((uint16_t) (r.hdr.x & 0xFFFF));
@@ -298,14 +299,14 @@ struct FmtKQ {
             const uint32_t h[8] = {r.ha.x, r.ha.y, r.ha.z, r.ha.w, r.hb.x, r.hb.y, r.hb.z, r.hb.w};
 #pragma unroll
             for (int i = 0; i < 8; i++) {
-                qlo[i] = (q[i] & 0x0F0F0F0Fu) | (((h[i] >> (2 * j)) & 0x01010101u) << 4);
-                qhi[i] = ((q[i] >> 4) & 0x0F0F0F0Fu) | (((h[i] >> (2 * j + 1)) & 0x01010101u) << 4);
+                qlo[i] = qd_nib_lo(q[i]) | qd_bit4(h[i], 2 * j);
+                qhi[i] = qd_nib_hi(q[i]) | qd_bit4(h[i], 2 * j + 1);
             }
         } else {
 #pragma unroll
             for (int i = 0; i < 8; i++) {
-                qlo[i] = q[i] & 0x0F0F0F0Fu;
-                qhi[i] = (q[i] >> 4) & 0x0F0F0F0Fu;
+                qlo[i] = qd_nib_lo(q[i]);
+                qhi[i] = qd_nib_hi(q[i]);
             }
         }
         const float dw = mi_h2f((uint16_t) (r.hdr.x & 0xFFFF));
@@ -452,8 +453,8 @@ struct FmtQ0 {
         } else {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                sumi = mi_dot4((int) (t[i] & 0x0F0F0F0Fu), av[i], sumi);
-                sumi = mi_dot4((int) ((t[i] >> 4) & 0x0F0F0F0Fu), av[i + 4], sumi);
+                sumi = mi_dot4((int) qd_nib_lo(t[i]), av[i], sumi);
+                sumi = mi_dot4((int) qd_nib_hi(t[i]), av[i + 4], sumi);
             }
             sumi -= 8 * s32;  // (q - 8) * y
         }
@@ -510,7 +511,7 @@ struct FmtQ0 {
                 if constexpr (Q8 || LUT) {
                     q = mi_dot4((int) t[l], av[l], 0);
                 } else {
-                    const uint32_t nib = l < 4 ? (t[l] & 0x0F0F0F0Fu) : ((t[l - 4] >> 4) & 0x0F0F0F0Fu);
+                    const uint32_t nib = l < 4 ? qd_nib_lo(t[l]) : qd_nib_hi(t[l - 4]);
                     q = mi_dot4((int) nib, av[l], mi_dot4((int) 0xF8F8F8F8u, av[l], 0));  // (q - 8) . y
                 }
                 e[l * S] = __float_as_uint((float) q);  // exact; _mm256_cvtepi32_ps
@@ -617,13 +618,11 @@ struct FmtQ1 {
         }
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            b.lo[i] = qs[i] & 0x0F0F0F0Fu;
-            b.hi[i] = (qs[i] >> 4) & 0x0F0F0F0Fu;
+            b.lo[i] = qd_nib_lo(qs[i]);
+            b.hi[i] = qd_nib_hi(qs[i]);
             if constexpr (HAS_QH) {
-                // four fifth bits to bit 4 of four bytes: bit k of x * 0x00204081 lands at k, k + 7,
-                // k + 14, k + 21 (distinct, no carries); bits 0, 8, 16, 24 are kept
-                b.lo[i] |= ((((qh >> (4 * i)) & 0xFu) * 0x00204081u) & 0x01010101u) << 4;
-                b.hi[i] |= ((((qh >> (16 + 4 * i)) & 0xFu) * 0x00204081u) & 0x01010101u) << 4;
+                b.lo[i] |= qd_spread4(qh >> (4 * i));
+                b.hi[i] |= qd_spread4(qh >> (16 + 4 * i));
             }
         }
     }
@@ -751,10 +750,10 @@ __device__ __forceinline__ float q0pair_dot(const uint32_t (&t0)[4], const uint3
     int s0 = 0, s1 = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-        s0 = mi_dot4((int) (t0[i] & 0x0F0F0F0Fu), av0[i], s0);
-        s0 = mi_dot4((int) ((t0[i] >> 4) & 0x0F0F0F0Fu), av0[i + 4], s0);
-        s1 = mi_dot4((int) (t1[i] & 0x0F0F0F0Fu), av1[i], s1);
-        s1 = mi_dot4((int) ((t1[i] >> 4) & 0x0F0F0F0Fu), av1[i + 4], s1);
+        s0 = mi_dot4((int) qd_nib_lo(t0[i]), av0[i], s0);
+        s0 = mi_dot4((int) qd_nib_hi(t0[i]), av0[i + 4], s0);
+        s1 = mi_dot4((int) qd_nib_lo(t1[i]), av1[i], s1);
+        s1 = mi_dot4((int) qd_nib_hi(t1[i]), av1[i + 4], s1);
     }
     s0 -= 8 * (int) (int16_t) (ss & 0xFFFF);
     s1 -= 8 * (int) (int16_t) (ss >> 16);
@@ -908,8 +907,8 @@ struct FmtQ8R {
     __device__ static __forceinline__ float dot_act(const Regs & r, int, const Act & v, float acc) { return bdot(r, v.av, v.da, acc); }
 };
 
-// Q6_K (210 B superblocks: ql[128] | qh[64] | int8 scales[16] | fp16 d; element e is
-// d * scales[e / 16] * (q - 32)). An item is (superblock s, 128-half h, 16-byte range u), item =
+// Q6_K (the block's layout and qd_q6k_levels: quant_decode.h).
+// An item is (superblock s, 128-half h, 16-byte range u), item =
 // 4 s + 2 h + u: ql[64h + 16u ..], ql[64h + 32 + 16u ..] and qh[32h + 16u ..] hold the four
 // 16-element sub-blocks at elements 128h + 32t + 16u (t = 0..3; t & 1 picks the ql range, t & 2 its
 // high nibbles, qh bits 2t..2t+1 the upper two bits), whose scales are scales[8h + 2t + u]. Four
@@ -923,7 +922,8 @@ struct FmtQ6K {
     static constexpr bool KL = false;
     static constexpr int QKA = 256;
     static constexpr int ITEM = 64;
-    static constexpr int BS = mi_type(MI_TYPE_Q6_K).bytes;
+    using L = q6k_fmt;
+    static constexpr int BS = L::BS;
     struct Regs {
         uint32_t la[5], lb[5], hh[5];  // the dwords covering the two ql ranges and the qh range
         uint32_t sc[3];                // ... the eight scales of the 128-half
@@ -935,7 +935,7 @@ struct FmtQ6K {
         const uint32_t blk = s * BS;
         r.off = ((uint32_t) (uintptr_t) row + blk) & 2;
         const uint8_t * p = row + (int) (blk - r.off);  // 4-byte aligned (item 0 of a misaligned row: its first dword starts in the row before)
-        const uint32_t qa = 64 * h + 16 * u, qh = 128 + 32 * h + 16 * u, sc = 192 + 8 * h;
+        const uint32_t qa = L::QL + 64 * h + 16 * u, qh = L::QH + 32 * h + 16 * u, sc = L::SC + 8 * h;
 #pragma unroll
         for (int i = 0; i < 5; i++) {
             r.la[i] = *(const uint32_t *) (p + qa + 4 * i);
@@ -945,7 +945,7 @@ struct FmtQ6K {
         r.sc[0] = *(const uint32_t *) (p + sc);
         r.sc[1] = *(const uint32_t *) (p + sc + 4);
         r.sc[2] = *(const uint32_t *) (p + sc + (r.off ? 8 : 4));  // (aligned blocks: not needed, no read past d)
-        r.dd = *(const uint32_t *) (p + 208);
+        r.dd = *(const uint32_t *) (p + L::D);
     }
     // the item's operands: (q - 32) of sub-block t as four int8x4 dwords, its scale, the block's d
     struct Dec {
@@ -953,8 +953,6 @@ struct FmtQ6K {
         int sc[4];
         float dw;
     };
-    // bytes of q (each 0..63) -> bytes of q - 32 as int8, no carries between the bytes
-    __device__ static __forceinline__ int center(uint32_t q) { return (int) (((q | 0x80808080u) - 0x20202020u) ^ 0x80808080u); }
     __device__ static __forceinline__ void decode(Dec & d, const Regs & r, int item) {
         const int u = item & 1;
 #pragma unroll
@@ -962,10 +960,7 @@ struct FmtQ6K {
             const uint32_t la = __builtin_amdgcn_alignbyte(r.la[i + 1], r.la[i], r.off);
             const uint32_t lb = __builtin_amdgcn_alignbyte(r.lb[i + 1], r.lb[i], r.off);
             const uint32_t hh = __builtin_amdgcn_alignbyte(r.hh[i + 1], r.hh[i], r.off);
-            d.q[0][i] = center((la & 0x0F0F0F0Fu) | ((hh & 0x03030303u) << 4));
-            d.q[1][i] = center((lb & 0x0F0F0F0Fu) | (((hh >> 2) & 0x03030303u) << 4));
-            d.q[2][i] = center(((la >> 4) & 0x0F0F0F0Fu) | (((hh >> 4) & 0x03030303u) << 4));
-            d.q[3][i] = center(((lb >> 4) & 0x0F0F0F0Fu) | (((hh >> 6) & 0x03030303u) << 4));
+            qd_q6k_levels<4>(la, lb, hh, &d.q[0][i]);
         }
         const uint32_t s0 = __builtin_amdgcn_alignbyte(r.sc[1], r.sc[0], r.off) >> (8 * u);
         const uint32_t s1 = __builtin_amdgcn_alignbyte(r.sc[2], r.sc[1], r.off) >> (8 * u);
@@ -1155,9 +1150,8 @@ struct FmtQ23K {
                 const uint32_t hb = (__builtin_amdgcn_alignbyte(r.hm[i + 1], r.hm[i], off) >> (4 * h)) << 2;  // high bit of sub-block t at bit 2 + t
 #pragma unroll
                 for (int t = 0; t < 4; t++) {
-                    const uint32_t v = ((qs >> (2 * t)) & 0x03030303u) | ((hb >> t) & 0x04040404u);
-                    // v - 4 per byte, no carries: (v + 128 - 4) never borrows, the xor takes the 128 back out
-                    d.q[t][i] = CENTER ? (int) (((v | 0x80808080u) - 0x04040404u) ^ 0x80808080u) : (int) v;
+                    const uint32_t v = qd_q2(qs, t) | ((hb >> t) & 0x04040404u);
+                    d.q[t][i] = CENTER ? (int) qd_sub_bytes<4>(v) : (int) v;
                 }
             }
             // scales j = 8h + 2t + u: low nibbles in byte 2t + u of aux[0..1] (nibble h), upper two bits in
@@ -1177,7 +1171,7 @@ struct FmtQ23K {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
 #pragma unroll
-                for (int t = 0; t < 4; t++) d.q[t][i] = (int) ((r.qs[i] >> (2 * t)) & 0x03030303u);
+                for (int t = 0; t < 4; t++) d.q[t][i] = (int) qd_q2(r.qs[i], t);
             }
             const uint32_t x0 = r.sc[0] >> (8 * u), x1 = r.sc[1] >> (8 * u);
             d.sc[0] = (int) (x0 & 0xF);         d.mn[0] = (int) ((x0 >> 4) & 0xF);

@@ -18,6 +18,7 @@
 
 #include "mi355x_common.h"
 #include "mi355x_kernels.h"
+#include "quant_decode.h"
 
 #include "cpu_order.h"
 
@@ -190,7 +191,7 @@ __device__ __forceinline__ float dequant_elem(const uint8_t * row, int64_t c) {
         // q * d + m resp. (q - 16) * d. The product of a 5-bit level and an fp16 scale is exact in f32,
         // so the reference build's contraction of q * d + m changes nothing. Q5_0 blocks are only
         // 2-byte aligned: bytes and 2-byte copies only.
-        constexpr int QH = I.has_m ? 4 : 2, QS = I.has_qh ? QH + 4 : QH;
+        constexpr int QH = q32_fmt<TYPE>::QH, QS = q32_fmt<TYPE>::QS;
         const uint8_t * blk = row + (c >> 5) * BS;
         const int j = (int) (c & 31);
         uint16_t dh;
@@ -209,10 +210,10 @@ __device__ __forceinline__ float dequant_elem(const uint8_t * row, int64_t c) {
         const uint8_t * blk = row + (c >> 8) * BS;
         const int e = (int) (c & 255), h = e >> 7, t = (e >> 5) & 3, p = e & 31;
         uint16_t dh;
-        __builtin_memcpy(&dh, blk + 208, 2);
-        const uint8_t lq = blk[64 * h + 32 * (t & 1) + p];
-        const int q = (int) (((t & 2) ? (lq >> 4) : (lq & 0x0F)) | (((blk[128 + 32 * h + p] >> (2 * t)) & 3) << 4)) - 32;
-        const int sc = (int8_t) blk[192 + (e >> 4)];
+        __builtin_memcpy(&dh, blk + q6k_fmt::D, 2);
+        const uint8_t lq = blk[q6k_fmt::QL + 64 * h + 32 * (t & 1) + p];
+        const int q = (int) (((t & 2) ? (lq >> 4) : (lq & 0x0F)) | (((blk[q6k_fmt::QH + 32 * h + p] >> (2 * t)) & 3) << 4)) - 32;
+        const int sc = (int8_t) blk[q6k_fmt::SC + (e >> 4)];
         return mul_rn(mul_rn(mi_h2f(dh), (float) sc), (float) q);
     } else if constexpr (TYPE == MI_TYPE_Q2_K) {  // Q2_K (84 B) superblocks: scales[16] qs[64] fp16 d, dmin
         // dequantize_row_q2_K (:1446-1490): dl * q - ml with dl = d * (sc & 0xF), ml = dmin * (sc >> 4).
@@ -223,10 +224,10 @@ __device__ __forceinline__ float dequant_elem(const uint8_t * row, int64_t c) {
         const uint8_t * blk = row + (c >> 8) * BS;
         const int e = (int) (c & 255), h = e >> 7, t = (e >> 5) & 3, p = e & 31;
         uint16_t dh, mh;
-        __builtin_memcpy(&dh, blk + 80, 2);
-        __builtin_memcpy(&mh, blk + 82, 2);
+        __builtin_memcpy(&dh, blk + q23k_fmt<TYPE>::D, 2);
+        __builtin_memcpy(&mh, blk + q23k_fmt<TYPE>::D + 2, 2);
         const int sc = blk[e >> 4];
-        const int q = (blk[16 + 32 * h + p] >> (2 * t)) & 3;
+        const int q = (blk[q23k_fmt<TYPE>::QS + 32 * h + p] >> (2 * t)) & 3;
         const float dl = mul_rn(mi_h2f(dh), (float) (sc & 0xF)), ml = mul_rn(mi_h2f(mh), (float) (sc >> 4));
         return sub_rn(mul_rn(dl, (float) q), ml);
     } else if constexpr (TYPE == MI_TYPE_Q3_K) {  // Q3_K (110 B) superblocks: hmask[32] qs[64] scales[12] fp16 d
@@ -235,11 +236,11 @@ __device__ __forceinline__ float dequant_elem(const uint8_t * row, int64_t c) {
         const uint8_t * blk = row + (c >> 8) * BS;
         const int e = (int) (c & 255), h = e >> 7, t = (e >> 5) & 3, p = e & 31, j = e >> 4;
         uint16_t dh;
-        __builtin_memcpy(&dh, blk + 108, 2);
-        const uint8_t * scales = blk + 96;
-        const int lo = j < 8 ? scales[j] & 0xF : scales[j - 8] >> 4;
+        __builtin_memcpy(&dh, blk + q23k_fmt<TYPE>::D, 2);
+        const uint8_t * scales = blk + q23k_fmt<TYPE>::SC;
+        const int lo = j < 8 ? scales[j] & 0xF : scales[j - 8] >> 4;  // (qd_q3k_scale's integers; that form costs this kernel occupancy)
         const int sc = (lo | (((scales[8 + (j & 3)] >> (2 * (j >> 2))) & 3) << 4)) - 32;
-        const int q = ((blk[32 + 32 * h + p] >> (2 * t)) & 3) - (((blk[p] >> (4 * h + t)) & 1) ? 0 : 4);
+        const int q = ((blk[q23k_fmt<TYPE>::QS + 32 * h + p] >> (2 * t)) & 3) - (((blk[p] >> (4 * h + t)) & 1) ? 0 : 4);
         return mul_rn(mul_rn(mi_h2f(dh), (float) sc), (float) q);
     } else {  // Q4_K (144 B) / Q5_K (176 B) superblocks of 256
         constexpr bool Q5 = TYPE == MI_TYPE_Q5_K;
@@ -249,13 +250,13 @@ __device__ __forceinline__ float dequant_elem(const uint8_t * row, int64_t c) {
         __builtin_memcpy(&dh, blk, 2);
         __builtin_memcpy(&mh, blk + 2, 2);
         uint32_t sc3[3];
-        __builtin_memcpy(sc3, blk + 4, 12);
+        __builtin_memcpy(sc3, blk + kq_fmt<Q5>::SC, 12);
         int sc, m;
-        mi_scale_min_k4(2 * g + hi, sc3[0], sc3[1], sc3[2], sc, m);
+        qd_kq_scale_min(2 * g + hi, sc3[0], sc3[1], sc3[2], sc, m);
         const float d1 = mul_rn(mi_h2f(dh), (float) sc), m1 = mul_rn(mi_h2f(mh), (float) m);
-        const uint8_t * qs = blk + (Q5 ? 48 : 16) + 32 * g;
+        const uint8_t * qs = blk + kq_fmt<Q5>::QS + 32 * g;
         int q = hi ? (qs[l] >> 4) : (qs[l] & 0x0F);
-        if constexpr (Q5) q += (blk[16 + l] >> (2 * g + hi)) & 1 ? 16 : 0;
+        if constexpr (Q5) q += (blk[kq_fmt<Q5>::QH + l] >> (2 * g + hi)) & 1 ? 16 : 0;
         return __fmaf_rn(d1, (float) q, -m1);
     }
 }

@@ -83,6 +83,12 @@ def test_mul_mat_tree_order(rt, backend, wt, K, N):
 
 @needs_ref
 @by_type
+def test_streaming_gemv_route(rt, backend, wt):
+    W.check_streaming_gemv_route(rt, backend, wt)
+
+
+@needs_ref
+@by_type
 def test_mul_mat_llama_ffn_down_rows(rt, backend, ref, wt):
     W.check_mul_mat_llama_ffn_down_rows(rt, backend, ref, wt)
 
@@ -92,6 +98,13 @@ def test_mul_mat_llama_ffn_down_rows(rt, backend, ref, wt):
 @by_type
 def test_weight_batch_and_strided_src1(rt, backend, ref, wt, ne11):
     W.check_weight_batch_and_strided_src1(rt, backend, ref, wt, ne11)
+
+
+@needs_ref
+@by_type
+@pytest.mark.parametrize("ne11", [1, 3, 9])
+def test_generic_gemv_route(rt, backend, ref, wt, ne11):
+    W.check_generic_gemv_route(rt, backend, ref, wt, ne11)
 
 
 @needs_ref

@@ -41,6 +41,11 @@ def test_mul_mat_tree_order(rt, backend, K, N):
 
 
 @needs_ref
+def test_streaming_gemv_route(rt, backend):
+    W.check_streaming_gemv_route(rt, backend, WT)
+
+
+@needs_ref
 def test_mul_mat_llama_ffn_down_rows(rt, backend, ref):
     W.check_mul_mat_llama_ffn_down_rows(rt, backend, ref, WT)
 
@@ -49,6 +54,12 @@ def test_mul_mat_llama_ffn_down_rows(rt, backend, ref):
 @pytest.mark.parametrize("ne11", [1, 3, 9])
 def test_weight_batch_and_strided_src1(rt, backend, ref, ne11):
     W.check_weight_batch_and_strided_src1(rt, backend, ref, WT, ne11)
+
+
+@needs_ref
+@pytest.mark.parametrize("ne11", [1, 3, 9])
+def test_generic_gemv_route(rt, backend, ref, ne11):
+    W.check_generic_gemv_route(rt, backend, ref, WT, ne11)
 
 
 @needs_ref

@@ -575,6 +575,23 @@ def check_mul_mat_tree_order(rt, backend, wt, shape):
         assert err <= TREE_TOL, (B, err)
 
 
+def check_streaming_gemv_route(rt, backend, wt):
+    """One column at the type's K = 4096 shape (one item per lane, or two) in both orders: the streaming
+    GEMV's instance of the type, the route asserted; the reference output is the one the sweeps above share."""
+    T, (K, N) = wt.type, next(s for s in wt.shapes if s[0] == 4096)
+    wq = weights(T, K, N, 100 + K + N)
+    x = synth.uniform(200 + K + 1, K)
+    yr = _ref_mul_mat(T, K, N, 1)
+    for order in (1, 0):
+        y = in_order(rt, order, lambda: G.mul_mat_once(rt, backend, T, wq, K, N, x, 1))
+        r = rt.ggml_backend_mi355x_last_mul_mat_route(backend).decode()
+        assert r.startswith(f"k_mmv_stream<type{T},") and f",ord{order}," in r, (order, r)
+        if order:
+            assert same_bits(y, yr), rel_err(y, yr)
+        else:
+            assert rel_err(y, yr) <= TREE_TOL, rel_err(y, yr)
+
+
 def check_mul_mat_llama_ffn_down_rows(rt, backend, ref, wt):
     """K = 11008 (LLaMA-7B's ffn_down): 43 superblocks or 344 blocks a row, more than two items per lane.
     Q6_K's 9030-byte and Q3_K's 4730-byte rows start 2 mod 4 every other row, Q2_K's 3612-byte rows
@@ -605,6 +622,36 @@ def check_weight_batch_and_strided_src1(rt, backend, ref, wt, ne11):
         y0 = in_order(rt, 0, lambda: _mul_mat_general(rt, backend, T, wq, w_ne, x, x_ne, permute))
         assert same_bits(y1, yr), (permute, rel_err(y1, yr))
         assert rel_err(y0, yr) <= TREE_TOL, (permute, rel_err(y0, yr))
+
+
+def generic_gemv(wt):
+    """The generic GEMV family (mmv.hip) that serves the type."""
+    return {"q6k": "k_mmv_q6k", "q2k": "k_mmv_q23k", "q3k": "k_mmv_q23k", "iq4xs": "k_mmv_iq4xs"}.get(wt.tag, "k_mmv_q0")
+
+
+def check_generic_gemv_route(rt, backend, ref, wt, ne11):
+    """The type's generic GEMV at the smallest shapes at which its decoder can go wrong, the route asserted.
+    A 3-D weight batch of 2 keeps the streaming GEMV out. N = 5: a partly filled workgroup in tree order
+    and dead row groups in the reference order, rows of every alignment the type has. K: one superblock and
+    two (the reference-order chain); the 32-element blocks three (66-byte Q5_0 rows: the second row 2 mod
+    4), IQ4_NL two and four (its reference order takes even block counts). ne11 1, 3, 9: one column, a
+    ragged chunk, a second chunk. Expected values: the reference CPU; bounds as the neighbouring checks."""
+    lib, cpu = ref
+    T, N, nb = wt.type, 5, 2
+    for K in ((256, 512) if wt.blck == 256 else (64, 128) if wt.tag == "iq4nl" else (96,)):
+        w_ne, x_ne = (K, N, nb, 1), (K, ne11, nb, 1)
+        wq = weights(T, K, N * nb, 311)
+        x = synth.uniform(312 + ne11 + K, K * ne11 * nb)
+        yr = _mul_mat_general(lib, cpu, T, wq, w_ne, x, x_ne, False)
+        for order in (1, 0):
+            y = in_order(rt, order, lambda: _mul_mat_general(rt, backend, T, wq, w_ne, x, x_ne, False))
+            r = rt.ggml_backend_mi355x_last_mul_mat_route(backend).decode()
+            nc = 8 if ne11 >= 5 else 4 if ne11 == 3 and order else ne11
+            assert r == f"{generic_gemv(wt)}{'_ord' if order else ''}<nc{nc}>", (K, order, r)
+            if order:
+                assert same_bits(y, yr), (K, rel_err(y, yr))
+            else:
+                assert rel_err(y, yr) <= TREE_TOL, (K, rel_err(y, yr))
 
 
 def check_prequantized_src1(rt, backend, ref, wt, B):
