@@ -47,7 +47,7 @@ struct mi_type_info {
     // routes
     int mmv_variant;   // streaming decode GEMV (mi_mul_mat_q_fused): its default mmv_variant, 0: no such kernel
     int mmv_align;     // ... and the weight row alignment it needs (the tensor base: 16)
-    bool mmqx;         // exact int8 prefill GEMM (mmq_exact.hip; Q6_K: mmq_q6k.hip)
+    bool mmqx;         // exact int8 prefill GEMM (mmq_exact.hip; Q6_K: mmq_q6k.hip; IQ4_XS: mmq_iq4xs.hip)
     bool planes;       // repacked MFMA planes for long prompts (mmq_planes.hip k_mmqr)
     bool aligned_copy; // 16-byte-aligned decode copy (mmq_planes.hip k_q40_repack / k_q80_repack): as many bytes a row as the blocks
     bool get_rows;     // GET_ROWS reads it (f32 / f16 elements, or the dequantizer of ops.hip)
@@ -88,7 +88,7 @@ constexpr mi_type_info kMiTypes[] = {
     {MI_TYPE_Q5_K,   256, 176, MI_ACT_Q8_K, false, false, 0,   false, 21,  16,   true,  false, false, true},
     {MI_TYPE_Q6_K,   256, 210, MI_ACT_Q8_K, false, false, 0,   false, 21,  2,    true,  false, false, true},
     {MI_TYPE_IQ4_NL, 32,  18,  MI_ACT_Q8_0, false, false, 0,   true,  21,  16,   false, false, false, true},
-    {MI_TYPE_IQ4_XS, 256, 136, MI_ACT_Q8_K, false, false, 0,   true,  21,  8,    false, false, false, true},
+    {MI_TYPE_IQ4_XS, 256, 136, MI_ACT_Q8_K, false, false, 0,   true,  21,  8,    true,  false, false, true},
 };
 constexpr mi_type_info kMiNoType = {-1, 1, 0, MI_ACT_NONE, false, false, 0, false, 0, 16, false, false, false, false};
 
