@@ -127,7 +127,7 @@ void invalidate_activations(mi_backend_ctx * ctx, const ggml_tensor * written) {
 // quantized shape the exact GEMM refuses (a row stride that is no multiple of 16 bytes, say), runs
 // the prompt on its GEMV in 8-column chunks. So does every Q6_K or IQ4_XS prompt of a reference-order graph,
 // split slices and pre-quantized src1 included: there the types are held to the reference CPU's bits,
-// and their GEMMs (mmq_q6k.hip, mmq_iq4xs.hip) fold the exact block sums in their own order.
+// and their GEMMs (mmq_sub.hip) fold the exact block sums in their own order.
 static bool mm_batched(const mi_mm_desc & m, const ggml_tensor * src1) {
     if ((m.type == GGML_TYPE_Q6_K || m.type == GGML_TYPE_IQ4_XS) && mi_mmv_order() == 1) return false;
     if (mi_env().no_mmq || src1->ne[1] <= 8 || m.ne02 != 1 || m.ne03 != 1 || m.ne12 != 1 || m.ne13 != 1 || ((uintptr_t) m.W % 16) != 0) return false;
@@ -251,7 +251,7 @@ static void mul_mat_run(mi_backend_ctx * ctx, const ggml_tensor * src0, const vo
             case MI_LAYOUT_SOA:  // the GEMVs, at any column count
                 mi_mul_mat_q(m, mi_act_q8_carve(xa, m.K, ncols, f.quant), ctx->stream);
                 break;
-            case MI_LAYOUT_MFMA:  // Q4_K / Q5_K / Q6_K / Q4_0 / Q8_0: the exact-integer int8 MFMA GEMMs (mmq_exact.hip, mmq_q6k.hip)
+            case MI_LAYOUT_MFMA:  // Q4_K / Q5_K / Q6_K / Q4_0 / Q8_0: the exact-integer int8 MFMA GEMMs (mmq_exact.hip, mmq_sub.hip)
                 mi_mul_mat_mmqx(m.type, m.W, m.nb01, m.K, m.N, mmx_carve(f.quant, xa, m.K, ncols), m.dst, m.nb1, ctx->stream,
                                 W == src0->data && N == src0->ne[1] ? planes_of(ctx, src0, src1) : nullptr);
                 break;

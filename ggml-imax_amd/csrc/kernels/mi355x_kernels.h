@@ -216,7 +216,7 @@ bool mi_mmf16p_supported(int64_t K, int64_t N, size_t nb01, int64_t ncols, size_
 void mi_mul_mat_f16p(const void * W, size_t nb01, int64_t K, int64_t N, const uint16_t * xh, int64_t ncols, float * dst, size_t ycol,
                      hipStream_t s);
 
-// ---- exact-integer prefill GEMM for Q4_K / Q5_K (mmq_exact.hip), Q6_K (mmq_q6k.hip) and IQ4_XS (mmq_iq4xs.hip) ----
+// ---- exact-integer prefill GEMM for Q4_K / Q5_K (mmq_exact.hip), Q6_K and IQ4_XS (mmq_sub.hip) ----
 // q8_K activation quants in the int8-MFMA layouts: xq [K/64][ncols][64] int8, xd [K/256][ncols]
 // f32 scale, xu [K/256][ncols][16] f16 (S_j & 63, S_j >> 6; S_j = sum of the 32 quants of
 // sub-block j) -- the bytes of quantize_row_q8_K_reference, rearranged
@@ -273,10 +273,9 @@ struct mi_mmx_group {
     mi_mmx_member m[kMiMaxPrefillMembers];
 };
 void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s);
-// its Q6_K members (mmq_q6k.hip: k_mmq6p / k_mmq6x); dst_local: every output is this device's memory
-void mi_mmq6_group(mi_mmx_group & g, hipStream_t s, bool dst_local);
-// its IQ4_XS members (mmq_iq4xs.hip: k_mmqi4p / k_mmqi4x)
-void mi_mmqi4_group(mi_mmx_group & g, hipStream_t s, bool dst_local);
+// its Q6_K (k_mmq6p / k_mmq6x) or IQ4_XS (k_mmqi4p / k_mmqi4x) members (mmq_sub.hip); dst_local: every
+// output is this device's memory
+void mi_mmqs_group(mi_mmx_group & g, hipStream_t s, bool dst_local);
 // one member
 void mi_mul_mat_mmqx(int type, const void * W, size_t nb01, int64_t K, int64_t N, const mi_act_mmx & act, float * dst,
                      size_t ycol, hipStream_t s, const char * planes = nullptr);

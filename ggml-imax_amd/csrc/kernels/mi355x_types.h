@@ -47,7 +47,7 @@ struct mi_type_info {
     // routes
     int mmv_variant;   // streaming decode GEMV (mi_mul_mat_q_fused): its default mmv_variant, 0: no such kernel
     int mmv_align;     // ... and the weight row alignment it needs (the tensor base: 16)
-    bool mmqx;         // exact int8 prefill GEMM (mmq_exact.hip; Q6_K: mmq_q6k.hip; IQ4_XS: mmq_iq4xs.hip)
+    bool mmqx;         // exact int8 prefill GEMM (mmq_exact.hip; Q6_K, IQ4_XS: mmq_sub.hip)
     bool planes;       // repacked MFMA planes for long prompts (mmq_planes.hip k_mmqr)
     bool aligned_copy; // 16-byte-aligned decode copy (mmq_planes.hip k_q40_repack / k_q80_repack): as many bytes a row as the blocks
     bool get_rows;     // GET_ROWS reads it (f32 / f16 elements, or the dequantizer of ops.hip)

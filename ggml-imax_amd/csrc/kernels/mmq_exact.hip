@@ -1624,27 +1624,17 @@ bool mi_mmqx_supported(int type, int64_t K, size_t ycol, int64_t ncols, size_t n
     if (mi_type(type).blck == 32) {
         return K % 256 == 0 && K >= 256 && nb01 % 16 == 0 && ycol % 16 == 0 && K * ncols < ((int64_t) 1 << 31) && (int64_t) nb01 * 32 < ((int64_t) 1 << 31);
     }
-    // Q6_K (mmq_q6k.hip): 32-row tiles, rows of any (2-byte) alignment; it stores single floats, so
+    // Q6_K (mmq_sub.hip): 32-row tiles, rows of any (2-byte) alignment; it stores single floats, so
     // any column stride of whole floats
     if (type == MI_TYPE_Q6_K) {
         return K % 256 == 0 && K >= 256 && ycol % sizeof(float) == 0 && K * ncols < ((int64_t) 1 << 31) && (int64_t) nb01 * 32 + 8 < ((int64_t) 1 << 31);
     }
-    // IQ4_XS (mmq_iq4xs.hip): 32-row tiles of dword-aligned rows (blocks are 34 dwords), single-float stores
+    // IQ4_XS (mmq_sub.hip): 32-row tiles of dword-aligned rows (blocks are 34 dwords), single-float stores
     if (type == MI_TYPE_IQ4_XS) {
         return K % 256 == 0 && K >= 256 && nb01 % 4 == 0 && ycol % sizeof(float) == 0 && K * ncols < ((int64_t) 1 << 31) && (int64_t) nb01 * 32 < ((int64_t) 1 << 31);
     }
     return K % 256 == 0 && K >= 256 && ycol % 16 == 0 && K * ncols < ((int64_t) 1 << 31) &&
            (int64_t) nb01 * XBM < ((int64_t) 1 << 31);
-}
-
-// tiles of every member for a tile shape of tr rows x tc columns; returns the total
-static int64_t mmx_deal(mi_mmx_group & g, int64_t tr, int64_t tc) {
-    int64_t t = 0;
-    for (int i = 0; i < g.n; i++) {
-        g.m[i].tile_begin = t;
-        t += ((g.m[i].N + tr - 1) / tr) * ((g.m[i].act.ncols + tc - 1) / tc);
-    }
-    return t;
 }
 
 // Q4_0 / Q8_0 (q8_0 activations, mi_act_mmx0_*), every column count. By workgroup count: 64 x 128
@@ -1721,8 +1711,7 @@ void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
     if (g.n <= 0) return;
     MI_ASSERT(mi_type(g.type).mmqx);
     if (mi_type(g.type).blck == 32) return mmq0_group(g, s);
-    if (g.type == MI_TYPE_Q6_K) return mi_mmq6_group(g, s, mmx_dst_local(g));
-    if (g.type == MI_TYPE_IQ4_XS) return mi_mmqi4_group(g, s, mmx_dst_local(g));
+    if (g.type == MI_TYPE_Q6_K || g.type == MI_TYPE_IQ4_XS) return mi_mmqs_group(g, s, mmx_dst_local(g));
     const bool q4 = g.type == MI_TYPE_Q4_K;
     const int S = (int) (g.K / 256);
     const int64_t ncols = g.m[0].act.ncols;  // every member has the same column count

@@ -172,6 +172,17 @@ struct XRaw {
     const size_t ycol = (g).m[mmx_i_].ycol;                                                \
     (void) nb01; (void) N; (void) dst; (void) ycol
 
+// The launcher's side of it: deals the tiles of every member for a tile shape of tr rows x tc
+// columns; returns the total
+inline int64_t mmx_deal(mi_mmx_group & g, int64_t tr, int64_t tc) {
+    int64_t t = 0;
+    for (int i = 0; i < g.n; i++) {
+        g.m[i].tile_begin = t;
+        t += ((g.m[i].N + tr - 1) / tr) * ((g.m[i].act.ncols + tc - 1) / tc);
+    }
+    return t;
+}
+
 // LDS-DMA of 16 (4) bytes per lane: lane l's bytes land at LDS byte address lds + 16 l (4 l). As
 // inline asm, outside the compiler's wait bookkeeping: with the builtin, hipcc treats the DMA as a
 // pending write to any LDS address and waits vmcnt(0) before the next LDS read -- the current

@@ -1,4 +1,4 @@
-"""IQ4_XS prompts on the int8-MFMA GEMM (mmq_iq4xs.hip: k_mmqi4p, k_mmqi4x) in tree order: the route, exact
+"""IQ4_XS prompts on the int8-MFMA GEMM (mmq_sub.hip: k_mmqi4p, k_mmqi4x) in tree order: the route, exact
 integers from hand-made rows, the saturated ends of the integer ranges, the reference CPU, and the one
 canonical fold (both shapes, grouped launches and column shards give the same bits).
 

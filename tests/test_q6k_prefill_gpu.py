@@ -1,4 +1,4 @@
-"""Q6_K prompts on the int8-MFMA GEMM (mmq_q6k.hip: k_mmq6p, k_mmq6x) in tree order: the route, exact
+"""Q6_K prompts on the int8-MFMA GEMM (mmq_sub.hip: k_mmq6p, k_mmq6x) in tree order: the route, exact
 integers from hand-made rows, the saturated ends of the integer ranges, the reference CPU, and the one
 canonical fold (both shapes, grouped launches and column shards give the same bits).
 

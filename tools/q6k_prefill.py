@@ -1,4 +1,4 @@
-"""Q6_K or IQ4_XS prompt mul_mats in tree order: the type's int8-MFMA GEMM (mmq_q6k.hip, mmq_iq4xs.hip)
+"""Q6_K or IQ4_XS prompt mul_mats in tree order: the type's int8-MFMA GEMM (mmq_sub.hip)
 against the 8-column chunks of the decode GEMV (tree_prefill_cols INT_MAX: the route every prompt of
 the type took before its GEMM existed), alternated in one process. Graphs of R rotated weights (> 288
 MiB per step, above the Infinity Cache), HIP events, us per mul_mat. Every setting is measured REPS
