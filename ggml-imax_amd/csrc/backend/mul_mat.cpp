@@ -125,11 +125,12 @@ void invalidate_activations(mi_backend_ctx * ctx, const ggml_tensor * written) {
 // a batched (prompt) GEMM applies: more than 8 columns of plain 2-D operands that the F16 GEMMs
 // (mmq.hip) resp. the exact int8 GEMMs (mmq_exact.hip) accept. Every other weight type, and a
 // quantized shape the exact GEMM refuses (a row stride that is no multiple of 16 bytes, say), runs
-// the prompt on its GEMV in 8-column chunks. So does every Q6_K or IQ4_XS prompt of a reference-order graph,
-// split slices and pre-quantized src1 included: there the types are held to the reference CPU's bits,
+// the prompt on its GEMV in 8-column chunks. So does every Q2_K, Q3_K, Q6_K or IQ4_XS prompt of a reference-order
+// graph, split slices and pre-quantized src1 included: there the types are held to the reference CPU's bits,
 // and their GEMMs (mmq_sub.hip) fold the exact block sums in their own order.
 static bool mm_batched(const mi_mm_desc & m, const ggml_tensor * src1) {
-    if ((m.type == GGML_TYPE_Q6_K || m.type == GGML_TYPE_IQ4_XS) && mi_mmv_order() == 1) return false;
+    const bool sub = m.type == GGML_TYPE_Q2_K || m.type == GGML_TYPE_Q3_K || m.type == GGML_TYPE_Q6_K || m.type == GGML_TYPE_IQ4_XS;
+    if (sub && mi_mmv_order() == 1) return false;
     if (mi_env().no_mmq || src1->ne[1] <= 8 || m.ne02 != 1 || m.ne03 != 1 || m.ne12 != 1 || m.ne13 != 1 || ((uintptr_t) m.W % 16) != 0) return false;
     if (m.type == GGML_TYPE_F16) return mi_mmq_supported(m.K, m.nb01, m.nb1);
     return mi_mmqx_supported(m.type, m.K, m.nb1, src1->ne[1], m.nb01);
@@ -137,7 +138,7 @@ static bool mm_batched(const mi_mm_desc & m, const ggml_tensor * src1) {
 
 // The activation format mul_mat_run converts src1 to for this mul_mat (quant MI_ACT_NONE, F32
 // weights: src1 is read as it lies). Batched (mm_batched): the exact-integer int8 GEMMs' MFMA layouts
-// for Q4_K / Q5_K / Q6_K / IQ4_XS / Q4_0 / Q8_0 prompts, the K-blocked f16 layout for F16 prompts. Everything else: the
+// for Q2_K .. Q6_K / IQ4_XS / Q4_0 / Q8_0 prompts, the K-blocked f16 layout for F16 prompts. Everything else: the
 // weight type's own format (q8 SoA, f16 / bf16 rows) at any column count; the quantized GEMVs run a
 // prompt in 8-column chunks.
 static mi_act_format mm_act_format(const mi_mm_desc & m, const ggml_tensor * src1) {
@@ -251,7 +252,7 @@ static void mul_mat_run(mi_backend_ctx * ctx, const ggml_tensor * src0, const vo
             case MI_LAYOUT_SOA:  // the GEMVs, at any column count
                 mi_mul_mat_q(m, mi_act_q8_carve(xa, m.K, ncols, f.quant), ctx->stream);
                 break;
-            case MI_LAYOUT_MFMA:  // Q4_K / Q5_K / Q6_K / Q4_0 / Q8_0: the exact-integer int8 MFMA GEMMs (mmq_exact.hip, mmq_sub.hip)
+            case MI_LAYOUT_MFMA:  // Q2_K .. Q6_K / IQ4_XS / Q4_0 / Q8_0: the exact-integer int8 MFMA GEMMs (mmq_exact.hip, mmq_sub.hip)
                 mi_mul_mat_mmqx(m.type, m.W, m.nb01, m.K, m.N, mmx_carve(f.quant, xa, m.K, ncols), m.dst, m.nb1, ctx->stream,
                                 W == src0->data && N == src0->ne[1] ? planes_of(ctx, src0, src1) : nullptr);
                 break;

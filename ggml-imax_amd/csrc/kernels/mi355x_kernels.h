@@ -216,7 +216,7 @@ bool mi_mmf16p_supported(int64_t K, int64_t N, size_t nb01, int64_t ncols, size_
 void mi_mul_mat_f16p(const void * W, size_t nb01, int64_t K, int64_t N, const uint16_t * xh, int64_t ncols, float * dst, size_t ycol,
                      hipStream_t s);
 
-// ---- exact-integer prefill GEMM for Q4_K / Q5_K (mmq_exact.hip), Q6_K and IQ4_XS (mmq_sub.hip) ----
+// ---- exact-integer prefill GEMM for Q4_K / Q5_K (mmq_exact.hip), Q2_K, Q3_K, Q6_K and IQ4_XS (mmq_sub.hip) ----
 // q8_K activation quants in the int8-MFMA layouts: xq [K/64][ncols][64] int8, xd [K/256][ncols]
 // f32 scale, xu [K/256][ncols][16] f16 (S_j & 63, S_j >> 6; S_j = sum of the 32 quants of
 // sub-block j) -- the bytes of quantize_row_q8_K_reference, rearranged
@@ -253,7 +253,7 @@ void mi_quantize_q8_0_mmx_group(mi_mmx_qgroup & q, hipStream_t s);
 void mi_quantize_rows_q8(const mi_src_cols & x, int64_t K, mi_act_quant q, const mi_src_cols & dst, hipStream_t s);
 void mi_q8_rows_to_act(const mi_src_cols & xs, int64_t K, mi_act_quant q, const mi_act_q8 * act, const mi_act_mmx * mx, hipStream_t s);
 bool mi_mmqx_supported(int type, int64_t K, size_t ycol, int64_t ncols, size_t nb01);
-// Independent Q4_K / Q5_K / Q6_K / IQ4_XS (q8_K activations) or Q4_0 / Q8_0 (q8_0 activations, mi_act_mmx0_*)
+// Independent Q2_K .. Q6_K / IQ4_XS (q8_K activations) or Q4_0 / Q8_0 (q8_0 activations, mi_act_mmx0_*)
 // mul_mats (same type, K and activation column count) in one launch:
 // member i = 2-D weights [K, N_i] x act_i.ncols columns -> dst_i (column stride ycol_i bytes)
 struct mi_mmx_member {
@@ -273,8 +273,8 @@ struct mi_mmx_group {
     mi_mmx_member m[kMiMaxPrefillMembers];
 };
 void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s);
-// its Q6_K (k_mmq6p / k_mmq6x) or IQ4_XS (k_mmqi4p / k_mmqi4x) members (mmq_sub.hip); dst_local: every
-// output is this device's memory
+// its Q6_K (k_mmq6p / k_mmq6x), IQ4_XS (k_mmqi4p / k_mmqi4x), Q3_K (k_mmq3p / k_mmq3x) or Q2_K (k_mmq2p /
+// k_mmq2x) members (mmq_sub.hip); dst_local: every output is this device's memory
 void mi_mmqs_group(mi_mmx_group & g, hipStream_t s, bool dst_local);
 // one member
 void mi_mul_mat_mmqx(int type, const void * W, size_t nb01, int64_t K, int64_t N, const mi_act_mmx & act, float * dst,

@@ -47,7 +47,7 @@ struct mi_type_info {
     // routes
     int mmv_variant;   // streaming decode GEMV (mi_mul_mat_q_fused): its default mmv_variant, 0: no such kernel
     int mmv_align;     // ... and the weight row alignment it needs (the tensor base: 16)
-    bool mmqx;         // exact int8 prefill GEMM (mmq_exact.hip; Q6_K, IQ4_XS: mmq_sub.hip)
+    bool mmqx;         // exact int8 prefill GEMM (mmq_exact.hip; Q2_K, Q3_K, Q6_K, IQ4_XS: mmq_sub.hip)
     bool planes;       // repacked MFMA planes for long prompts (mmq_planes.hip k_mmqr)
     bool aligned_copy; // 16-byte-aligned decode copy (mmq_planes.hip k_q40_repack / k_q80_repack): as many bytes a row as the blocks
     bool get_rows;     // GET_ROWS reads it (f32 / f16 elements, or the dequantizer of ops.hip)
@@ -82,8 +82,8 @@ constexpr mi_type_info kMiTypes[] = {
     {MI_TYPE_Q5_0,   32,  22,  MI_ACT_Q8_0, false, true,  16,  false, 21,  16,   false, false, false, true},
     {MI_TYPE_Q5_1,   32,  24,  MI_ACT_Q8_1, true,  true,  0,   false, 21,  16,   false, false, false, true},
     {MI_TYPE_Q8_0,   32,  34,  MI_ACT_Q8_0, false, false, 0,   false, 11,  16,   true,  false, true,  true},
-    {MI_TYPE_Q2_K,   256, 84,  MI_ACT_Q8_K, false, false, 0,   false, 21,  4,    false, false, false, true},
-    {MI_TYPE_Q3_K,   256, 110, MI_ACT_Q8_K, false, false, 0,   false, 11,  2,    false, false, false, true},
+    {MI_TYPE_Q2_K,   256, 84,  MI_ACT_Q8_K, false, false, 0,   false, 21,  4,    true,  false, false, true},
+    {MI_TYPE_Q3_K,   256, 110, MI_ACT_Q8_K, false, false, 0,   false, 11,  2,    true,  false, false, true},
     {MI_TYPE_Q4_K,   256, 144, MI_ACT_Q8_K, false, false, 0,   false, 31,  16,   true,  true,  false, true},
     {MI_TYPE_Q5_K,   256, 176, MI_ACT_Q8_K, false, false, 0,   false, 21,  16,   true,  false, false, true},
     {MI_TYPE_Q6_K,   256, 210, MI_ACT_Q8_K, false, false, 0,   false, 21,  2,    true,  false, false, true},

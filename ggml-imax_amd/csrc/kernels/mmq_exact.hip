@@ -1624,13 +1624,13 @@ bool mi_mmqx_supported(int type, int64_t K, size_t ycol, int64_t ncols, size_t n
     if (mi_type(type).blck == 32) {
         return K % 256 == 0 && K >= 256 && nb01 % 16 == 0 && ycol % 16 == 0 && K * ncols < ((int64_t) 1 << 31) && (int64_t) nb01 * 32 < ((int64_t) 1 << 31);
     }
-    // Q6_K (mmq_sub.hip): 32-row tiles, rows of any (2-byte) alignment; it stores single floats, so
+    // Q6_K, Q3_K (mmq_sub.hip): 32-row tiles, rows of any (2-byte) alignment; it stores single floats, so
     // any column stride of whole floats
-    if (type == MI_TYPE_Q6_K) {
+    if (type == MI_TYPE_Q6_K || type == MI_TYPE_Q3_K) {
         return K % 256 == 0 && K >= 256 && ycol % sizeof(float) == 0 && K * ncols < ((int64_t) 1 << 31) && (int64_t) nb01 * 32 + 8 < ((int64_t) 1 << 31);
     }
-    // IQ4_XS (mmq_sub.hip): 32-row tiles of dword-aligned rows (blocks are 34 dwords), single-float stores
-    if (type == MI_TYPE_IQ4_XS) {
+    // IQ4_XS, Q2_K (mmq_sub.hip): 32-row tiles of dword-aligned rows (blocks are 34 / 21 dwords), single-float stores
+    if (type == MI_TYPE_IQ4_XS || type == MI_TYPE_Q2_K) {
         return K % 256 == 0 && K >= 256 && nb01 % 4 == 0 && ycol % sizeof(float) == 0 && K * ncols < ((int64_t) 1 << 31) && (int64_t) nb01 * 32 < ((int64_t) 1 << 31);
     }
     return K % 256 == 0 && K >= 256 && ycol % 16 == 0 && K * ncols < ((int64_t) 1 << 31) &&
@@ -1711,7 +1711,7 @@ void mi_mul_mat_mmqx_group(mi_mmx_group & g, hipStream_t s) {
     if (g.n <= 0) return;
     MI_ASSERT(mi_type(g.type).mmqx);
     if (mi_type(g.type).blck == 32) return mmq0_group(g, s);
-    if (g.type == MI_TYPE_Q6_K || g.type == MI_TYPE_IQ4_XS) return mi_mmqs_group(g, s, mmx_dst_local(g));
+    if (g.type == MI_TYPE_Q6_K || g.type == MI_TYPE_IQ4_XS || g.type == MI_TYPE_Q2_K || g.type == MI_TYPE_Q3_K) return mi_mmqs_group(g, s, mmx_dst_local(g));
     const bool q4 = g.type == MI_TYPE_Q4_K;
     const int S = (int) (g.K / 256);
     const int64_t ncols = g.m[0].act.ncols;  // every member has the same column count

@@ -1,10 +1,13 @@
 // mmq_sub.hip -- batched (prompt / prefill) GGML_OP_MUL_MAT on the gfx950 int8 matrix cores with the
-// reference's exact integer block sums, one MFMA per sub-block: Q6_K (sub_q6k) and IQ4_XS (sub_iq4xs).
+// reference's exact integer block sums, one MFMA per sub-block: Q6_K (sub_q6k), IQ4_XS (sub_iq4xs), Q3_K
+// (sub_q3k) and Q2_K (sub_q2k).
 //
-// Both reference dot products are, per superblock s of 256 weights of a row n and activation column b
-// (Q8_K activations, no mins term),
+// The reference dot products are, per superblock s of 256 weights of a row n and activation column b
+// (Q8_K activations),
 //     y += d_a(b,s) * d_w(n,s) * T,   T = sum_j s_j * D_j,   D_j = sum_e level[j][e] * a[j][e]
-// with s_j the signed scale of sub-block j. s_j level does not fit an int8 operand the way Q4_K's plane
+// with s_j the signed scale of sub-block j; Q2_K alone has a mins term, y -= d_a dmin_w U with U = sum_j
+// m_j bsum_j, which its policy computes exactly from the activation bytes in hand and two more MFMAs per
+// superblock (sub_q23k), t = fma(-dmin_w, U, d_w T) (mmqx_pre). s_j level does not fit an int8 operand the way Q4_K's plane
 // fields do, so the MFMA's K is the sub-block: one MFMA from a zero accumulator is D_j of a 32 x 32 tile
 // (a signed 24-bit operand), and T += s_j * D_j is one v_mad_i32_i24 per accumulator register (exact
 // int32; the bounds are with each format). Per superblock t = fp16(d_w) * (float) T, and the terms are
@@ -24,15 +27,16 @@
 // slot the hardware assigns to (h, i).
 //
 // A format F gives: its block's raw dwords (from memory into a lane's registers, or read from the
-// row's dwords in a stage buffer), d_w and the scales from them, and one phase of the superblock --
-// four sub-blocks, whose activations are requested a phase ahead.
+// row's dwords in a stage buffer), d_w and the scales from them (Head; Q2_K: dmin and the mins too), one
+// phase of the superblock -- four sub-blocks, whose activations are requested a phase ahead -- any state
+// the phases leave for a mins term (Mins, mins_term; empty but for Q2_K) and the superblock's t (term).
 //
 // Two shapes of one template (k_mmqs<F, NT, STAGED>), bit-identical (the same terms, the same fold):
-//   short  (k_mmq6p, k_mmqi4p) short prompts, and any destination that is not local device memory: a
+//   short  (k_mmq6p, k_mmqi4p, k_mmq3p, k_mmq2p) short prompts, and any destination that is not local device memory: a
 //          32 x 32 tile per 4-wave workgroup; wave w computes the canonical groups w and w + 4, the next
 //          superblock's raw dwords requested before the current one's MFMAs; the group sums meet once
 //          in LDS.
-//   long   (k_mmq6x, k_mmqi4x) long prompts: the workgroup (4 waves, 32 rows x 256 columns) stages the
+//   long   (k_mmq6x, k_mmqi4x, k_mmq3x, k_mmq2x) long prompts: the workgroup (4 waves, 32 rows x 256 columns) stages the
 //          raw blocks of its rows for one superblock into LDS once (coalesced aligned dwords,
 //          double-buffered); each wave decodes the rows once per superblock and uses every operand for
 //          its two 32-column tiles; it runs all eight groups itself (cfold_vec_park: the low half's sum
@@ -65,6 +69,14 @@ __device__ __forceinline__ void sub_mad(int (&T)[16], const typename F::Op & xa,
     __builtin_amdgcn_sched_barrier(0);  // one sub-block's accumulator at a time
 }
 
+// A format without a mins term: no state through the phases, t = d_w T
+struct sub_no_mins {
+    template <int NT> struct Mins {};
+    struct NoU {};
+    template <typename M, typename H> static __device__ __forceinline__ NoU mins_term(const M &, const H &, int) { return {}; }
+    template <typename H> static __device__ __forceinline__ float term(int T, NoU, int, float dw, const H &) { return dw * (float) T; }
+};
+
 // Q6_K. Reference: ggml_vec_dot_q6_K_q8_K (src/ggml-quants.c:8730-9310): D_j = sum_{e<16} (q - 32)[16j + e]
 // a[16j + e] with q the 6-bit levels and sc_j the signed 8-bit scales of the sixteen 16-element
 // sub-blocks (sc (q - 32) needs 14 bits). v_mfma_i32_32x32x16_i8: |D_j| <= 16 * 32 * 128 = 2^16, |T| <=
@@ -78,7 +90,7 @@ __device__ __forceinline__ void sub_mad(int (&T)[16], const typename F::Op & xa,
 // every load is an aligned dword, re-aligned with v_alignbyte by the block's own misalignment (0 or 2,
 // from its address): three dwords cover a lane's 8 bytes, five the 16 scales and d. The dword holding
 // d may reach two bytes past the block (the next block, or the buffer's tail slack), as in the GEMV.
-struct sub_q6k {
+struct sub_q6k : sub_no_mins {
     using L = q6k_fmt;
     using Op = long;
     static constexpr int BS = L::BS;
@@ -171,7 +183,7 @@ struct sub_q6k {
     // T += sc_j D_j for the four sub-blocks of quarter qi: its operands op[t][0..1] = the lane's 8 bytes of
     // sub-block j as q - 32 from the nine raw dwords, then tile by tile
     template <int NT, typename Src>
-    static __device__ __forceinline__ void phase(int (&T)[NT][16], const Src & src, const Head & hd, const Op (&xa)[NT][4], int qi, int h, uint32_t off) {
+    static __device__ __forceinline__ void phase(int (&T)[NT][16], Mins<NT> &, const Src & src, const Head & hd, const Op (&xa)[NT][4], int qi, int h, uint32_t off) {
         uint32_t w[9];
         raw_q(w, src, qi, h);
         int op[4][2];
@@ -208,7 +220,7 @@ struct sub_q6k {
 // half of the superblock, sub-blocks 4 hf + t; the scale and d_w come from the block's first two dwords
 // (qd_iq4xs_scale). A staged row takes 36 dwords, the block from the third on, so its quants are
 // 16-byte aligned.
-struct sub_iq4xs {
+struct sub_iq4xs : sub_no_mins {
     using Op = i32x4;
     static constexpr int BS = mi_type(MI_TYPE_IQ4_XS).bytes;  // 136
     static constexpr int kPhases = 2;
@@ -267,7 +279,7 @@ struct sub_iq4xs {
     // T += (ls_ib - 32) D_ib for the four sub-blocks of half hf, each operand (the levels of the low, h =
     // 0, or the high nibbles) decoded once for every tile
     template <int NT, typename Src>
-    static __device__ __forceinline__ void phase(int (&T)[NT][16], const Src & src, const Head & hd, const Op (&xa)[NT][4], int hf, int h, uint32_t) {
+    static __device__ __forceinline__ void phase(int (&T)[NT][16], Mins<NT> &, const Src & src, const Head & hd, const Op (&xa)[NT][4], int hf, int h, uint32_t) {
         const int sh = 4 * h;
 #pragma unroll
         for (int t = 0; t < 4; t++) {
@@ -280,6 +292,205 @@ struct sub_iq4xs {
         }
     }
 };
+
+// Q3_K (sub_q3k) and Q2_K (sub_q2k). References: ggml_vec_dot_q3_K_q8_K (src/ggml-quants.c:6001-6103), D_j =
+// sum_{e<16} (q - (hbit ? 0 : 4))[16j + e] a[16j + e] with levels in -4..3 and s_j = sc_j - 32 in -32..31:
+// |D_j| <= 16 * 4 * 128 = 2^13, |T| <= 16 * 32 * 2^13 = 2^22; ggml_vec_dot_q2_K_q8_K (:5105-5169), levels q in
+// 0..3, s_j = sc_j & 15, and the mins m_j = sc_j >> 4: |T| <= 16 * 15 * 16 * 3 * 128 < 2^21,
+//     t = d_w T - dmin_w U,   U = sum_j m_j bsum_j,   bsum_j = sum_{e<16} a[16j + e]
+// (mmqx_pre, the Q4_K family's form). v_mfma_i32_32x32x16_i8 as Q6_K.
+//
+// Decode (quant_decode.h: q23k_fmt, qd_q23k_levels): both pack the quants as Q6_K packs ql, so a phase is
+// Q6_K's quarter (hq = qi / 2, u = qi % 2): the lane's 8 bytes of qs at 32 hq + 16u + 8h (Q3_K: and of hmask
+// at 16u + 8h, the same for both hq) are the elements 8h .. 8h + 7 of the four sub-blocks j = 8 hq + 2t + u,
+// whose activations are the 8 bytes at 16u + 8h of 32-block 4 hq + t: sub_q6k's load_act and act_blk.
+// Q3_K blocks are 110 = 4 * 27 + 2 bytes, only 2-byte aligned, rows of an odd superblock count 2 mod 4:
+// aligned dwords re-aligned with v_alignbyte as in sub_q6k, three covering a lane's 8 bytes, four the 12
+// scale bytes and d. The 28 aligned dwords from a block's dword cover it at either misalignment (2 + 110 =
+// 112 = 4 * 28); from an aligned block they end 2 bytes past it, inside the next block or the whole dword
+// of slack that follows the tile's rows, as sub_q6k's. The scales are unpacked once per superblock
+// into four dwords of int8 (qd_q3k_scales4), one v_bfe_i32 per sub-block. A staged row takes 29 dwords: an
+// odd stride, as Q6_K's 53 and Q2_K's 21 are, so the 32 rows' same dword falls into 32 different banks.
+// Q2_K blocks are 84 = 4 * 21 bytes of rows that are whole dwords (nb01 % 4 == 0): nothing is re-aligned,
+// the scale is one v_bfe_u32 of the block's own dword.
+//
+// Q2_K's mins term is exact and needs no activation plane: lane (c, h) holds 8 of the 16 activation
+// bytes of sub-block j of column c, so two v_dot4 against 0x02020202 are 2 P, P[j][h] their sum (|P| <=
+// 1024) and bsum_j = P[j][0] + P[j][1]. P = 128 (P >> 7) + (P & 127) is two int8: byte 1 of 2 P and half
+// of its byte 0, which v_perm_b32 gathers for the four sub-blocks of a phase into one dword each
+// (Mins: hi[qi], lo[qi], byte t). After the phases two v_mfma_i32_32x32x32_i8 per tile, A = the sixteen
+// P parts of the lane's column and half, B = the sixteen m_j of the lane's row in the same slots (qi, t)
+// in both halves (Head::mn, qd_q2k_range4), give U = 128 U_hi + U_lo: the K slots sum over (j, h), so U
+// comes out whatever K slot the hardware gives a byte. |U| <= 16 * 15 * 16 * 128 < 2^19: exact in f32.
+template <int NT> struct q2k_mins {
+    uint32_t hi[NT][4], lo[NT][4];
+};
+template <int TYPE>
+struct sub_q23k : sub_no_mins {
+    using L = q23k_fmt<TYPE>;
+    static constexpr bool Q3 = L::Q3;
+    using Op = long;
+    static constexpr int BS = L::BS;
+    static constexpr int kPhases = 4;
+    static constexpr int kSlack = Q3 ? 4 : 0;                // Q3_K: the dword holding the last block's d
+    static constexpr int kLoadDw = Q3 ? 28 : 21;             // aligned dwords of a block: 2 + 110 = 4 * 28; 84 = 4 * 21
+    static constexpr int kRowDw = Q3 ? 29 : 21, kBlkDw = 0;  // a staged row: those dwords, an odd count of them
+    static constexpr int NQ = Q3 ? 3 : 2;  // aligned dwords covering a lane's 8 bytes
+    static constexpr int NS = Q3 ? 4 : 5;  // ... the 12 scale bytes and d; Q2_K: the 16 scale bytes, d | dmin
+    static_assert(Q3 ? BS % 4 == 2 && 4 * kLoadDw == BS + 2 : 4 * kLoadDw == BS, "the aligned dwords of a block");
+    // Prompts of up to 128 columns: the short shape; longer ones: the long shape (profiles/q2k_q3k_prefill.txt, us
+    // per mul_mat, short / long. k_mmq3p / k_mmq3x: 4096 x 4096 B = 64 7.8 / 19.1, B = 128 13.1 / 19.5, B = 512 46.4 /
+    // 38.0; 11008 x 4096 B = 64 19.9 / 52.4, B = 128 34.3 / 53.7, B = 512 118.9 / 98.2. k_mmq2p / k_mmq2x: 4096 x 4096
+    // B = 64 10.3 / 20.5, B = 128 18.9 / 21.0, B = 512 70.0 / 41.1; 11008 x 4096 B = 64 21.3 / 52.2, B = 128 39.3 / 53.2,
+    // B = 512 149.0 / 104.5: the short shape wins by 1.1-1.6x at 128, the long one by 1.2-1.7x at 512; nothing
+    // between them was measured. The 8-column GEMV chunks every prompt of these types took before: 56-61 and
+    // 149-150 at B = 64, 335-385 and 903-935 at B = 512.)
+    static constexpr int64_t kShortCols = 128;
+    static constexpr const char * kShort = Q3 ? "k_mmq3p" : "k_mmq2p", * kLong = Q3 ? "k_mmq3x" : "k_mmq2x";
+
+    static __device__ __forceinline__ uint32_t mis(uint32_t a) { return Q3 ? a & 2 : 0; }
+    static __device__ __forceinline__ int sb_odd(int sb) { return Q3 ? 2 * (sb & 1) : 0; }
+    static __device__ __forceinline__ int lds_slot(int, int row, int dw) { return row * kRowDw + dw; }
+
+    // block byte offset of a quarter's qs dwords and of a range's hmask dwords, half 0
+    static __device__ __forceinline__ constexpr int qs(int qi) { return L::QS + 32 * (qi >> 1) + 16 * (qi & 1); }
+    static __device__ __forceinline__ constexpr int hm(int u) { return 16 * u; }
+
+    // a lane's raw dwords of one superblock: per quarter those covering its 8 bytes of qs, per range
+    // those of hmask (Q3_K), and the scales' and d's
+    struct Raw {
+        uint32_t q[4][NQ];
+        uint32_t hm[2][NQ];
+        uint32_t s[NS];
+    };
+    struct Head {
+        uint32_t sc[4];  // Q3_K: sc - 32 as int8, byte j; Q2_K: the scale bytes as they lie (sc | m << 4)
+        uint32_t mn[4];  // Q2_K: the mins in slot order, byte t of dword qi
+        float dm;        // Q2_K: dmin
+    };
+    // the phases' sums of the lane's activation bytes (Q2_K), split into two int8, slot order
+    template <int NT> using Mins = std::conditional_t<Q3, sub_no_mins::Mins<NT>, q2k_mins<NT>>;
+    static __device__ __forceinline__ void load_raw(Raw & o, __amdgpu_buffer_rsrc_t wres, uint32_t vo, int h, uint32_t so) {
+#pragma unroll
+        for (int i = 0; i < NQ; i++) {
+#pragma unroll
+            for (int qi = 0; qi < 4; qi++) o.q[qi][i] = __builtin_amdgcn_raw_buffer_load_b32(wres, vo + 8 * h + qs(qi) + 4 * i, so, 0);
+#pragma unroll
+            for (int u = 0; u < 2; u++) o.hm[u][i] = Q3 ? __builtin_amdgcn_raw_buffer_load_b32(wres, vo + 8 * h + hm(u) + 4 * i, so, 0) : 0u;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) o.s[i] = __builtin_amdgcn_raw_buffer_load_b32(wres, vo + L::SC + 4 * i, so, 0);
+        if constexpr (!Q3) o.s[4] = __builtin_amdgcn_raw_buffer_load_b32(wres, vo + L::D, so, 0);
+    }
+    // the raw dwords of the scales and d, of quarter qi's quants and of its hmask range, from a lane's
+    // registers or from its row in a stage buffer
+    static __device__ __forceinline__ void raw_s(uint32_t (&s)[NS], const Raw & o) {
+#pragma unroll
+        for (int i = 0; i < NS; i++) s[i] = o.s[i];
+    }
+    static __device__ __forceinline__ void raw_s(uint32_t (&s)[NS], const uint32_t * blk) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) s[i] = blk[L::SC / 4 + i];
+        if constexpr (!Q3) s[4] = blk[L::D / 4];
+    }
+    static __device__ __forceinline__ void raw_q(uint32_t (&w)[2][NQ], const Raw & o, int qi, int) {
+#pragma unroll
+        for (int i = 0; i < NQ; i++) {
+            w[0][i] = o.q[qi][i];
+            w[1][i] = o.hm[qi & 1][i];
+        }
+    }
+    static __device__ __forceinline__ void raw_q(uint32_t (&w)[2][NQ], const uint32_t * blk, int qi, int h) {
+#pragma unroll
+        for (int i = 0; i < NQ; i++) {
+            w[0][i] = blk[qs(qi) / 4 + 2 * h + i];
+            w[1][i] = Q3 ? blk[hm(qi & 1) / 4 + 2 * h + i] : 0u;
+        }
+    }
+
+    // the scales (and Q2_K's mins and dmin) of a superblock, and d; off: the block's misalignment
+    template <typename Src>
+    static __device__ __forceinline__ float head(Head & hd, const Src & src, uint32_t off) {
+        uint32_t s[NS];
+        raw_s(s, src);
+        if constexpr (Q3) {
+            uint32_t a[3];
+#pragma unroll
+            for (int i = 0; i < 3; i++) a[i] = __builtin_amdgcn_alignbyte(s[i + 1], s[i], off);
+#pragma unroll
+            for (int g = 0; g < 4; g++) hd.sc[g] = qd_q3k_scales4(a[0], a[1], a[2], g);
+            return mi_h2f((uint16_t) ((s[3] >> (8 * off)) & 0xFFFF));
+        } else {
+#pragma unroll
+            for (int qi = 0; qi < 4; qi++) {
+                hd.sc[qi] = s[qi];
+                hd.mn[qi] = qd_nib_hi(qd_q2k_range4(s[2 * (qi >> 1)], s[2 * (qi >> 1) + 1], qi & 1));
+            }
+            hd.dm = mi_h2f((uint16_t) (s[4] >> 16));
+            return mi_h2f((uint16_t) (s[4] & 0xFFFF));
+        }
+    }
+    static __device__ __forceinline__ Op load_act(__amdgpu_buffer_rsrc_t xres, uint32_t vo, uint32_t so, int qi, int h) {
+        return sub_q6k::load_act(xres, vo, so, qi, h);
+    }
+    static __device__ __forceinline__ constexpr int act_blk(int qi, int t) { return sub_q6k::act_blk(qi, t); }
+    static __device__ __forceinline__ i32x16 mfma(Op xa, Op b) { return sub_q6k::mfma(xa, b); }
+
+    // T += s_j D_j for the four sub-blocks of quarter qi: its operands op[t][0..1] = the lane's 8 bytes of
+    // sub-block j as levels, then tile by tile; Q2_K: and the tile's P parts of the quarter
+    template <int NT, typename Src>
+    static __device__ __forceinline__ void phase(int (&T)[NT][16], Mins<NT> & ms, const Src & src, const Head & hd, const Op (&xa)[NT][4], int qi, int h, uint32_t off) {
+        uint32_t w[2][NQ];
+        raw_q(w, src, qi, h);
+        int op[4][2];
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const uint32_t q = Q3 ? __builtin_amdgcn_alignbyte(w[0][i + 1], w[0][i], off) : w[0][i];
+            const uint32_t hb = Q3 ? __builtin_amdgcn_alignbyte(w[1][i + 1], w[1][i], off) : 0u;
+#pragma unroll
+            for (int t = 0; t < 4; t++) op[t][i] = qd_q23k_levels<Q3>(q, hb, qi >> 1, t);
+        }
+#pragma unroll
+        for (int ct = 0; ct < NT; ct++) {
+            int p2[4];  // 2 P of the four sub-blocks
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const int j = 8 * (qi >> 1) + 2 * t + (qi & 1);
+                const long b = (long) (((unsigned long) (uint32_t) op[t][1] << 32) | (uint32_t) op[t][0]);
+                const int s = Q3 ? __builtin_amdgcn_sbfe(hd.sc[j >> 2], 8 * (j & 3), 8) : (int) __builtin_amdgcn_ubfe(hd.sc[j >> 2], 8 * (j & 3), 4);
+                sub_mad<sub_q23k>(T[ct], xa[ct][t], b, s);
+                if constexpr (!Q3) p2[t] = mi_dot4(0x02020202, (int) xa[ct][t], mi_dot4(0x02020202, (int) (xa[ct][t] >> 32), 0));
+            }
+            if constexpr (!Q3) {
+                // bytes 0 and 1 of p2[0..3]: [t0.b0 t1.b0 t0.b1 t1.b1] of each pair, then the b0s and the b1s
+                const uint32_t p01 = __builtin_amdgcn_perm((uint32_t) p2[1], (uint32_t) p2[0], 0x05010400u);
+                const uint32_t p23 = __builtin_amdgcn_perm((uint32_t) p2[3], (uint32_t) p2[2], 0x05010400u);
+                ms.lo[ct][qi] = (__builtin_amdgcn_perm(p23, p01, 0x05040100u) >> 1) & 0x7F7F7F7Fu;
+                ms.hi[ct][qi] = __builtin_amdgcn_perm(p23, p01, 0x07060302u);
+            }
+        }
+    }
+    // U of tile ct (Q2_K): 128 U_hi + U_lo
+    template <typename M>
+    static __device__ __forceinline__ auto mins_term(const M & ms, const Head & hd, int ct) {
+        if constexpr (Q3) {
+            return NoU{};
+        } else {
+            const i32x4 b = {(int) hd.mn[0], (int) hd.mn[1], (int) hd.mn[2], (int) hd.mn[3]};
+            const i32x4 ah = {(int) ms.hi[ct][0], (int) ms.hi[ct][1], (int) ms.hi[ct][2], (int) ms.hi[ct][3]};
+            const i32x4 al = {(int) ms.lo[ct][0], (int) ms.lo[ct][1], (int) ms.lo[ct][2], (int) ms.lo[ct][3]};
+            const i32x16 uh = __builtin_amdgcn_mfma_i32_32x32x32_i8(ah, b, i32x16{}, 0, 0, 0);
+            const i32x16 ul = __builtin_amdgcn_mfma_i32_32x32x32_i8(al, b, i32x16{}, 0, 0, 0);
+            return uh * 128 + ul;
+        }
+    }
+    using sub_no_mins::term;
+    static __device__ __forceinline__ float term(int T, const i32x16 & U, int el, float dw, const Head & hd) {
+        return mmqx_pre(T, (float) U[el], dw, hd.dm);
+    }
+};
+using sub_q3k = sub_q23k<MI_TYPE_Q3_K>;
+using sub_q2k = sub_q23k<MI_TYPE_Q2_K>;
 
 template <typename F, int NT, bool STAGED>
 __global__ __launch_bounds__(256, 2) void k_mmqs(mi_mmx_group grp) {
@@ -370,7 +581,8 @@ __global__ __launch_bounds__(256, 2) void k_mmqs(mi_mmx_group grp) {
     // T of superblock sb from `src` (the lane's registers, or its row in a stage buffer); each phase's
     // activations are requested a phase ahead, the last one requests the first of superblock sn
     using Src = std::conditional_t<STAGED, const uint32_t *, Raw>;
-    auto phases = [&](int (&T)[NT][16], const Src & src, const typename F::Head & hd, int sb, int sn, uint32_t off) {
+    using Mins = typename F::template Mins<NT>;
+    auto phases = [&](int (&T)[NT][16], Mins & ms, const Src & src, const typename F::Head & hd, int sb, int sn, uint32_t off) {
 #pragma unroll
         for (int p = 0; p < NP; p++) {
 #pragma unroll
@@ -378,7 +590,7 @@ __global__ __launch_bounds__(256, 2) void k_mmqs(mi_mmx_group grp) {
                 if (p < NP - 1) load_xa(xa[(p + 1) & 1][ct], sb, p + 1, acol[ct]);
                 else load_xa(xa[0][ct], sn, 0, acol[ct]);
             }
-            F::template phase<NT>(T, src, hd, xa[p & 1], p, h, off);
+            F::template phase<NT>(T, ms, src, hd, xa[p & 1], p, h, off);
         }
     };
 
@@ -417,7 +629,9 @@ __global__ __launch_bounds__(256, 2) void k_mmqs(mi_mmx_group grp) {
                 const float dac = dan;
                 dan = ld_d(sn, acol[0]);
                 int T[1][16] = {};
-                phases(T, cur, hd, sb, sn, off);
+                Mins ms;
+                phases(T, ms, cur, hd, sb, sn, off);
+                const auto U = F::mins_term(ms, hd, 0);
                 f32x16 da;
                 spread_da(da, dac, dal[w][0]);
                 if (first) {  // uniform: a group starts at -0 (-0 + t == t), kept a branch (no selects)
@@ -425,7 +639,7 @@ __global__ __launch_bounds__(256, 2) void k_mmqs(mi_mmx_group grp) {
                     gsum = f32x16(-0.0f);
                 }
 #pragma unroll
-                for (int el = 0; el < 16; el++) gsum[el] = __builtin_fmaf(da[el], dw * (float) T[0][el], gsum[el]);
+                for (int el = 0; el < 16; el++) gsum[el] = __builtin_fmaf(da[el], F::term(T[0][el], U, el, dw, hd), gsum[el]);
                 if (last) {  // the group's sum -> LDS slot of group sb / gs
                     const int gi = sb / gs;
 #pragma unroll
@@ -506,7 +720,8 @@ __global__ __launch_bounds__(256, 2) void k_mmqs(mi_mmx_group grp) {
             typename F::Head hd;
             const float dw = F::head(hd, blk, off);
             int T[NT][16] = {};
-            phases(T, blk, hd, sb, sn, off);
+            Mins ms;
+            phases(T, ms, blk, hd, sb, sn, off);
             // the stage's successor into the other buffer (its readers passed the last barrier), then
             // the request for the one after
             store_stage(st, (sb + 1) & 1);
@@ -516,8 +731,9 @@ __global__ __launch_bounds__(256, 2) void k_mmqs(mi_mmx_group grp) {
                 f32x16 da, tv;
                 spread_da(da, dan[ct], dal[w][ct]);
                 dan[ct] = ld_d(sn, acol[ct]);
+                const auto U = F::mins_term(ms, hd, ct);
 #pragma unroll
-                for (int el = 0; el < 16; el++) tv[el] = dw * (float) T[ct][el];
+                for (int el = 0; el < 16; el++) tv[el] = F::term(T[ct][el], U, el, dw, hd);
                 float * pk = parked + ct * 16 * 64 + lane;
                 cfold_vec_park(gsum[ct], y[ct], tv, da, sb, gs, S, [&](const f32x16 & v) {
 #pragma unroll
@@ -561,6 +777,8 @@ void mmqs_launch(mi_mmx_group & g, hipStream_t s, bool dst_local) {
 
 void mi_mmqs_group(mi_mmx_group & g, hipStream_t s, bool dst_local) {
     if (g.type == MI_TYPE_Q6_K) return mmqs_launch<sub_q6k>(g, s, dst_local);
+    if (g.type == MI_TYPE_Q3_K) return mmqs_launch<sub_q3k>(g, s, dst_local);
+    if (g.type == MI_TYPE_Q2_K) return mmqs_launch<sub_q2k>(g, s, dst_local);
     MI_ASSERT(g.type == MI_TYPE_IQ4_XS);
     mmqs_launch<sub_iq4xs>(g, s, dst_local);
 }

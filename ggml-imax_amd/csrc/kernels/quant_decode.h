@@ -182,6 +182,19 @@ __device__ __forceinline__ int qd_q3k_scale(const uint8_t * scales, int j) {
     const int lo = (scales[j & 7] >> (4 * (j >> 3))) & 0xF;
     return (lo | (((scales[8 + (j & 3)] >> (2 * (j >> 2))) & 3) << 4)) - 32;
 }
+// the same integers for the four sub-blocks 4g .. 4g + 3 at once, as int8x4, from the 12 scale bytes
+// as three little-endian dwords a0 a1 a2
+__device__ __forceinline__ uint32_t qd_q3k_scales4(uint32_t a0, uint32_t a1, uint32_t a2, int g) {
+    const uint32_t lo = (g & 1) ? a1 : a0;
+    return qd_sub_bytes<32>(((g & 2) ? qd_nib_hi(lo) : qd_nib_lo(lo)) | (((a2 >> (2 * g)) & 0x03030303u) << 4));
+}
+
+// Q2_K: the scale | min bytes of the four sub-blocks 8h + 2t + u (t = 0..3: the 16-byte range u of
+// the 128-half h), byte t, from the dwords s0 = scales[8h ..] and s1 = scales[8h + 4 ..]; qd_nib_lo
+// of it are the four scales, qd_nib_hi the four mins
+__device__ __forceinline__ uint32_t qd_q2k_range4(uint32_t s0, uint32_t s1, int u) {
+    return __builtin_amdgcn_perm(s1, s0, u ? 0x07050301u : 0x06040200u);
+}
 
 // ---------------------------------------------------------------- IQ4_XS
 //

@@ -8,6 +8,7 @@ the box.
 
   python tools/q6k_prefill.py            (kept as profiles/q6k_prefill.txt)
   python tools/q6k_prefill.py iq4_xs     (kept as profiles/iq4xs_prefill.txt)
+  python tools/q6k_prefill.py q3_K q2_K  (kept as profiles/q2k_q3k_prefill.txt)
 """
 import os, statistics, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,6 +24,8 @@ REPS = 3
 # setting -> (tree_prefill_cols, mmq_variant)
 SETTINGS = {"q6_K": (("default", 0, 0), ("k_mmq6p", 0, 16), ("k_mmq6x", 0, 128), ("chunks", INT_MAX, 0)),
             "iq4_xs": (("default", 0, 0), ("k_mmqi4p", 0, 16), ("k_mmqi4x", 0, 128), ("chunks", INT_MAX, 0)),
+            "q3_K": (("default", 0, 0), ("k_mmq3p", 0, 16), ("k_mmq3x", 0, 128), ("chunks", INT_MAX, 0)),
+            "q2_K": (("default", 0, 0), ("k_mmq2p", 0, 16), ("k_mmq2x", 0, 128), ("chunks", INT_MAX, 0)),
             "q4_K": (("default", 0, 0), ("chunks", INT_MAX, 0))}
 TYPES = (sys.argv[1:] or ["q6_K"]) + ["q4_K"]
 assert all(t in SETTINGS for t in TYPES), TYPES
