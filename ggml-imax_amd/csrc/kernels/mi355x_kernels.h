@@ -124,6 +124,7 @@ struct mi_mmv_group {
     int pro_off = 0;   // set by the launcher: LDS byte offset of the normalized columns
     int q0r = 0;       // Q4_0 / Q8_0: every member's W is its 16-byte-aligned repacked copy (mi_planes_get), nb01 = K / 32 * the block's bytes
     int pro_q = 0;     // set by the launcher (g_mi_tuning.mmv_pro4): one Q8_K column's norm prologue quantizes from registers
+    int slice_rows = 0;  // set by the launcher: > 0: workgroup rb of a member owns its slices rb, rb + blocks_per_member, ... of this many rows (0: one range of rows_per_block rows)
     mi_mmv_member m[kMiMaxMembers];
     // GGML_OP_MUL_MAT_ID decode (behind m: the other fields keep their places; ncols == 1, no prologue / epilogue): ids_w != nullptr makes every
     // member's W a pointer to its int32 expert id in device memory; the kernel streams
@@ -139,7 +140,7 @@ constexpr int64_t kMiMmvProMaxK = 768;  // norm prologue: the column is held in 
 // a row of the knob table in mmv_fused.hip: set_tuning("<field>", v) and GGML_MI355X_<FIELD>=v pass
 // the same range check.
 struct mi_tuning {
-    int mmv_blocks = 0;    // target resident workgroups for the fused GEMV (all members); 0: from the kernel's residency (hipOccupancy...) per instance
+    int mmv_blocks = 0;    // target resident workgroups for the fused GEMV (all members); 0: from the kernel's residency (hipOccupancy...) per instance, grouped launches in interleaved slices; > 0: always one contiguous row range per workgroup
     int mmv_variant = 0;   // 10*prefetch_depth + {0: activations in VGPRs, 1: from LDS, 2: LDS + waves/EU cap}; 0: the per-type default
     int f16_variant = 0;   // decode F16 GEMV: 0 = 16 lanes per row (k_mmv_f16_w16), 1 = quad per row (k_mmv_f16_x)
     int f16_threads = 0;   // k_mmv_f16_w16 workgroup size override (0 = automatic)

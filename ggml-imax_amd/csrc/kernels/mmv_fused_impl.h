@@ -1768,6 +1768,20 @@ __device__ __forceinline__ void store_out(const mi_mmv_group & g, float * dst, i
 // IDS (GGML_OP_MUL_MAT_ID decode): the member's W field points at its expert id in device memory;
 // the workgroup reads it at entry and streams expert id's matrix of the stack g.ids_w (stride
 // g.ids_nb02). An id outside [0, g.ids_n_as) ends the workgroup here, before any barrier.
+// Sliced (g.slice_rows > 0, instances kStreamSliced only): one resident pass. The member's rows are
+// dealt to its workgroups in interleaved slices of g.slice_rows rows -- workgroup rb owns slices rb,
+// rb + blocks_per_member, ... -- and a wave walks its rows of one slice after the other in one
+// sequence of steps, so the ring runs across the slice boundaries (one prologue, one barrier). Whole
+// rows, each with the arithmetic of the contiguous partition: the same bits.
+// (Q8_0 on its repacked copy, the default; the canonical blocks' 8-column instance would lose a wave
+// per SIMD to the slice bookkeeping's registers.)
+constexpr int kSliceRows = 16;
+template <class F> constexpr bool kFmtSliced = std::is_same<F, FmtKQ<false>>::value || std::is_same<F, FmtKQ<true>>::value ||
+                                               std::is_same<F, FmtQ0Pair>::value || std::is_same<F, FmtQ0R>::value ||
+                                               std::is_same<F, FmtQ8R>::value;
+template <class F, bool TAIL, bool ORD, bool PRO, int MR, bool IDS>
+constexpr bool kStreamSliced = kFmtSliced<F> && !TAIL && !ORD && !PRO && MR == 1 && !IDS;
+
 template <class F, int NC, int PD, int IPL, bool TAIL, bool ORD, bool PRO, int MR = 1, bool IDS = false>
 __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -1792,20 +1806,33 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
 
     // 32-bit row bookkeeping (N < 2^31): scalar compares, no 64-bit VGPR temporaries in the loop
     const int Nr = (int) g.N;
-    const int row_begin = rb * (int) g.rows_per_block;
-    const int row_end = row_begin + (int) g.rows_per_block < Nr ? row_begin + (int) g.rows_per_block : Nr;
-    const int nrows = row_end - row_begin > wave ? (row_end - row_begin - wave + 3) / 4 : 0;
-    auto wrow_of = [&](int k) {
-        const int r = row_begin + 4 * k + wave;
-        return W + (size_t) (r < Nr ? r : Nr - 1) * g.nb01;
-    };
+    constexpr bool SLICED = kStreamSliced<F, TAIL, ORD, PRO, MR, IDS>;
+    // sliced: rows per slice (a multiple of 4), the wave's steps per slice, and the rows between the
+    // wave's last row of a slice and its first of the workgroup's next one, less the usual 4
+    const int SL = SLICED && g.slice_rows ? g.slice_rows : (int) g.rows_per_block;
+    const int row_begin = rb * SL;
+    int nrows, spw = 0x7fffffff, skip = 0;
+    if (SLICED && g.slice_rows) {
+        const int nsl = (Nr + SL - 1) / SL;  // the member's slices; the last one may be short
+        const int cnt = rb < nsl ? (nsl - 1 - rb) / g.blocks_per_member + 1 : 0;
+        const int last = Nr - (rb + (cnt - 1) * g.blocks_per_member) * SL;  // rows from the workgroup's last slice on
+        spw = SL / 4;
+        skip = (g.blocks_per_member - 1) * SL;
+        nrows = cnt > 0 ? (cnt - 1) * spw + (last >= SL ? spw : last > wave ? (last - wave + 3) / 4 : 0) : 0;
+    } else {
+        const int row_end = row_begin + SL < Nr ? row_begin + SL : Nr;
+        nrows = row_end - row_begin > wave ? (row_end - row_begin - wave + 3) / 4 : 0;
+    }
+    auto wrow = [&](int r) { return W + (size_t) (r < Nr ? r : Nr - 1) * g.nb01; };
+    auto step_row = [&](int k) { return row_begin + 4 * k + wave; };  // (one contiguous range)
+    auto wrow_of = [&](int k) { return wrow(step_row(k)); };
 
     // Every load of the ring is unconditional, with clamped row / item indices: a load under a
     // branch makes the compiler merge the ring registers after it, and the merge copy waits for
     // the load just issued (vmcnt(0)), which serialises the prefetch.
     typename F::Regs ring[NB][IPL];
-    auto prefetch = [&](typename F::Regs (&slot)[IPL], int k) {
-        const uint8_t * wr = wrow_of(k);
+    auto prefetch = [&](typename F::Regs (&slot)[IPL], int row) {
+        const uint8_t * wr = wrow(row);
 #pragma unroll
         for (int i = 0; i < IPL; i++) {
             const int item = lane + 64 * i;
@@ -1820,6 +1847,22 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
     };
     const int nsteps = MR > 1 ? (nrows + MR - 1) / MR : nrows;
     const int klast = nsteps > 0 ? nsteps - 1 : 0;
+    // the row of the next step to prefetch (the last step again past the end, as step_row's callers
+    // clamp k), and the rows of the steps in the ring: wave-uniform, kept in scalar registers
+    int pf_row = row_begin + wave, pf_j = 0, pf_k = 0;
+    int rows[NB];
+    auto next_row = [&] {
+        const int r = pf_row;
+        if (pf_k < klast) {
+            pf_k++;
+            pf_row += 4;
+            if (++pf_j == spw) {
+                pf_j = 0;
+                pf_row += skip;
+            }
+        }
+        return r;
+    };
 
     // 0) what the prologue reads first, requested before the weights (vmcnt retires in order: a
     //    use of it would otherwise wait for the weight loads too): the norm prologue's first
@@ -1876,7 +1919,8 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
 #pragma unroll
     for (int u = 0; u < PD; u++) {
         if constexpr (MR > 1) prefetch_mr(ring[u], u < klast ? u : klast);
-        else prefetch(ring[u], u < klast ? u : klast);
+        else if constexpr (SLICED) prefetch(ring[u], rows[u] = next_row());
+        else prefetch(ring[u], step_row(u < klast ? u : klast));
     }
 
     // 2) quantize the member's activation columns into LDS (wave w: 256-slices w, w+4, ...),
@@ -1985,8 +2029,14 @@ __global__ __launch_bounds__(256) void k_mmv_stream(mi_mmv_group g) {
         for (int u = 0; u < NB; u++) {
             const int k = k0 + u;
             if (k >= nrows) break;  // wave-uniform
-            prefetch(ring[(u + PD) % NB], k + PD < klast ? k + PD : klast);
-            const int row = row_begin + 4 * k + wave;
+            int row;
+            if constexpr (SLICED) {
+                row = rows[u];
+                prefetch(ring[(u + PD) % NB], rows[(u + PD) % NB] = next_row());
+            } else {
+                row = step_row(k);
+                prefetch(ring[(u + PD) % NB], step_row(k + PD < klast ? k + PD : klast));
+            }
             if constexpr (ORD) {
                 const int R = g.ord_rows, cs = g.ord_cs, S = g.ord_s;
                 auto sync = [] {
@@ -2179,19 +2229,32 @@ void launch_one(mi_mmv_group g, hipStream_t s) {
     // in its prologue, so at 4 rows per workgroup that redundant work dominates (Q4_K 4096^2 alone
     // in its graph 7.96 -> 6.57 us, profiles/r04e_pf_single_blocks.txt)
     int target = g_mi_tuning.mmv_blocks > 0 ? g_mi_tuning.mmv_blocks : resident_blocks(fn, lds);
-    if (g_mi_tuning.mmv_blocks <= 0 && g.n == 1 && g.K >= 4096) target = std::min(target, mi_cu_count());
-    // Q5_K grouped launches: twice the resident count (smaller workgroups, a later tail; 4096 x 11008
-    // 5.56 -> 5.75 TB/s, r04r_gemv_sweep.txt)
-    // Q4_K tall members (4096 x 11008): the same (5.47-5.49 -> 5.56-5.62 TB/s on one box,
-    // profiles/r05sw_gemv_blocks_sweep.txt; 4096^2 members unchanged within noise, left alone)
-    else if (g_mi_tuning.mmv_blocks <= 0 && !ORD && !PRO &&
-             (std::is_same<F, FmtKQ<true>>::value || (std::is_same<F, FmtKQ<false>>::value && g.N >= 8192))) target *= 2;
-    int bpm = target / g.n;
-    if (bpm < 1) bpm = 1;
-    int64_t rows = (g.N + bpm - 1) / bpm;
-    rows = (rows + 3) / 4 * 4;
-    g.rows_per_block = rows;
-    g.blocks_per_member = (int) ((g.N + rows - 1) / rows);
+    auto rows_at = [&](int t) {
+        const int bpm = std::max(t / g.n, 1);
+        return ((g.N + bpm - 1) / bpm + 3) / 4 * 4;
+    };
+    // grouped launches whose workgroups get more than a slice of rows each: the resident count of
+    // workgroups, the member's rows dealt to them in interleaved slices (see k_mmv_stream). The
+    // workgroups of a member then stream one advancing window of its rows, and their shares differ
+    // by a slice at most. A positive mmv_blocks keeps the contiguous ranges below.
+    g.slice_rows = 0;
+    if (kStreamSliced<F, TAIL, ORD, PRO, MR, IDS> && g_mi_tuning.mmv_blocks <= 0 && g.n > 1 && rows_at(target) > kSliceRows) {
+        g.slice_rows = kSliceRows;
+        g.rows_per_block = kSliceRows;
+        g.blocks_per_member = target / g.n;  // (fewer than the member's slices)
+    } else {
+        if (g_mi_tuning.mmv_blocks <= 0 && g.n == 1 && g.K >= 4096) target = std::min(target, mi_cu_count());
+        // Q5_K grouped launches: twice the resident count (smaller workgroups, a later tail; 4096 x 11008
+        // 5.56 -> 5.75 TB/s, r04r_gemv_sweep.txt)
+        // Q4_K tall members (4096 x 11008): the same (5.47-5.49 -> 5.56-5.62 TB/s on one box,
+        // profiles/r05sw_gemv_blocks_sweep.txt; 4096^2 members unchanged within noise, left alone)
+        // (what of these is not sliced: lone members, long-row, expert-routed and short launches)
+        else if (g_mi_tuning.mmv_blocks <= 0 && !ORD && !PRO &&
+                 (std::is_same<F, FmtKQ<true>>::value || (std::is_same<F, FmtKQ<false>>::value && g.N >= 8192))) target *= 2;
+        const int64_t rows = rows_at(target);
+        g.rows_per_block = rows;
+        g.blocks_per_member = (int) ((g.N + rows - 1) / rows);
+    }
     mi_route(stream_route<F, NC, PD, IPL, TAIL, ORD, PRO, MR, IDS>(g.type));
     hipLaunchKernelGGL((k_mmv_stream<F, NC, PD, IPL, TAIL, ORD, PRO, MR, IDS>), dim3((unsigned) (g.blocks_per_member * g.n)), dim3(256), lds,
                        s, g);
